@@ -3,6 +3,8 @@
 bench.py -- VB iterations/sec of probabilistic PCA (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full   # + steady region, CPU baseline, legs
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR  # + outputs as DIR/*.npy
     python bench.py --config {gmm,masked,lssm}        # the secondary BASELINE configurations
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -18,6 +20,12 @@ on N=1e7 at 1/2/4/8 GPUs).  In the default Gram form the D x D Gram matrix of th
 all-reduced once (RCCL) when the model is set up and an iteration needs no exchange at all;
 in the streaming-statistics form (--stats stream) the child->parent message sums are one
 all-reduce per iteration.
+
+A plain run sets the model up, warms up, times --steps iterations and prints the line.  --full
+adds what the headline figure does not need: the longer steady region, the CPU baseline on the
+whole workload and, at the metric size on one GPU, the secondary configurations under "extra".
+--dump-outputs DIR writes the posterior moments and lower bounds of the last timed iteration
+(see dump_outputs) before anything else runs.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
 """
@@ -60,19 +68,30 @@ def parse():
                    default='pca',
                    help="pca = the BASELINE.json metric (default); the others print the "
                         "secondary configurations of tools/workloads.py as the JSON line")
+    p.add_argument('--full', action='store_true',
+                   help='headline run: also the steady region, the CPU baseline and the secondary '
+                        'configurations under "extra" (a plain run times the headline only)')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='headline run: write the posterior moments and lower bounds of the last '
+                        'timed iteration to DIR/<name>.npy (float64)')
     p.add_argument('--no-extra', action='store_true',
-                   help='default run: do not append the secondary configurations under "extra"')
+                   help='--full run: do not append the secondary configurations under "extra"')
     p.add_argument('--layout', choices=['tiled', 'rows'], default=None)
     p.add_argument('--steady-steps', type=int, default=200,
-                   help='a second, longer region after the timed one: per-step median / max '
-                        '("steady" in the line); 0 to skip')
+                   help='--full run: a second, longer region after the timed one: per-step median '
+                        '/ max ("steady" in the line); 0 to skip')
     p.add_argument('--exact-steps', action='store_true',
                    help='--config runs: time exactly --steps iterations (profiling runs); the '
                         'default raises short requests to the per-leg floor of >= 50 steps')
     p.add_argument('--full-out', default=None,
                    help='write the full (verbose) records of the headline and of every extra leg '
                         'to this JSON file; the printed line carries their compact forms')
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs and args.config != 'pca':
+        p.error('--dump-outputs writes the outputs of the headline run (--config pca)')
+    return args
 
 
 def make_shard(torch, dev, n_local, D, K, seed, rank):
@@ -185,8 +204,35 @@ def cpu_baseline(y_dev, x0_dev, D, K, n_total, L_gpu, Q, sample_n):
     return out
 
 
+def dump_outputs(out_dir, Q, plan, W, X, tau, alpha, n_local, sample=4096):
+    """What a caller of the timed path holds after its last iteration, as float64 files
+    out_dir/<name>.npy: ``L`` (the lower bound of every iteration so far, warm-up included), the
+    moments ``node.u`` of W, tau and alpha (``W_u0``, ``W_u1``, ...), and of the (n_local, K)
+    plate of X a fixed, seeded sample of rows: ``X_rows`` (their indices), ``X_u0`` (<x_n> of
+    those rows) and ``X_cov`` (the covariance all rows share: <x_n x_n^T> = <x_n><x_n>^T +
+    X_cov).  About 1 MB at any N.  With several ranks the caller writes rank 0's: X of its shard."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    out = {'L': np.asarray(Q.L[:Q.iter], dtype=np.float64)}
+    for name, node in (('W', W), ('tau', tau), ('alpha', alpha)):
+        for i, u in enumerate(node.u):
+            out['%s_u%d' % (name, i)] = np.asarray(u, dtype=np.float64)
+    rows = np.random.default_rng(0).choice(n_local, size=min(sample, n_local), replace=False)
+    rows.sort()
+    plan.finish()                     # the last pass has written <x>
+    xd = plan.Xd                      # (KP, ldx), row-major <x>
+    sel = xd[:plan.K].index_select(1, torch.as_tensor(rows, device=xd.device))
+    out['X_rows'] = rows.astype(np.float64)
+    out['X_u0'] = sel.T.cpu().numpy().astype(np.float64)
+    out['X_cov'] = plan._block(plan.layout.off_CX, plan.K, plan.K, int(plan.layout.KP))
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(out)
+
+
 def run_extra(name, fn, budget_s, **kw):
-    """One secondary configuration for the "extra" list of the default run; a failure there is
+    """One secondary configuration for the "extra" list of the --full run; a failure there is
     reported, never fatal to the headline line."""
     import torch
     t = time.time()
@@ -342,8 +388,10 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     L = Q.L[:Q.iter]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Q, plan, W, X, tau, alpha, n_local)
     steady = None
-    if args.steady_steps > 0:
+    if args.full and args.steady_steps > 0:
         # the contract's region above is K steps (20 x 2.2 ms on the driver's command): a second,
         # longer region of the same loop with the per-iteration wall times VB records
         # (Q.cputime) -- mean, median, max
@@ -399,6 +447,7 @@ def main():
         roof['traffic'], roof['traffic_source'] = pmc_traffic(roof['kernel'], D, K, n_local)
         roof['library_build'] = library_build_id()
         out['config']['stats'] = args.stats
+        out['config']['full'] = bool(args.full)
         out['config']['plate_layout'] = plan.plate_layout if args.stats == 'gram' else 'rows'
         out['config']['initial_x'] = 'initialize_from_value (injected normal draws)'
         # set-up: allocations of X / tile-major Y tried, pass time on each (plans/pca.py)
@@ -427,11 +476,12 @@ def main():
             out['steady'] = {k: (round(v, 4) if isinstance(v, float) else v)
                              for k, v in steady.items()}
         out['comm'] = comm
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(y, x0, D, K, n_total, [float(v) for v in L], Q,
                                                args.cpu_sample_n)
         full = {'headline': dict(out, placement_grid=pl)}
-        if world == 1 and not args.no_extra and (n_total, D, K) == (10_000_000, 128, 32):
+        if world == 1 and args.full and not args.no_extra and \
+                (n_total, D, K) == (10_000_000, 128, 32):
             # the other BASELINE configurations that fit one GPU, on the driver-visible line: ONE
             # compact record per leg (tools/workloads.py:compact -- step time with median / max,
             # dominant kernel time, roofline fraction, in-run parity, CPU baseline), LAST in the

@@ -3,7 +3,7 @@ oracle/ -- CPU restatement of the reference's VMP hot path.  TEST INFRASTRUCTURE
 
 Nothing in the product package (``bayespy_amd``) may import this package.  The
 only legal importers are ``tests/``, ``__graft_entry__.smoke()`` and the
-``cpu_baseline`` leg of ``bench.py`` -- and there only as the checker, never as
+``cpu_baseline`` leg of ``bench.py --full`` -- and there only as the checker, never as
 the thing that is measured or shipped.
 
 Parity status: PINNED.  Every function here is checked against the live

@@ -316,7 +316,7 @@ def test_user_guide_plate_doctests():
 
 
 def test_bench_extra_records_are_compact():
-    """The default bench line must stay far below the ~8 KB tail the driver keeps: every leg of
+    """The --full bench line must stay far below the ~8 KB tail the driver keeps: every leg of
     "extra" is the one-screen record of tools/workloads.py:compact (VERDICT r03 #1)."""
     import json
     from tools import workloads

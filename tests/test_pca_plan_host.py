@@ -602,3 +602,32 @@ def test_checkpoint_of_the_older_state_layout_loads(golden_dir):
     items['plans/0/state'] = items['plans/0/state'][:-3]
     with pytest.raises(ValueError, match='state values'):
         Q2.plans[0].load_state(Reader(items), [], 0)
+
+
+@pytest.mark.parametrize('stats', ['gram', 'stream'])
+def test_bench_dump_outputs_are_the_posterior(golden_dir, tmp_path, stats):
+    """bench.py --dump-outputs: float64 .npy files of what the caller holds after the last
+    iteration -- the bound trace, node.u of W / tau / alpha and a seeded row sample of X with the
+    shared covariance -- equal to the live-reference golden and to X.u of the same rows."""
+    from bench import dump_outputs
+    g = np.load(os.path.join(golden_dir, 'pca_n777_d20_k5.npz'))
+    Q = _attach_cpu(build_pca(nodes, VB, g['y'], g['x0'], 5), stats)
+    Q.update(repeat=int(g['n_iter']), verbose=False)
+    names = dump_outputs(str(tmp_path), Q, Q.plans[0], Q['W'], Q['X'], Q['tau'], Q['alpha'],
+                         777, sample=100)
+    o = {n: np.load(os.path.join(str(tmp_path), n + '.npy')) for n in names}
+    assert sorted(os.listdir(str(tmp_path))) == sorted(n + '.npy' for n in names)
+    assert all(a.dtype == np.float64 for a in o.values())
+    rows = o['X_rows'].astype(np.int64)
+    assert rows.shape == (100,) and np.all(np.diff(rows) > 0) and rows[-1] < 777
+    np.testing.assert_allclose(o['L'], g['L'], rtol=1e-10)
+    for k in ('W_u0', 'W_u1', 'tau_u0', 'alpha_u1'):
+        np.testing.assert_allclose(o[k], g[k], rtol=1e-8, atol=1e-10, err_msg=k)
+    np.testing.assert_allclose(o['X_u0'], g['X_u0'][0, rows], rtol=1e-8, atol=1e-10)
+    xx = o['X_u0'][:, :, None] * o['X_u0'][:, None, :] + o['X_cov']
+    np.testing.assert_allclose(xx, Q['X'].u[1][0, rows], rtol=1e-10, atol=1e-12)
+    # the sample is fixed: a second dump picks the same rows
+    names2 = dump_outputs(str(tmp_path / 'again'), Q, Q.plans[0], Q['W'], Q['X'], Q['tau'],
+                          Q['alpha'], 777, sample=100)
+    assert names2 == names
+    np.testing.assert_array_equal(np.load(str(tmp_path / 'again' / 'X_rows.npy')), o['X_rows'])

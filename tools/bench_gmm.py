@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Secondary measurement: BASELINE.json config 3 (GMM N=1e7, D=8, K=64, 1 GPU).
 Prints one JSON line with the same fields as bench.py (tools/workloads.py:run_gmm; also
-``python bench.py --config gmm`` and the "extra" list of the default bench.py run)."""
+``python bench.py --config gmm`` and the "extra" list of ``bench.py --full``)."""
 import argparse
 import json
 import os

@@ -6,7 +6,7 @@ mkdir -p $O
 R=$PWD
 export TMPDIR=/tmp
 for st in gram stream; do
-  B="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --stats $st"
+  B="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --stats $st"
   (cd /tmp; timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/p_stats_$st -o r -- $B > $R/$O/bench_under_rocprof_$st.log 2>&1)
   python tools/rocpd_summary.py /tmp/p_stats_$st/r_results.db > $O/kernel_stats_pca_$st.txt 2>&1
   (cd /tmp; timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/p_fetch_$st -o r -- $B > /dev/null 2>&1)
@@ -28,16 +28,16 @@ M="python $R/tools/bench_masked_pca.py --n 200000 --steps 9"
 python tools/rocpd_summary.py /tmp/p_stats_mpca/r_results.db > $O/kernel_stats_masked_pca.txt 2>&1
 python tools/bench_masked_pca.py --n 20000 --steps 10 > $O/bench_masked_pca_n2e4.json 2>/dev/null
 python tools/bench_masked_pca.py --n 200000 --steps 10 > $O/bench_masked_pca_n2e5.json 2>/dev/null
-S="python $R/bench.py --n 1250000 --steps 10 --warmup 2 --no-cpu-baseline"
+S="python $R/bench.py --full --n 1250000 --steps 10 --warmup 2 --no-cpu-baseline"
 (cd /tmp; timeout 300 rocprofv3 --kernel-trace -d /tmp/p_tl -o r -- $S > /dev/null 2>&1)
 python tools/rocpd_summary.py --timeline 30 /tmp/p_tl/r_results.db > $O/timeline_shard_n1250000.txt 2>&1
-python bench.py --n 1250000 --no-cpu-baseline > $O/bench_shard_n1250000_overlap.json 2>/dev/null
-VMP_PCA_PLATE_STREAM=0 python bench.py --n 1250000 --no-cpu-baseline > $O/bench_shard_n1250000_inorder.json 2>/dev/null
-VMP_PCA_PLATE_STREAM=0 python bench.py --no-cpu-baseline > $O/bench_n1_gram_inorder.json 2>/dev/null
-python bench.py --n 1000000 --d 64 --k 16 --no-cpu-baseline > $O/bench_config2.json 2>/dev/null
+python bench.py --full --n 1250000 --no-cpu-baseline > $O/bench_shard_n1250000_overlap.json 2>/dev/null
+VMP_PCA_PLATE_STREAM=0 python bench.py --full --n 1250000 --no-cpu-baseline > $O/bench_shard_n1250000_inorder.json 2>/dev/null
+VMP_PCA_PLATE_STREAM=0 python bench.py --full --no-cpu-baseline > $O/bench_n1_gram_inorder.json 2>/dev/null
+python bench.py --full --n 1000000 --d 64 --k 16 --no-cpu-baseline > $O/bench_config2.json 2>/dev/null
 python tools/bench_lssm.py > $O/bench_lssm.json 2>/dev/null
-python bench.py --steps 20 --warmup 3 > $O/bench_n1_gram.json 2>/dev/null
-python bench.py --steps 20 --warmup 3 --stats stream --no-cpu-baseline > $O/bench_n1_stream.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 3 > $O/bench_n1_gram.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 3 --stats stream --no-cpu-baseline > $O/bench_n1_stream.json 2>/dev/null
 python tools/bench_gmm.py > $O/bench_gmm_n1.json 2>/dev/null
 tools/microbench.bin > $O/microbench.txt 2>&1
 # forward-backward kernel of categorical Markov chains and the generic kernels (incl. the

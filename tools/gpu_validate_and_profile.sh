@@ -10,7 +10,7 @@ s=$(date +%s)
 echo "pytest secs: $(( $(date +%s) - s ))"
 tail -16 $O/pytest_all.txt
 grep -E "^(FAILED|ERROR)|^E  " $O/pytest_all.txt | head -30
-( timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ); cut -c1-700 $O/bench_default.json; tail -2 $O/bench_default.err
+( timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ); cut -c1-700 $O/bench_default.json; tail -2 $O/bench_default.err
 python - <<PY
 import json
 d=json.load(open('$O/bench_default.json'))

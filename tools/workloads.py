@@ -7,8 +7,8 @@ The secondary BASELINE.json configurations as functions that return the bench.py
     run_masked  SURVEY.md 8(d) secondary run: PCA N=1e7, D=128, K=32 with 10 % missing values
     run_lssm    config 5  linear state-space model, T=1e3 x B=1e5 sequences
 
-``bench.py --config {pca_c2,gmm,masked,lssm}`` prints one of them as its JSON line; the default
-``bench.py`` run (the PCA headline) appends all of them under "extra".  tools/bench_*.py are the
+``bench.py --config {pca_c2,gmm,masked,lssm}`` prints one of them as its JSON line;
+``bench.py --full`` (the PCA headline) appends all of them under "extra".  tools/bench_*.py are the
 stand-alone command lines of the same functions.
 """
 import os
@@ -115,7 +115,7 @@ def timed_update(Q, steps, barrier=None):
 
 
 def compact(rec, leg):
-    """The one-screen form of a leg's record for the "extra" list of the default bench line (the
+    """The one-screen form of a leg's record for the "extra" list of the --full bench line (the
     driver keeps only the tail of that line): step time with its spread, the dominant kernel's
     time and roofline fraction, in-run parity, CPU baseline.  No prose."""
     if 'error' in rec:
