@@ -777,7 +777,7 @@ constexpr int SPD_LD = SPD_MAXN + 1;
 
 // one workgroup of NTH threads per matrix (n <= 64): Gauss-Jordan sweeps in LDS.  The arithmetic of
 // an element does not depend on NTH (the stand-alone kernel runs it with 256 threads, the
-// interpreter of queued small operations with its 1024).
+// interpreter of queued small operations with its QNT = 512; bit for bit on gfx950, tests/test_small_queue_gpu.py).
 template <int NTH>
 __device__ inline void spd_block_body(double *M, int *bad, int tid, int n,
                                       const double *__restrict__ a, double *__restrict__ ainv,
@@ -1577,7 +1577,8 @@ inline void span_of(int nd, const int64_t *size, const int64_t *stride, int64_t 
 // inside the result of an earlier record of the launch is read from that result's place in the arena
 // (from memory if the result has no place there: the barrier + fence between records makes the write
 // visible); an operand that overlaps no earlier result is an array from outside -- copied in when it
-// is small and there is room; results of inverses (SMALL_SPD) are never placed.
+// is small and there is room; results of inverses (SMALL_SPD) and sums that are not written densely
+// from their base pointer on (negative or gapped output strides) are never placed.
 inline void queue_place(SmallOp *h, int n, SmallPre *pre, int *npre_out, int64_t *cached, int64_t *uncached)
 {
     ByteRange outs[2 * QUEUE_CAP + 8];      // results of the records so far (inverses: two each)
@@ -1657,20 +1658,25 @@ inline void queue_place(SmallOp *h, int n, SmallPre *pre, int *npre_out, int64_t
                 outs[nout++] = ByteRange{reinterpret_cast<const char *>(op.spd.logdet),
                                          reinterpret_cast<const char *>(op.spd.logdet + op.spd.batch), -1};
         } else {
-            int64_t cnt;
+            // the elements [lo, hi] the result spans around op.out; only a dense result (a formula's
+            // always, a sum's when its output strides pack nkeep elements from op.out on) gets a place
+            // in the arena.  A sum written backwards or with gaps keeps its true span with no place:
+            // a later reader of any part of it fences and reads memory (a place holding the span
+            // densely would leave the gaps unwritten, an empty span would not be seen as written)
+            int64_t lo = 0, hi = 0;
+            bool dense = true;
             if (op.kind == SMALL_EWISE) {
-                cnt = op.ew.total;
+                hi = op.ew.total - 1;
             } else {
-                int64_t lo = 0, hi = 0;
                 span_of(op.it.nk, op.it.ksize, op.it.okstride, lo, hi);
-                cnt = lo < 0 ? -1 : hi + 1;
+                dense = lo == 0 && hi + 1 == op.it.nkeep;
             }
+            const int64_t cnt = hi - lo + 1;
             int32_t o = -1;
-            if (cnt > 0 && cnt <= PRE_MAX) o = alloc(cnt);
+            if (dense && cnt > 0 && cnt <= PRE_MAX) o = alloc(cnt);
             op.lout = o;
-            const int64_t bytes = (cnt > 0 ? cnt : 0) * 8;
-            outs[nout++] = ByteRange{reinterpret_cast<const char *>(op.out),
-                                     reinterpret_cast<const char *>(op.out) + bytes, o};
+            outs[nout++] = ByteRange{reinterpret_cast<const char *>(op.out + lo),
+                                     reinterpret_cast<const char *>(op.out + hi + 1), o};
         }
     }
     *npre_out = next;

@@ -269,28 +269,39 @@ class Runtime:
         return self._op_depth > 0 and self._queue_env and self.lib is not None \
             and self._tune_sm
 
-    def keep_until_flush(self, arrays, out, kind='ew'):
+    def keep_until_flush(self, arrays, out, kind='ew', spd=None):
         """A queued operation runs LATER: its operands and its result must not go back to the
         allocator before (a block handed out again would be written by something else first).
         References are kept only when the library can have queued the call -- the queue is open,
-        the tune of this kind of operation (``'ew'`` formulas, ``'sm'`` sums and inverses) is on,
-        and the result is small (the library queues <= 2048 outputs) -- so plate-sized temporaries
-        go back to the allocator at once, also inside a sweep recording (where both tunes are off);
-        the list is dropped at every flush this side knows of."""
+        the tune of this kind of operation is on, and the call is small by the library's own rule
+        for its kind: ``'ew'`` formulas of <= small_queue_ew_max elements, ``'sm'`` sums of <= 2048
+        outputs, ``'spd'`` inverses (``spd=(n, batch)``) of 8 < n <= 32 and batch <= 4
+        (vmp_generic.hip: vmp_ewise / vmp_sum_multiply / vmp_spd_batched) -- so plate-sized
+        temporaries go back to the allocator at once, also inside a sweep recording (where both
+        tunes are off); the list is dropped at every flush this side knows of."""
         if self._op_depth == 0 or self.lib is None or not self._queue_env:
             return
-        if not (self._tune_sm if kind == 'sm' else self._tune_ew):
+        if not (self._tune_ew if kind == 'ew' else self._tune_sm):
             return
-        outs = out if isinstance(out, (tuple, list)) else (out,)
-        for o in outs:
-            t = getattr(o, 't', o)
-            if hasattr(t, 'numel') and t.numel() > self._queue_max_out:
+        if kind == 'spd':
+            n, batch = spd
+            if not (8 < n <= self._queue_spd_maxn and batch <= self._queue_spd_batch):
                 return
+        else:
+            limit = self._queue_max_out if kind == 'ew' else self._queue_sm_keep
+            outs = out if isinstance(out, (tuple, list)) else (out,)
+            for o in outs:
+                t = getattr(o, 't', o)
+                if hasattr(t, 'numel') and t.numel() > limit:
+                    return
         self._queue_alive.append((arrays, out))
 
     _tune_sm = False
     _tune_ew = True
-    _queue_max_out = 2048        # elements of a result the library may have queued (its tune small_queue_ew_max)
+    _queue_max_out = 2048        # elements of a formula the library may have queued (its tune small_queue_ew_max)
+    _queue_sm_keep = 2048        # outputs of a queued sum (SMALL_SM_KEEP)
+    _queue_spd_maxn = 32         # a queued inverse: n <= 32 (SMALL_SPD_MAXN), batch <= 4 (SMALL_SPD_BATCH)
+    _queue_spd_batch = 4
 
     # which device arrays the kernels of a sweep recording READ (graph_iter.py: an input of the
     # recorded graph that no launch reads needs no copy-back before a replay); None = not logging
@@ -313,7 +324,7 @@ class Runtime:
             elif key == 'small_queue_ew':
                 self._tune_ew = bool(value)
             elif key == 'small_queue_ew_max':
-                self._queue_max_out = max(2048, int(value))
+                self._queue_max_out = int(value)
 
     def queue_stats(self):
         if self.ctx is None or self.lib is None:
