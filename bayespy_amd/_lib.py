@@ -211,6 +211,10 @@ SIGNATURES = {
                                  c_f64, c_vp, c_sz]),
     'vmp_block_banded_solve': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_vp, c_vp, c_vp]),
+    'vmp_ml_invpsi': (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    'vmp_ml_gamma_shape': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'vmp_ml_concentration': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
+                                     c_vp, c_vp]),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_ensure_gram': (c_i32, [c_vp]),

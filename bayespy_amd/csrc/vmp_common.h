@@ -173,6 +173,17 @@ __host__ __device__ inline double vmp_trigamma(double x)
     return s + inv + 0.5 * inv2 + ser;
 }
 
+// Inverse digamma: y with psi(y) = x (misc.invpsi, utils/misc.py:1404-1429), the reference's recipe
+// step for step -- start at exp(x) + 1/2 for x >= -2.22, else -1 / (x - psi(1)), then exactly five
+// Newton steps.  A NaN argument takes the second start (the comparison is false) and stays NaN.
+__host__ __device__ inline double vmp_invpsi(double x)
+{
+    const double psi1 = -0.57721566490153286061;       // psi(1) = -Euler's constant
+    double y = x >= -2.22 ? exp(x) + 0.5 : -1.0 / (x - psi1);
+    for (int i = 0; i < 5; ++i) y = y - (vmp_digamma(y) - x) / vmp_trigamma(y);
+    return y;
+}
+
 #ifdef __HIPCC__
 // Running log-determinant without a log per pivot: the product of the pivots is kept in
 // `prod` and folded into `ld` only when it leaves a safe range (fp64 log is ~1000 cycles on

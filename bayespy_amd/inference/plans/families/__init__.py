@@ -24,6 +24,8 @@ from .gaussian import (GaussianARDFamily, GaussianFamily, GaussianGammaFamily,
 from .mixture import MixtureFamily
 from .chain import GaussianMarkovChainFamily, ChainToGaussianFamily
 from .dot import SumMultiplyFamily
+from .ml import GammaShapeFamily, ConcentrationFamily
+from ....nodes.ml import GammaShape, Concentration
 
 
 def make_family(node):
@@ -40,6 +42,10 @@ def make_family(node):
         return fam
     if isinstance(node, Mixture):
         return MixtureFamily(node, make_family(node._proto))
+    if isinstance(node, GammaShape):
+        return GammaShapeFamily(node)
+    if isinstance(node, Concentration):
+        return ConcentrationFamily(node)
     if isinstance(node, Gamma):
         return GammaFamily(node)
     if isinstance(node, GaussianGamma):

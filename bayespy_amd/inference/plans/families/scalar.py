@@ -72,7 +72,8 @@ class GammaFamily(Family):
     def message_to_parent(self, index, u, up):
         if index == 1:
             return [fuse(lambda x: -x, u[0]), up[0][0]]
-        raise NotImplementedError('message from Gamma to its shape parameter')
+        # to a GammaShape node: [<log x> + <log b>, -1]  (gamma.py:96-113)
+        return [fuse(lambda lx, lb: lx + lb, u[1], up[1][1]), -1.0]
 
     def gradient(self, rg, u, phi):
         # gamma.py:183-211
@@ -145,6 +146,8 @@ class DirichletFamily(Family):
         return [u0], g
 
     def cgf_from_parents(self, up):
+        if not isinstance(self.node.parents[0], Constant):
+            return up[0][1]          # a Concentration node carries it as a moment (dirichlet.py:163-167)
         a = _arr(up[0][0])
         s = misc.sum_multiply(a, axis=-1)
         lg = misc.sum_multiply(fuse(lambda v: da.gammaln(v), a), axis=-1)
@@ -156,7 +159,8 @@ class DirichletFamily(Family):
         return [logp], fuse(lambda s: -s, misc.sum_multiply(logp, axis=-1))
 
     def message_to_parent(self, index, u, up):
-        raise NotImplementedError('Dirichlet concentration is a constant in the built path')
+        # to a Concentration node: [<log p>, 1]  (dirichlet.py:113-120)
+        return [u[0], 1.0]
 
     def gradient(self, rg, u, phi):
         # dirichlet.py:213-231

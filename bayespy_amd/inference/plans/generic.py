@@ -176,6 +176,11 @@ class GenericPlan(GraphIteration):
             if isinstance(n, Stochastic):
                 self.state[id(n)] = _State()
             n._plan = self
+        point = [n.name for n in self.all
+                 if getattr(self.family.get(id(n)), 'point_estimate', False)]
+        if point and any(getattr(n, '_shard_axis', None) is not None for n in self.all):
+            raise NotImplementedError('maximum-likelihood nodes (%s) in a model sharded over ranks '
+                                      'are not built' % ', '.join(point))
         self._const_cache = {}
         self._masks_ready = False
         self._graph_init()
@@ -187,9 +192,12 @@ class GenericPlan(GraphIteration):
         """Device state exists (a recompilation would discard it)."""
         return any(st.ready for st in self.state.values())
 
-    def invalidate(self, node):
+    def invalidate(self, node, keep_state=False):
+        """``node`` changed outside the plan: its state is formed again on next use -- or, with
+        ``keep_state`` (a changed constant of a maximum-likelihood node, whose present estimate stays
+        as in the reference), only the recorded sweep is dropped."""
         st = self.state.get(id(node))
-        if st is not None:
+        if st is not None and not keep_state:
             st.ready = False
         self._masks_ready = False
 
@@ -201,6 +209,12 @@ class GenericPlan(GraphIteration):
             return st
         fam = self.family[id(node)]
         st.ready = True          # guards recursion through parents
+        if getattr(fam, 'point_estimate', False):
+            # a maximum-likelihood node: moments only (gamma.py:298-301, dirichlet.py:256)
+            init = node._init
+            st.u = fam.fixed_moments(init[1]) if init is not None else fam.initial_moments()
+            st.observed, st.phi, st.g, st.f = False, None, None, None
+            return st
         if node.observed:
             data, om = node._data, node._mask
             st.partial = om is not True and not bool(np.all(om))
@@ -772,6 +786,10 @@ class GenericPlan(GraphIteration):
                 self._refresh_partial(node, st)
             return
         fam = self.family[id(node)]
+        if getattr(fam, 'point_estimate', False):
+            # the children's messages summed to the node's plates, then ONE library launch
+            st.u = fam.ml_update(self._messages_from_children(node))
+            return
         cand = self._shared_cov_candidate(node, fam)
         phi_p, msgs = self._phi_parts(node, lazy=cand)
         if cand and self._shared_cov_update(node, st, fam, phi_p, msgs):
@@ -789,6 +807,9 @@ class GenericPlan(GraphIteration):
         for node in nodes:
             if not isinstance(node, Stochastic):
                 continue
+            if getattr(self.family[id(node)], 'point_estimate', False):
+                raise NotImplementedError('gradient step of %s: a maximum-likelihood node has no '
+                                          'natural parameters' % node.name)
             st = self._ensure(node)
             if st.observed:
                 continue
@@ -807,6 +828,9 @@ class GenericPlan(GraphIteration):
             return None, 0.0
         st = self._ensure(node)
         fam = self.family[id(node)]
+        if getattr(fam, 'point_estimate', False):
+            tot = fam.bound_term(st.u)
+            return (None, 0.0) if tot is None else (tot, 1.0)
         up = self._parent_moments(node)
         closed = None
         # annealing temperature: the entropy part of the term, i.e. phi and g of q, is
@@ -1197,7 +1221,7 @@ class GenericPlan(GraphIteration):
                                  'observed' % node.name)
             st.u = [DArray.from_host(np.array(reader.get(base + 'u%d' % i), dtype=np.float64))
                     for i in range(len(st.u))]
-            if not st.observed:
+            if not st.observed and not getattr(self.family[id(node)], 'point_estimate', False):
                 st.phi = [DArray.from_host(np.array(reader.get(base + 'phi%d' % i),
                                                     dtype=np.float64))
                           for i in range(len(node.dims))]
@@ -1352,6 +1376,10 @@ class GenericPlan(GraphIteration):
 
     # -- natural parameters, gradients, densities (expfamily.py:258-340, :483-542) --------------
     def _latent_state(self, node):
+        if getattr(self.family.get(id(node)), 'point_estimate', False):
+            raise NotImplementedError('%s is a maximum-likelihood estimate: it has no variational '
+                                      'distribution (natural parameters, gradients, densities, '
+                                      'draws)' % node.name)
         st = self._ensure(node)
         if st.observed or st.phi is None:
             raise ValueError('node %s is observed: it has no variational parameters' % node.name)

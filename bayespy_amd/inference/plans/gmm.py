@@ -127,6 +127,10 @@ class GMMPlan:
             if not (isinstance(alpha, Dirichlet) and all(p == 1 for p in alpha.plates)):
                 no(Y, 'the assignment prior is not one Dirichlet node')
                 continue
+            if not isinstance(alpha.parents[0], Constant):
+                no(Y, 'the concentration of the assignment prior is a node (%s), not a constant'
+                      % type(alpha.parents[0]).__name__)
+                continue
             N = Y.plates[0]
             K, D = Y.clusters, Y.dims[0][0]
             if D > 32 or K > 64:

@@ -165,6 +165,13 @@ class LSSMPlan:
             if not isinstance(Y, GaussianARD) or Y.ndim != 0:
                 continue
             F, tau = Y.parents
+            if isinstance(F, SumMultiply) \
+                    and any(isinstance(q, MarkovChainToGaussian) for q in F.parents) \
+                    and isinstance(tau, Gamma) \
+                    and not all(isinstance(p, Constant) for p in tau.parents):
+                # a state-space model whose noise precision has a learnt hyperparameter
+                no(Y, 'its precision %s has a node-valued hyperparameter' % (tau.name or 'tau'))
+                continue
             if not isinstance(F, SumMultiply) or not _gamma_const(tau, tau.plates) \
                     or any(p != 1 for p in tau.plates):
                 continue

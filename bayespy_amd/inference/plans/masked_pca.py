@@ -123,7 +123,7 @@ class MaskedPCAPlan:
 
     @staticmethod
     def match(nodes, why=None):
-        roles = PCAPlan.match_graph(nodes)
+        roles = PCAPlan.match_graph(nodes, why)
         if roles is None:
             return None
         D, N = roles['Y'].plates

@@ -20,10 +20,12 @@ from .mixture import Mixture, MultiMixture
 from .gaussian_markov_chain import (GaussianMarkovChain, SwitchingGaussianMarkovChain,
                                     VaryingGaussianMarkovChain)
 from .categorical_markov_chain import CategoricalMarkovChain
+from .ml import GammaShape, Concentration, DirichletConcentration, BetaConcentration
 
 __all__ = ['Node', 'Constant', 'Stochastic', 'Gamma', 'GaussianARD', 'Gaussian', 'GaussianGamma',
            'GaussianToGaussianGamma', 'WrapToGaussianGamma', 'SumMultiply',
            'Dot', 'Wishart', 'Dirichlet', 'Categorical', 'Multinomial', 'Mixture', 'MultiMixture',
            'GaussianMarkovChain', 'Exponential', 'Beta', 'Binomial', 'Bernoulli', 'Poisson', 'Add', 'ConcatGaussian',
            'Take', 'Concatenate', 'Gate', 'Choose', 'CategoricalMarkovChain',
-           'SwitchingGaussianMarkovChain', 'VaryingGaussianMarkovChain']
+           'SwitchingGaussianMarkovChain', 'VaryingGaussianMarkovChain', 'GammaShape',
+           'Concentration', 'DirichletConcentration', 'BetaConcentration']

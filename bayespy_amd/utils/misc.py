@@ -410,6 +410,19 @@ def normalized_exp(phi):
     return p, lse
 
 
+def invpsi(x):
+    """Inverse digamma function elementwise (utils/misc.py:1404-1429): the reference's start and
+    five Newton steps -- ``vmp_ml_invpsi``."""
+    rt = get_runtime()
+    x = contiguous(asdarray(x))
+    y = DArray.empty(x.shape)
+    rt.sync_stream()
+    rt.note_reads([x])
+    rt.check(rt.lib.vmp_ml_invpsi(rt.ctx, x.size, ctypes.c_void_p(x.t.data_ptr()),
+                                  ctypes.c_void_p(y.t.data_ptr())))
+    return y
+
+
 _HALF_ARANGE = {}
 
 

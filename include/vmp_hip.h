@@ -753,6 +753,25 @@ int32_t vmp_block_banded_solve(vmp_ctx *ctx, int32_t T, int32_t K, int64_t nm, i
                                const double *A, const double *B, const double *y, double *V,
                                double *C, double *x, double *ldet, int32_t *info);
 
+/* Maximum-likelihood hyperparameter nodes (gamma.py:273-334, dirichlet.py:234-330; details:
+ * bayespy_amd/csrc/vmp_ml.hip).  Dense fp64 arrays; the summed messages of the children m0, m1
+ * and the node's own terms r0, r1 ("prior" m0 / m1 of GammaShape, the regularization of
+ * Concentration) come broadcast to the node's shape.
+ *   vmp_ml_invpsi:        y = invpsi(x) elementwise (misc.invpsi, utils/misc.py:1404-1429).
+ *   vmp_ml_gamma_shape:   a = invpsi(-(m0 + r0) / (m1 + r1)), lga = lgamma(a); n elements.
+ *   vmp_ml_concentration: rows x K concentrations by the fixed point a <- invpsi(psi(sum a) +
+ *     (m0 + r0) / (m1 + r1)) from a = 1, stopped at the first iteration where no element of ANY row
+ *     moved by more than 1e-5 of its new value, at most max_iter iterations (one workgroup, one
+ *     lane per element); z[r] = lgamma(sum a) - sum lgamma(a).  m0, r0, alpha and the scratch
+ *     array work: rows x K, m1, r1, z: rows.  status (3 int32):
+ *     [some mean_logp infinite (nothing iterated), max_iter reached, iterations run]. */
+int32_t vmp_ml_invpsi(vmp_ctx *ctx, int64_t n, const double *x, double *y);
+int32_t vmp_ml_gamma_shape(vmp_ctx *ctx, int64_t n, const double *m0, const double *m1,
+                           const double *r0, const double *r1, double *a, double *lga);
+int32_t vmp_ml_concentration(vmp_ctx *ctx, int64_t rows, int32_t K, const double *m0,
+                             const double *m1, const double *r0, const double *r1, int32_t max_iter,
+                             double *alpha, double *work, double *z, int32_t *status);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
