@@ -215,6 +215,8 @@ SIGNATURES = {
     'vmp_ml_gamma_shape': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'vmp_ml_concentration': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
                                      c_vp, c_vp]),
+    'vmp_chain_pair_stats_limits': (c_i32, [c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'vmp_chain_pair_stats': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64]),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_ensure_gram': (c_i32, [c_vp]),

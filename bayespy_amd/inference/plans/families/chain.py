@@ -53,6 +53,11 @@ class GaussianMarkovChainFamily(Family):
         self._e0 = DArray.from_host(e0.reshape(N, 1, 1))
         self._en0 = DArray.from_host((1.0 - e0).reshape(N, 1, 1))
         self._enl = DArray.from_host(enl.reshape(N, 1, 1))
+        # A or nu carry an N-1 plate (GaussianMarkovChain only): the formulas keep the time axis
+        self.time_varying = bool(getattr(node, 'time_varying', False))
+        self._solve = None          # (x, V, C) of the last smoother run
+        self._pair = None           # (x, sum_b <x_t x_t^T>, sum_b <x_t x_{t+1}^T>) made from it
+        self.pair_stats_calls = 0   # messages answered from the plate sums of vmp_chain_pair_stats
 
     def plates_to_parent(self, index):
         if index < 2:
@@ -97,7 +102,35 @@ class GaussianMarkovChainFamily(Family):
         lognu = self._time_axis(up[3][1], (D,), 3)
         return Am, AA, nu, lognu
 
+    def _over_time(self, a, nvar):
+        """``a`` with its (unit or N-1) time axis, ``nvar`` axes from the end, as N-1 blocks."""
+        ax = a.ndim - nvar - 1
+        if a.shape[ax] == self.N - 1:
+            return a
+        return a.broadcast_to(a.shape[:ax] + (self.N - 1,) + a.shape[ax + 1:])
+
+    def _phi_time_varying(self, up):
+        """phi of N-1 different transitions (gaussian_markov_chain.py:560-610): the blocks
+        nu_t <a a^T>_t sit at the times 0..N-2 of phi1, diag(nu_t) at 1..N-1, nu_t A_t in phi2."""
+        m, Lam = up[0][0], up[1][0]
+        Am, AA, nu, _ = self._dyn(up)
+        D = self.D
+        Lm = linalg.mvdot(Lam, m)
+        phi0 = fuse(lambda e, v: e * v, self._e0v, _arr(Lm).reshape(_shape(Lm)[:-1] + (1, D)))
+        nuAA = self._over_time(misc.sum_multiply(_trail(nu, 2), AA, axis=-3), 2)
+        dnu = self._over_time(misc.diag(nu, ndim=1), 2)
+        zero = _const(('zeros', (1, D, D)), lambda: np.zeros((1, D, D)))
+        at_prev = misc.concatenate([nuAA, zero], axis=-3)                     # (..., N, D, D)
+        at_next = misc.concatenate([zero, dnu], axis=-3)
+        L = _arr(Lam)
+        L = L.reshape(L.shape[:-2] + (1,) + L.shape[-2:])
+        phi1 = fuse(lambda a, l, d, q: -0.5 * (a * l + d + q), self._e0, L, at_next, at_prev)
+        phi2 = fuse(lambda n, a: n * a, _trail(nu, 1), Am).swapaxes(-1, -2)
+        return [phi0, phi1, phi2]
+
     def phi_from_parents(self, up):
+        if self.time_varying:
+            return self._phi_time_varying(up)
         m, Lam = up[0][0], up[1][0]
         Am, AA, nu, _ = self._dyn(up)
         Lm = linalg.mvdot(Lam, m)
@@ -122,6 +155,11 @@ class GaussianMarkovChainFamily(Family):
         u2 = fuse(lambda a, b, c: a * b + c, xa[..., :-1, :, :], xb[..., 1:, :, :], C)
         g = fuse(lambda s, l: -0.5 * s + 0.5 * l,
                  misc.sum_multiply(x, phi[0], axis=(-1, -2)), ld)
+        if self.time_varying:
+            # kept for the plate sums of the messages -- only where they can be used (the solver
+            # ran with shared matrices: V, C are not plate-sized)
+            shared = all(p == 1 for p in V.shape[:-3])
+            self._solve, self._pair = ((x, V, C) if shared else None), None
         return [x, u1, u2], g
 
     def cgf_from_parents(self, up):
@@ -129,7 +167,9 @@ class GaussianMarkovChainFamily(Family):
         Lam, logdet = up[1]
         _, _, _, lognu = self._dyn(up)
         s = misc.sum_multiply(lognu, axis=(-1, -2))
-        return fuse(lambda t, ld, ln: -0.5 * t + 0.5 * ld + 0.5 * (self.N - 1) * ln,
+        # a unit time axis stands for N-1 equal rows, an N-1 axis was summed over the transitions
+        reps = 1 if (self.time_varying and lognu.shape[-2] != 1) else self.N - 1
+        return fuse(lambda t, ld, ln: -0.5 * t + 0.5 * ld + 0.5 * reps * ln,
                     misc.sum_multiply(Lam, mm, axis=(-1, -2)), logdet, s)
 
     def fixed_moments_and_f(self, x):
@@ -155,8 +195,58 @@ class GaussianMarkovChainFamily(Family):
             xm, mx = linalg.outer(x0, m), linalg.outer(m, x0)
             return [fuse(lambda a, b, c, d: -0.5 * (a - b - c + d), x0x0, xm, mx, mm), 0.5]
         Am, AA, nu, _ = self._dyn(up)
+        pair = self._summed_pair_moments(index, u) if self.time_varying else None
+        if pair is not None:
+            # the sums over the sequences are made already: the formulas below are linear in the
+            # second moments, and neither A nor nu carries a sequence plate here
+            XX, XpXn = pair
         XnXp = XpXn.swapaxes(-1, -2)                     # [i][j] = <x_n[i] x_{n-1}[j]>
         XXp = XX[..., :-1, :, :]
+        if pair is not None:
+            out = _SummedMessage(self._dynamics_message(index, XX, XXp, XnXp, Am, AA, nu,
+                                                         count=int(np.prod(self.node.plates))))
+            out.plates_from = (1,) * len(self.node.plates) + (self.N - 1, self.D)
+            return out
+        return self._dynamics_message(index, XX, XXp, XnXp, Am, AA, nu)
+
+    def _summed_pair_moments(self, index, u):
+        """(sum_b <x_t x_t^T>, sum_b <x_t x_{t+1}^T>) with unit sequence plates from ONE read of the
+        means (``vmp_chain_pair_stats``) plus ny times the covariances the solver returned once --
+        when the solver ran with shared matrices, the chain has sequence plates, the mask to the
+        parent is all true and the kernel has an instance for D (tune key chain_pair_stats);
+        None otherwise: the general operations plate-sum the (ny, N, D, D) moments."""
+        ent = self._solve
+        if ent is None or ent[0] is not u[0]:
+            return None             # moments not from this family's smoother (loaded, fixed value)
+        x, V, C = ent
+        node = self.node
+        ny = int(np.prod(x.shape[:-2])) if x.ndim > 2 else 1
+        if ny <= 1 or ny != int(np.prod(node.plates)) or any(p != 1 for p in V.shape[:-3]):
+            return None
+        if self._pair is None or self._pair[0] is not x:
+            max_d, on, _ = linalg.chain_pair_stats_limits()
+            if not on or self.D > max_d:
+                return None
+            plan = node._plan
+            for idx in (2, 3):
+                if isinstance(node.parents[idx], Constant):
+                    continue
+                mask, _ = plan._mask_factor(
+                    (id(node), idx),
+                    lambda idx=idx: self.mask_to_parent(idx, np.asarray(plan._mask_array(node))))
+                if mask is not None:
+                    return None
+            Sxx, Sxp = linalg.chain_pair_stats(x)
+            lead = (1,) * len(node.plates)
+            N, D = self.N, self.D
+            XX = fuse(lambda s, v: s + float(ny) * v, Sxx, V.reshape((N, D, D)))
+            XpXn = fuse(lambda s, c: s + float(ny) * c, Sxp, C.reshape((N - 1, D, D)))
+            self._pair = (x, XX.reshape(lead + (N, D, D)), XpXn.reshape(lead + (N - 1, D, D)))
+        self.pair_stats_calls += 1
+        return self._pair[1], self._pair[2]
+
+    def _dynamics_message(self, index, XX, XXp, XnXp, Am, AA, nu, count=1):
+        """``count``: the sequences already summed into the second moments."""
         if index == 2:
             # to the dynamics matrix, weighted by the innovation precision (:462-475,
             # gaussian.py:2354-2360)
@@ -168,7 +258,13 @@ class GaussianMarkovChainFamily(Family):
         t2 = misc.sum_multiply(XXp.reshape(XXp.shape[:-2] + (1,) + XXp.shape[-2:]), AA,
                                axis=(-1, -2))
         t3 = misc.get_diag(XX[..., 1:, :, :], ndim=1)
-        return [fuse(lambda a, b, c: a - 0.5 * b - 0.5 * c, t1, t2, t3), 0.5]
+        return [fuse(lambda a, b, c: a - 0.5 * b - 0.5 * c, t1, t2, t3), 0.5 * count]
+
+
+class _SummedMessage(list):
+    """A message whose factors are summed over some of the child's plates already:
+    ``plates_from`` stands for ``plates_to_parent`` when the router sums what is left."""
+    plates_from = None
 
 
 class ChainToGaussianFamily:

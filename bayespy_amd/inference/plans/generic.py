@@ -181,6 +181,10 @@ class GenericPlan(GraphIteration):
         if point and any(getattr(n, '_shard_axis', None) is not None for n in self.all):
             raise NotImplementedError('maximum-likelihood nodes (%s) in a model sharded over ranks '
                                       'are not built' % ', '.join(point))
+        tv = [n.name for n in self.all if getattr(n, 'time_varying', False)]
+        if tv and any(getattr(n, '_shard_axis', None) is not None for n in self.all):
+            raise NotImplementedError('Gaussian Markov chains with time-varying dynamics (%s) in a '
+                                      'model sharded over ranks are not built' % ', '.join(tv))
         self._const_cache = {}
         self._masks_ready = False
         self._graph_init()
@@ -505,7 +509,8 @@ class GenericPlan(GraphIteration):
             msgs = fam.message_to_parent(index, u, up)
         finally:
             fam._terms_ok = False
-        plates_self = tuple(fam.plates_to_parent(index))
+        # (a family may answer with some of its plates summed already: it names what is left)
+        plates_self = tuple(getattr(msgs, 'plates_from', None) or fam.plates_to_parent(index))
         mask, _ = self._mask_factor(
             (id(child), index),
             lambda: fam.mask_to_parent(index, np.asarray(self._mask_array(child))))

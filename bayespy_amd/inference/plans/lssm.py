@@ -191,6 +191,11 @@ class LSSMPlan:
                 continue
             D, T = X.D, X.N
             mu, Lam, A, nu = X.parents
+            if getattr(X, 'time_varying', False):
+                no(Y, 'the chain %s has a time plate (N-1 = %d) on its dynamics A or its innovation '
+                      'precision nu: time-varying dynamics run in the generic engine'
+                      % (X.name or 'X', T - 1))
+                continue
             if not (isinstance(mu, Constant) and isinstance(Lam, Constant)):
                 continue
             if np.shape(mu.value) != (D,) or np.shape(Lam.value) != (D, D):

@@ -254,6 +254,9 @@ class RotateGaussianMarkovChain:
         mu, Lam, A, nu = X.parents[:4]
         if len(X.parents) > 4:
             raise NotImplementedError('input signals of the chain are not built')
+        if getattr(X, 'time_varying', False):
+            raise NotImplementedError('RotateGaussianMarkovChain: a chain with a time plate on its '
+                                      'dynamics A or its innovation precision nu is not built')
         if self.A_rotator.node_X is not A:
             raise ValueError('the rotator of the dynamics must rotate the A of this chain')
         if not (isinstance(nu, Constant) and np.all(np.asarray(nu.value) == 1)):

@@ -5,8 +5,11 @@ bayespy/inference/vmp/nodes/gaussian_markov_chain.py:709-1190, formulas :270-707
 ``GaussianMarkovChain(mu, Lambda, A, nu, n=N, plates=...)``: x_0 ~ N(mu, Lambda^-1),
 x_n ~ N(A x_{n-1}, diag(nu)^-1).  Moments u = [<x_n> (N,D), <x_n x_n^T> (N,D,D),
 <x_{n-1} x_n^T> (N-1,D,D)].  The dynamics matrix ``A`` is a Gaussian variable with
-shape (D,) whose LAST plate (D) indexes the rows of A; ``nu`` has last plate D.  Only
-time-constant dynamics are built (A, nu without the N-1 plate).  A chain used as a
+shape (D,) whose LAST plate (D) indexes the rows of A; ``nu`` has last plate D.  Both may
+change at every transition: a second-to-last plate of N-1 on ``A`` (plates (..., N-1, D), or an
+(..., N-1, D, D) array) or on ``nu`` (plates (..., N-1, D)) is the time axis, a unit or missing
+one means constant dynamics; ``n`` is inferred from such a plate when it is not given
+(reference :768-778, :839-857).  Input signals (``inputs=``) are not built.  A chain used as a
 Gaussian parent (e.g. of SumMultiply) is seen through :class:`MarkovChainToGaussian`,
 which turns the time axis into the last plate (reference :1988-2098).
 """
@@ -50,13 +53,25 @@ class GaussianMarkovChain(Stochastic):
             if len(pl) == 0 or pl[-1] != D:
                 raise Exception("Dynamics matrix should have a last plate equal to the "
                                 "dimensionality of the system.")
+        # time instances the parents give (:839-857): the second-to-last plate of A and nu
+        n_parents = 1
+        for pl in (Apl, nupl):
             if len(pl) >= 2 and pl[-2] != 1:
-                raise NotImplementedError('time-varying dynamics (an N-1 plate on A / nu) '
-                                          'are not built')
+                if n_parents != 1 and pl[-2] != n_parents:
+                    raise Exception("Plates of parents are giving different number of time "
+                                    "instances")
+                n_parents = pl[-2]
         if n is None:
-            raise Exception("The number of time instances could not be determined "
-                            "automatically. Give the number of time instances.")
+            if n_parents == 1:
+                raise Exception("The number of time instances could not be determined "
+                                "automatically. Give the number of time instances.")
+            n = n_parents + 1
+        elif n_parents != 1 and n_parents + 1 != n:
+            raise Exception("The number of time instances must match the number of last plates "
+                            "of parents: %d != %d+1" % (n, n_parents))
         self.N, self.D = int(n), int(D)
+        # the dynamics or the innovation precision change along the chain
+        self.time_varying = n_parents != 1
         self.dims = ((self.N, D), (self.N, D, D), (self.N - 1, D, D))
         given = tuple(plates) if plates is not None else ()
         self.plates = broadcasted_shape(given, mupl, Lpl, Apl[:-2], nupl[:-2])

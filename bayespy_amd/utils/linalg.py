@@ -14,7 +14,7 @@ import numpy as np
 
 from .. import _lib
 from ..darray import DArray, asdarray, contiguous, fuse
-from ..device import get_runtime
+from ..device import get_runtime, ptr
 from .misc import sum_multiply
 
 
@@ -224,3 +224,39 @@ def block_banded_solve(A, B, y):
     # recorded sweep the flag is one of the graph's outputs)
     rt.defer_check(info, _lib.NotPositiveDefiniteError, "Matrix not positive definite")
     return V, C, x, ldet
+
+
+def chain_pair_stats_limits(ny=0, N=1, D=1):
+    """(largest state dimension ``vmp_chain_pair_stats`` has an instance for, whether the tune key
+    ``chain_pair_stats`` leaves it on, doubles of scratch the call needs for (ny, N, D))."""
+    rt = get_runtime()
+    max_d, on, work = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    rc = rt.lib.vmp_chain_pair_stats_limits(int(ny), int(N), int(D), ctypes.byref(max_d),
+                                            ctypes.byref(on), ctypes.byref(work))
+    if rc not in (_lib.VMP_OK, _lib.VMP_ERR_UNSUPPORTED):
+        rt.check(rc)
+    return int(max_d.value), bool(on.value), int(work.value)
+
+
+# calls of vmp_chain_pair_stats made by this process (each is the two launches of the entry point)
+PAIR_STATS_LAUNCHES = [0]
+
+
+def chain_pair_stats(x):
+    """Sums over the sequences of the outer products of a chain's means with themselves and with
+    their successors: x (..., N, D) -> (sum_b x_t x_t^T (N, D, D), sum_b x_t x_{t+1}^T (N-1, D, D)).
+    One read of ``x`` (``vmp_chain_pair_stats``), the same bits on every call."""
+    rt = get_runtime()
+    x = contiguous(asdarray(x))
+    N, D = x.shape[-2], x.shape[-1]
+    ny = int(np.prod(x.shape[:-2])) if x.ndim > 2 else 1
+    _, _, nwork = chain_pair_stats_limits(ny, N, D)
+    Sxx = DArray.empty((N, D, D))
+    Sxp = DArray.empty((max(N - 1, 0), D, D))
+    work = DArray.empty((max(nwork, 1),))
+    rt.sync_stream()
+    rt.note_reads([x])
+    rt.check(rt.lib.vmp_chain_pair_stats(
+        rt.ctx, ny, N, D, ptr(x.t), ptr(Sxx.t), ptr(Sxp.t), ptr(work.t), nwork))
+    PAIR_STATS_LAUNCHES[0] += 1
+    return Sxx, Sxp

@@ -772,6 +772,21 @@ int32_t vmp_ml_concentration(vmp_ctx *ctx, int64_t rows, int32_t K, const double
                              const double *m1, const double *r0, const double *r1, int32_t max_iter,
                              double *alpha, double *work, double *z, int32_t *status);
 
+/* Plate sums of a Gaussian Markov chain's messages to time-varying dynamics shared by ny sequences
+ * (gaussian_markov_chain.py:462-527; details: bayespy_amd/csrc/vmp_chain_tv.hip).
+ *   vmp_chain_pair_stats: x (ny, N, D) row-major ->  Sxx (N, D, D) = sum_b x_{b,t} x_{b,t}^T  and
+ *     Sxp (N-1, D, D) = sum_b x_{b,t} x_{b,t+1}^T  (Sxp may be NULL when N = 1).  x is read once;
+ *     no atomics: two calls on the same input give the same bits.  ny = 0 is legal (zeros).
+ *     `work`: scratch of at least the `work_doubles` the limits query reports for (ny, N, D).
+ *     D above the limit: VMP_ERR_UNSUPPORTED; null / negative arguments: VMP_ERR_INVALID.
+ *   vmp_chain_pair_stats_limits (host only): *max_d = the largest D with an instance (16),
+ *     *enabled = the tune key "chain_pair_stats" (default 1; 0 keeps callers on the general
+ *     operations), *work_doubles = the scratch the call needs for (ny, N, D). */
+int32_t vmp_chain_pair_stats_limits(int64_t ny, int32_t N, int32_t D, int32_t *max_d,
+                                    int32_t *enabled, int64_t *work_doubles);
+int32_t vmp_chain_pair_stats(vmp_ctx *ctx, int64_t ny, int32_t N, int32_t D, const double *x,
+                             double *Sxx, double *Sxp, double *work, int64_t work_doubles);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
