@@ -217,6 +217,14 @@ SIGNATURES = {
                                      c_vp, c_vp]),
     'vmp_chain_pair_stats_limits': (c_i32, [c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'vmp_chain_pair_stats': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    'vmp_lda_limits': (c_i32, [P(c_i32), P(c_i32)]),
+    'vmp_lda_plan': (c_i32, [c_i64, c_i32, P(c_i32), P(c_i32), P(c_i64)]),
+    'vmp_lda_token_pass': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp, c_vp]),
+    'vmp_lda_dirichlet': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp]),
+    'vmp_lda_dot': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_ensure_gram': (c_i32, [c_vp]),

@@ -8,8 +8,9 @@ from .masked_pca import MaskedPCAPlan
 from .gmm import GMMPlan
 from .lssm import LSSMPlan
 from .lssm_masked import MaskedLSSMPlan
+from .lda import LDAPlan
 
-PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan]
+PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
 
 
 def _reusable_plans(nodes, engine, options=None):

@@ -205,6 +205,20 @@ class GenericPlan(GraphIteration):
             st.ready = False
         self._masks_ready = False
 
+    def constant_changed(self, const):
+        """``Constant.set_value``: the copies formed from the old value (moments of the constant,
+        prior terms of its children, whatever was derived from them, the recorded sweep) go; the
+        posteriors stay, as in the reference (constant.py:64-76)."""
+        for n in self.all:
+            for i, p in enumerate(n.parents):
+                if p is const:
+                    self._const_cache.pop((id(n), i), None)
+                    self._const_cache.pop((id(n), 'prior'), None)
+        self._graph_reset_caches()
+        if self._g_rec is not None:
+            self._graph_drop('a constant changed')
+        self._g_warm = 0
+
     # -- moments -----------------------------------------------------------------------
     def _ensure(self, node):
         """Materialise the device state of a stochastic node (prior / value / data)."""
@@ -469,9 +483,6 @@ class GenericPlan(GraphIteration):
         # (node.py:589-632)
         r = multiplier_factor(child.plates_multiplier, parent.plates_multiplier)
         if getattr(fam, 'deterministic', False):
-            if r != 1.0:
-                raise NotImplementedError('plate multipliers through %s are not built'
-                                          % type(child).__name__)
             m_child = self._messages_from_children(child)
             ups = self._parent_moments(child)
             mask, _ = self._mask_factor((id(child), 'self'), lambda: self._mask_array(child))
@@ -487,6 +498,19 @@ class GenericPlan(GraphIteration):
                         if hasattr(fam, 'plates_to_parent') else tuple(child.plates)
                     msgs[i] = misc.sum_multiply_to_plates(
                         m, to_plates=parent.plates + dims, from_plates=own + dims, ndim=0)
+            if r != 1.0:
+                # a deterministic node scales its message like any other (node.py:589-632): e.g.
+                # the gate between mini-batch topics and the word distributions of an LDA model
+                for i, m in enumerate(msgs):
+                    if m is None:
+                        continue
+                    if isinstance(m, DArray):
+                        msgs[i] = fuse(lambda a, r_=r: a * r_, m)
+                    elif isinstance(m, (int, float, np.ndarray)):
+                        msgs[i] = m * r
+                    else:
+                        raise NotImplementedError('plate multipliers through %s are not built'
+                                                  % type(child).__name__)
             return msgs
         u = self._moments(child)
         indep = getattr(fam, 'message_independent_of_target', False)

@@ -12,6 +12,26 @@ from .node import Stochastic, Constant
 from ..utils.shapes import broadcasted_shape
 
 
+class CategoricalMoments:
+    """Moments class of categorical variables (categorical.py:25-71), here only the tag that
+    ``Constant(CategoricalMoments(K), indices)`` needs: the number of categories and the check of
+    fixed values.  The one-hot array of the reference's ``compute_fixed_moments`` is never formed:
+    an index constant keeps the integers."""
+
+    def __init__(self, categories):
+        self.categories = categories
+        self.dims = ((categories,),)
+
+    def check_fixed_value(self, x):
+        """The integer array of ``x`` after the checks of categorical.py:35-40."""
+        x = np.asanyarray(x)
+        if not (np.issubdtype(x.dtype, np.integer) or x.dtype == bool):
+            raise ValueError("Values must be integers")
+        if np.any(x < 0) or np.any(x >= self.categories):
+            raise ValueError("Invalid category index")
+        return x.astype(np.int64)
+
+
 class Categorical(Stochastic):
     _parent_count = 1
 

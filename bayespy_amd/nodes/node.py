@@ -108,11 +108,57 @@ class Node:
 
 
 class Constant(Node):
-    """Fixed numeric parent (reference: constant.py:13-86)."""
+    """Fixed numeric parent (reference: constant.py:13-86).
 
-    def __init__(self, value, name=None):
+    ``Constant(value, name=None)`` wraps an array.  ``Constant(moments, value, name=None)`` is the
+    reference's form; the only moments class built is ``CategoricalMoments(K)``: the constant then
+    holds integer class indices (``indices``), and ``Gate`` / ``Mixture`` take it as their index
+    parent exactly like a raw integer array."""
+
+    def __init__(self, value, *rest, name=None):
+        self.moments = None
+        if len(rest) == 1 and isinstance(rest[0], str) and name is None:
+            name, rest = rest[0], ()
+        if len(rest) > 1:
+            raise TypeError('Constant takes (value) or (moments, value)')
+        if rest:
+            from .categorical import CategoricalMoments
+            moments, value = value, rest[0]
+            if isinstance(moments, type):
+                raise ValueError("Give moments as an object instance instead of a class")
+            if not isinstance(moments, CategoricalMoments):
+                raise NotImplementedError(
+                    'Constant(moments, value) is built for CategoricalMoments(K) only, not for %s; '
+                    'give other constants as Constant(value)' % type(moments).__name__)
+            self.moments = moments
+            self.indices = moments.check_fixed_value(value)
+            value = self.indices
         self.value = np.asarray(value, dtype=np.float64)
         super().__init__(plates=self.value.shape, dims=((),), name=name)
+
+    def set_value(self, x):
+        """Replace the value by one of the same shape (constant.py:64-76); the plans that read
+        this constant form their copies again."""
+        if self.moments is not None:
+            x = self.moments.check_fixed_value(x)
+        x = np.asarray(x)
+        if x.shape != self.value.shape:
+            raise ValueError("Incorrect shape {0} for the array, expected {1}"
+                             .format(x.shape, self.value.shape))
+        if self.moments is not None:
+            self.indices = x
+        self.value = np.asarray(x, dtype=np.float64)
+        seen = []
+        for c, _ in self.children:
+            for n in [c] + [g for g, _ in c.children]:
+                p = n._plan
+                if p is not None and not any(p is q for q in seen):
+                    seen.append(p)
+                    changed = getattr(p, 'constant_changed', None)
+                    if changed is not None:
+                        changed(self)
+                    else:
+                        p.invalidate(n)
 
     def is_scalar(self):
         return self.value.size == 1

@@ -787,6 +787,54 @@ int32_t vmp_chain_pair_stats_limits(int64_t ny, int32_t N, int32_t D, int32_t *m
 int32_t vmp_chain_pair_stats(vmp_ctx *ctx, int64_t ny, int32_t N, int32_t D, const double *x,
                              double *Sxx, double *Sxp, double *work, int64_t work_doubles);
 
+/* Latent Dirichlet allocation: the token pass and the Dirichlet rows of the fused block
+ * (doc/source/examples/lda.rst; details: bayespy_amd/csrc/vmp_lda.hip, vmp_lda_dev.h).  n tokens, D
+ * documents, V vocabulary entries, K topics; no tokens x K, tokens x V or tokens x D array exists.
+ *   vmp_lda_limits (host only): *max_K = the largest K with an instance (64), *max_chunk = the
+ *     largest number of tokens one lane group walks in order (256).
+ *   vmp_lda_plan (host only): for (n, K) the lane group *group (power of two >= K), the tokens per
+ *     chunk *chunk (a function of (n, K) alone) and the scratch *workspace_doubles of the pass.
+ *   vmp_lda_token_pass: for every token l_k = elog_theta[doc, k] + elog_beta_t[word, k] (elog_theta:
+ *     D x K, elog_beta_t: V x K, i.e. <log beta> transposed; NULL = no word term, the moments of
+ *     `topics` under its prior), lse = max + log sum exp(l - max), phi_k = exp(l_k - lse).  Out:
+ *     Ndk (D x K) and Nvk (V x K), the sums of phi over the tokens of a document / of a word;
+ *     scal[0] = sum of lse, scal[1] = sum Ndk * elog_theta, scal[2] = sum Nvk * elog_beta_t (0
+ *     without the word term); lse (n doubles, document order); with `phi` (n x K) also phi itself,
+ *     row orig[i] for the i-th token in document order.  `labels` (document order) non-NULL: phi is
+ *     the one-hot array of these topics instead and lse = 0.
+ *     Layouts, built once per observation: tokens sorted by document -- doc_d, word_d (n) with the
+ *     offsets doc_off (D + 1); tokens sorted by word -- word_w, doc_w and pos_w (n; position of that
+ *     token in document order) with word_off (V + 1).  Indices are NOT checked against D, V, K on
+ *     the device: the caller validates them.  `phases`: 1 = document pass, 2 = word pass, 4 = the two
+ *     scal dot products; 7 = all (the parts exist for measurements).  ws: vmp_lda_plan's doubles.
+ *     No atomics: the bits of every output depend on (inputs, n, K, layouts) only; two calls give
+ *     the same bits.  Empty documents / unused words give zero rows; n = 0 gives zeros.  A topic
+ *     with l_k = -inf gets phi_k = 0; a token whose logits are ALL -inf gets NaN (lse and phi), as in
+ *     the reference.  K above the limit or n >= 2^31: VMP_ERR_UNSUPPORTED; null / negative
+ *     arguments: VMP_ERR_INVALID.
+ *   vmp_lda_dirichlet: rows x cols Dirichlet rows, element (r, c) of prior / counts / alpha / elog
+ *     at r * row_stride + c * col_stride: alpha = prior + counts (counts NULL: the prior), elog =
+ *     psi(alpha) - psi(sum_c alpha), *bound = sum over rows of the node's lower-bound term
+ *     sum_c (prior - alpha) elog + [lgamma(sum prior) - sum lgamma(prior)] - [the same of alpha]
+ *     (dirichlet.py:107-231).  ws: at least `rows` doubles.
+ *   vmp_lda_dot: *out = sum a * b over m elements, added in an order that depends on m alone
+ *     (ws: 1024 doubles). */
+int32_t vmp_lda_limits(int32_t *max_K, int32_t *max_chunk);
+int32_t vmp_lda_plan(int64_t n, int32_t K, int32_t *group, int32_t *chunk,
+                     int64_t *workspace_doubles);
+int32_t vmp_lda_token_pass(vmp_ctx *ctx, int64_t n, int64_t D, int64_t V, int32_t K,
+                           const int32_t *doc_d, const int32_t *word_d, const int64_t *doc_off,
+                           const int32_t *word_w, const int32_t *doc_w, const int32_t *pos_w,
+                           const int64_t *word_off, const int32_t *labels,
+                           const double *elog_theta, const double *elog_beta_t, int32_t phases,
+                           double *lse, double *ws, double *Ndk, double *Nvk, double *scal,
+                           const int32_t *orig, double *phi);
+int32_t vmp_lda_dirichlet(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t row_stride,
+                          int64_t col_stride, const double *prior, const double *counts,
+                          double *alpha, double *elog, double *ws, double *bound);
+int32_t vmp_lda_dot(vmp_ctx *ctx, int64_t m, const double *a, const double *b, double *ws,
+                    double *out);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
