@@ -224,6 +224,9 @@ SIGNATURES = {
                                    c_vp, c_vp]),
     'vmp_lda_dirichlet': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp]),
+    'vmp_lda_dirichlet_step_workspace': (c_i32, [c_i64, c_i64, c_i64, c_i64, P(c_i64)]),
+    'vmp_lda_dirichlet_step': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_f64, c_f64,
+                                       c_vp, c_vp, c_vp, c_vp]),
     'vmp_lda_dot': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),

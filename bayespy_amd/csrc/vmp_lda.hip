@@ -180,12 +180,26 @@ lda_sum_final_kernel(int64_t cnt, const double *__restrict__ x, double *__restri
     if (threadIdx.x == 0) out[0] = v;
 }
 
+// The parameter a Dirichlet step leaves at element e: q = prior + mult * counts, and from the
+// present alpha a step of length `scale` towards q.  scale == 1 does not read alpha (it may hold the
+// NaN of a point mass).
+__device__ __forceinline__ double lda_step_value(double p, const double *__restrict__ counts,
+                                                 int64_t e, double mult, double scale,
+                                                 const double *alpha)
+{
+    const double q = counts ? p + mult * counts[e] : p;
+    if (scale == 1.0) return q;
+    const double a = alpha[e];
+    return a + scale * (q - a);
+}
+
 // Dirichlet rows with few columns: one thread per row.  Element (r, c) of every array stands at
-// r * rs + c * cs.
+// r * rs + c * cs.  STEP: alpha moves by lda_step_value instead of being set to prior + counts.
+template <bool STEP>
 __global__ void __launch_bounds__(LDA_NT)
 lda_dirichlet_rows_kernel(int64_t rows, int cols, int64_t rs, int64_t cs,
                           const double *__restrict__ prior, const double *__restrict__ counts,
-                          double *__restrict__ alpha, double *__restrict__ elog,
+                          double mult, double scale, double *alpha, double *__restrict__ elog,
                           double *__restrict__ rowL)
 {
     const int64_t r = (int64_t)blockIdx.x * LDA_NT + threadIdx.x;
@@ -194,7 +208,8 @@ lda_dirichlet_rows_kernel(int64_t rows, int cols, int64_t rs, int64_t cs,
     for (int c = 0; c < cols; ++c) {
         const int64_t e = r * rs + c * cs;
         const double p = prior[e];
-        const double v = counts ? p + counts[e] : p;
+        const double v = STEP ? lda_step_value(p, counts, e, mult, scale, alpha)
+                              : (counts ? p + counts[e] : p);
         alpha[e] = v;
         s += v;
         s0 += p;
@@ -214,10 +229,11 @@ lda_dirichlet_rows_kernel(int64_t rows, int cols, int64_t rs, int64_t cs,
 }
 
 // Dirichlet rows with many columns: one workgroup per row
+template <bool STEP>
 __global__ void __launch_bounds__(LDA_NT)
 lda_dirichlet_wide_kernel(int64_t cols, int64_t rs, int64_t cs, const double *__restrict__ prior,
-                          const double *__restrict__ counts, double *__restrict__ alpha,
-                          double *__restrict__ elog, double *__restrict__ rowL)
+                          const double *__restrict__ counts, double mult, double scale,
+                          double *alpha, double *__restrict__ elog, double *__restrict__ rowL)
 {
     __shared__ double red[LDA_NT / 64];
     const int64_t r = blockIdx.x;
@@ -225,7 +241,8 @@ lda_dirichlet_wide_kernel(int64_t cols, int64_t rs, int64_t cs, const double *__
     for (int64_t c = threadIdx.x; c < cols; c += LDA_NT) {
         const int64_t e = r * rs + c * cs;
         const double p = prior[e];
-        const double v = counts ? p + counts[e] : p;
+        const double v = STEP ? lda_step_value(p, counts, e, mult, scale, alpha)
+                              : (counts ? p + counts[e] : p);
         alpha[e] = v;
         s += v;
         s0 += p;
@@ -247,6 +264,126 @@ lda_dirichlet_wide_kernel(int64_t cols, int64_t rs, int64_t cs, const double *__
     g0 = block_sum<LDA_NT>(g0, red);
     L = block_sum<LDA_NT>(L, red);
     if (threadIdx.x == 0) rowL[r] = L + (vmp_lgamma(s0) - g0) - (vmp_lgamma(s) - g);
+}
+
+// -- the step on a transposed table ------------------------------------------------------------------
+// `p_word` is kept as V x K (vocabulary entry c, topic r at c * K + r): the Dirichlet rows run down
+// the strided axis, the memory along K.  A workgroup owns `cpb` consecutive vocabulary entries, i.e.
+// one contiguous piece of cpb * K doubles, and walks it with the first per * K of its threads
+// (per = LDA_NT / K whole vocabulary entries per sweep): consecutive lanes touch consecutive
+// doubles and a thread keeps the topic r = t % K throughout, so its running sums belong to one
+// Dirichlet row.  The grid is a function of (V, K) alone and every sum has a fixed order.
+constexpr int LDA_T_MAX_BLOCKS = 2048;
+constexpr int LDA_T_MIN_SWEEPS = 4;
+
+struct TGrid {
+    int per;            // vocabulary entries per sweep of a workgroup
+    int64_t cpb, nb;    // vocabulary entries per workgroup, workgroups
+};
+
+inline TGrid lda_t_grid(int64_t V, int K)
+{
+    TGrid g;
+    g.per = LDA_NT / K;
+    g.cpb = (V + LDA_T_MAX_BLOCKS - 1) / LDA_T_MAX_BLOCKS;
+    if (g.cpb < (int64_t)LDA_T_MIN_SWEEPS * g.per) g.cpb = (int64_t)LDA_T_MIN_SWEEPS * g.per;
+    g.nb = (V + g.cpb - 1) / g.cpb;
+    return g;
+}
+
+// ws of the transposed step: [nb] bound partials, [K] row constants, [K] psi(row sum),
+// [nb x 2 x K] partial row sums of alpha and of the prior
+inline int64_t lda_t_ws_doubles(int64_t V, int K)
+{
+    const TGrid g = lda_t_grid(V, K);
+    return g.nb + 2 * (int64_t)K + 2 * g.nb * K;
+}
+
+// first pass: alpha, and per workgroup the partial sums over its vocabulary entries
+__global__ void __launch_bounds__(LDA_NT)
+lda_step_t_alpha_kernel(int64_t V, int K, int64_t cpb, const double *__restrict__ prior,
+                        const double *__restrict__ counts, double mult, double scale,
+                        double *alpha, double *__restrict__ part)
+{
+    __shared__ double sh[2][LDA_NT];
+    const int t = threadIdx.x;
+    const int per = LDA_NT / K;
+    const int64_t c0 = (int64_t)blockIdx.x * cpb;
+    const int64_t c1 = (c0 + cpb < V) ? c0 + cpb : V;
+    double s = 0.0, s0 = 0.0;
+    if (t < per * K) {
+        const int64_t end = c1 * K, stride = (int64_t)per * K;
+        for (int64_t e = c0 * K + t; e < end; e += stride) {
+            const double p = prior[e];
+            const double v = lda_step_value(p, counts, e, mult, scale, alpha);
+            alpha[e] = v;
+            s += v;
+            s0 += p;
+        }
+    }
+    sh[0][t] = s;
+    sh[1][t] = s0;
+    __syncthreads();
+    if (t < K) {
+        double a = 0.0, b = 0.0;
+        for (int i = 0; i < per; ++i) {
+            a += sh[0][t + i * K];
+            b += sh[1][t + i * K];
+        }
+        part[((int64_t)blockIdx.x * 2) * K + t] = a;
+        part[((int64_t)blockIdx.x * 2 + 1) * K + t] = b;
+    }
+}
+
+// one workgroup per Dirichlet row: the partials in a fixed order, then what the second pass needs
+// of the row sums
+__global__ void __launch_bounds__(LDA_NT)
+lda_step_t_combine_kernel(int64_t nb, int K, const double *__restrict__ part,
+                          double *__restrict__ rowc, double *__restrict__ psis)
+{
+    __shared__ double red[LDA_NT / 64];
+    const int r = blockIdx.x;
+    double s = 0.0, s0 = 0.0;
+    for (int64_t b = threadIdx.x; b < nb; b += LDA_NT) {
+        s += part[(b * 2) * K + r];
+        s0 += part[(b * 2 + 1) * K + r];
+    }
+    s = block_sum<LDA_NT>(s, red);
+    s0 = block_sum<LDA_NT>(s0, red);
+    if (threadIdx.x == 0) {
+        psis[r] = vmp_digamma(s);
+        rowc[r] = vmp_lgamma(s0) - vmp_lgamma(s);
+    }
+}
+
+// second pass: <log> and the partial sums of the bound
+__global__ void __launch_bounds__(LDA_NT)
+lda_step_t_elog_kernel(int64_t V, int K, int64_t cpb, const double *__restrict__ prior,
+                       const double *__restrict__ alpha, const double *__restrict__ psis,
+                       double *__restrict__ elog, double *__restrict__ bpart)
+{
+    __shared__ double red[LDA_NT / 64];
+    const int t = threadIdx.x;
+    const int per = LDA_NT / K;
+    const int64_t c0 = (int64_t)blockIdx.x * cpb;
+    const int64_t c1 = (c0 + cpb < V) ? c0 + cpb : V;
+    double g = 0.0, g0 = 0.0, L = 0.0;
+    if (t < per * K) {
+        const double psi_row = psis[t % K];
+        const int64_t end = c1 * K, stride = (int64_t)per * K;
+        for (int64_t e = c0 * K + t; e < end; e += stride) {
+            const double p = prior[e], v = alpha[e];
+            const double el = vmp_digamma(v) - psi_row;
+            elog[e] = el;
+            g += vmp_lgamma(v);
+            g0 += vmp_lgamma(p);
+            L += (p - v) * el;
+        }
+    }
+    g = block_sum<LDA_NT>(g, red);
+    g0 = block_sum<LDA_NT>(g0, red);
+    L = block_sum<LDA_NT>(L, red);
+    if (t == 0) bpart[blockIdx.x] = L + (g - g0);
 }
 
 inline int64_t chunks_of(int64_t n, int T) { return n > 0 ? (n + T - 1) / T : 0; }
@@ -392,15 +529,81 @@ int32_t vmp_lda_dirichlet(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t row_
         return VMP_OK;
     }
     if (cols <= 64)
-        hipLaunchKernelGGL(lda_dirichlet_rows_kernel, dim3((unsigned)((rows + LDA_NT - 1) / LDA_NT)),
-                           dim3(LDA_NT), 0, ctx->stream, rows, (int)cols, row_stride, col_stride,
-                           prior, counts, alpha, elog, ws);
+        hipLaunchKernelGGL(lda_dirichlet_rows_kernel<false>,
+                           dim3((unsigned)((rows + LDA_NT - 1) / LDA_NT)), dim3(LDA_NT), 0,
+                           ctx->stream, rows, (int)cols, row_stride, col_stride, prior, counts, 1.0,
+                           1.0, alpha, elog, ws);
     else
-        hipLaunchKernelGGL(lda_dirichlet_wide_kernel, dim3((unsigned)rows), dim3(LDA_NT), 0,
-                           ctx->stream, cols, row_stride, col_stride, prior, counts, alpha, elog,
-                           ws);
+        hipLaunchKernelGGL(lda_dirichlet_wide_kernel<false>, dim3((unsigned)rows), dim3(LDA_NT), 0,
+                           ctx->stream, cols, row_stride, col_stride, prior, counts, 1.0, 1.0,
+                           alpha, elog, ws);
     hipLaunchKernelGGL(lda_sum_final_kernel, dim3(1), dim3(LDA_RED_NT), 0, ctx->stream, rows, ws,
                        bound);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+// the table is stored transposed (the rows run down the strided axis) and has few enough rows for
+// the kernel pair that walks the memory in order
+static inline bool lda_step_transposed(int64_t rows, int64_t row_stride, int64_t col_stride)
+{
+    return row_stride == 1 && col_stride == rows && rows <= LDA_MAX_K;
+}
+
+int32_t vmp_lda_dirichlet_step_workspace(int64_t rows, int64_t cols, int64_t row_stride,
+                                         int64_t col_stride, int64_t *workspace_doubles)
+{
+    if (rows < 0 || cols < 1 || row_stride < 1 || col_stride < 1 || !workspace_doubles)
+        return VMP_ERR_INVALID;
+    if (rows > 0 && lda_step_transposed(rows, row_stride, col_stride))
+        *workspace_doubles = lda_t_ws_doubles(cols, (int)rows);
+    else
+        *workspace_doubles = rows > 0 ? rows : 1;
+    return VMP_OK;
+}
+
+int32_t vmp_lda_dirichlet_step(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t row_stride,
+                               int64_t col_stride, const double *prior, const double *counts,
+                               double mult, double scale, double *alpha, double *elog, double *ws,
+                               double *bound)
+{
+    VMP_FLUSH_SMALL(ctx);
+    VMP_REQUIRE(ctx, ctx && rows >= 0 && cols >= 1 && row_stride >= 1 && col_stride >= 1,
+                VMP_ERR_INVALID, "bad arguments");
+    VMP_REQUIRE(ctx, mult > 0.0 && scale == scale && mult == mult, VMP_ERR_INVALID,
+                "mult must be positive, scale a number");
+    VMP_REQUIRE(ctx, bound && ws && (rows == 0 || (prior && alpha && elog)), VMP_ERR_INVALID,
+                "null argument");
+    if (rows == 0) {
+        VMP_HIP_CHECK(ctx, hipMemsetAsync(bound, 0, sizeof(double), ctx->stream));
+        return VMP_OK;
+    }
+    if (lda_step_transposed(rows, row_stride, col_stride)) {
+        const int K = (int)rows;
+        const TGrid g = lda_t_grid(cols, K);
+        double *bpart = ws, *rowc = ws + g.nb, *psis = rowc + K, *part = psis + K;
+        hipLaunchKernelGGL(lda_step_t_alpha_kernel, dim3((unsigned)g.nb), dim3(LDA_NT), 0,
+                           ctx->stream, cols, K, g.cpb, prior, counts, mult, scale, alpha, part);
+        hipLaunchKernelGGL(lda_step_t_combine_kernel, dim3((unsigned)K), dim3(LDA_NT), 0,
+                           ctx->stream, g.nb, K, part, rowc, psis);
+        hipLaunchKernelGGL(lda_step_t_elog_kernel, dim3((unsigned)g.nb), dim3(LDA_NT), 0,
+                           ctx->stream, cols, K, g.cpb, prior, alpha, psis, elog, bpart);
+        // bound partials and row constants stand side by side
+        hipLaunchKernelGGL(lda_sum_final_kernel, dim3(1), dim3(LDA_RED_NT), 0, ctx->stream,
+                           g.nb + K, ws, bound);
+    } else {
+        if (cols <= 64)
+            hipLaunchKernelGGL(lda_dirichlet_rows_kernel<true>,
+                               dim3((unsigned)((rows + LDA_NT - 1) / LDA_NT)), dim3(LDA_NT), 0,
+                               ctx->stream, rows, (int)cols, row_stride, col_stride, prior, counts,
+                               mult, scale, alpha, elog, ws);
+        else
+            hipLaunchKernelGGL(lda_dirichlet_wide_kernel<true>, dim3((unsigned)rows), dim3(LDA_NT),
+                               0, ctx->stream, cols, row_stride, col_stride, prior, counts, mult,
+                               scale, alpha, elog, ws);
+        hipLaunchKernelGGL(lda_sum_final_kernel, dim3(1), dim3(LDA_RED_NT), 0, ctx->stream, rows,
+                           ws, bound);
+    }
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }

@@ -8,9 +8,11 @@ from .masked_pca import MaskedPCAPlan
 from .gmm import GMMPlan
 from .lssm import LSSMPlan
 from .lssm_masked import MaskedLSSMPlan
-from .lda import LDAPlan
+from .lda import LDAPlan, LDASVIPlan
 
 PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
+# engine='fused': a block's opt-in form takes the place of its default form
+OPT_IN_FORMS = {LDAPlan: LDASVIPlan}
 
 
 def _reusable_plans(nodes, engine, options=None):
@@ -32,6 +34,10 @@ def _reusable_plans(nodes, engine, options=None):
         return None
     if engine == 'generic' and not all(isinstance(p, GenericPlan) for p in plans):
         return None
+    if engine == 'fused' and any(isinstance(p, GenericPlan) for p in plans):
+        return None
+    if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values() for p in plans):
+        return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
     if not all(id(n) in covered for n in nodes):
         return None
@@ -79,12 +85,13 @@ def compile_model(nodes, engine=None, **options):
         plan = GenericPlan(nodes)
         plan._engine_request = 'generic'
         return [plan]
+    types = [OPT_IN_FORMS.get(P, P) for P in PLAN_TYPES] if engine == 'fused' else PLAN_TYPES
     remaining = [n for n in nodes]
     plans = []
     progress = True
     while progress:
         progress = False
-        for P in PLAN_TYPES:
+        for P in types:
             roles = P.match(remaining)
             if roles is not None:
                 plan = P(roles, **options)
@@ -94,6 +101,22 @@ def compile_model(nodes, engine=None, **options):
                 progress = True
                 break
     left = [n for n in remaining if isinstance(n, Stochastic)]
+    if left and engine == 'fused':
+        why = []
+        for P in types:
+            try:
+                P.match(remaining, why)
+            except TypeError:       # a test double without the diagnostic argument
+                pass
+        for p in plans:                 # the blocks that did match let go of their nodes
+            for n in p.nodes():
+                n._plan = None
+        raise NotImplementedError(
+            "engine='fused': no fused block covers %s%s" % (
+                ', '.join(n.name for n in left),
+                ' -- ' + '; '.join(dict.fromkeys(why)) if why else
+                ' (the blocks: ' + '; '.join(P.describe() for P in types
+                                             if hasattr(P, 'describe')) + ')'))
     if left:
         # nodes outside the fused blocks: the whole model runs on the generic device
         # message-passing engine (raises NotImplementedError for unknown node types).  A model

@@ -62,6 +62,20 @@ class LDAKernels:
             self.ctx, rows, cols, rs, cs, ptr(prior), ptr(counts) if counts is not None else None,
             ptr(alpha), ptr(elog), ptr(ws), ptr(bound)))
 
+    def dirichlet_step_ws(self, rows, cols, rs, cs):
+        """Doubles of the workspace of ``dirichlet_step`` for this table."""
+        w = ctypes.c_int64()
+        rc = self.lib.vmp_lda_dirichlet_step_workspace(rows, cols, rs, cs, ctypes.byref(w))
+        if rc != _lib.VMP_OK:
+            _lib.raise_for_status(rc, 'vmp_lda_dirichlet_step_workspace')
+        return w.value
+
+    def dirichlet_step(self, rows, cols, rs, cs, prior, counts, mult, scale, alpha, elog, ws,
+                       bound):
+        self.rt.check(self.lib.vmp_lda_dirichlet_step(
+            self.ctx, rows, cols, rs, cs, ptr(prior), ptr(counts) if counts is not None else None,
+            float(mult), float(scale), ptr(alpha), ptr(elog), ptr(ws), ptr(bound)))
+
     def dot(self, m, a, b, ws, out):
         self.rt.check(self.lib.vmp_lda_dot(self.ctx, m, ptr(a), ptr(b), ptr(ws), ptr(out)))
 
@@ -86,6 +100,101 @@ def _structure(words):
                 gate_topic=g1, document_indices=idx)
 
 
+def _no_multiplier(words, topics, p_word, p_topic):
+    if any(any(m != 1 for m in n.plates_multiplier) for n in (words, topics, p_word, p_topic)):
+        return ('plates_multiplier (mini-batches) goes through the generic engine '
+                '(VB(..., engine="fused") runs mini-batches of tokens on the block)')
+    return None
+
+
+def _scalar_multiplier(node):
+    """The one factor of a node with at most one plate axis, or None."""
+    m = tuple(np.ravel(node.plates_multiplier))
+    if len(m) > 1:
+        return None
+    return float(m[0]) if m else 1.0
+
+
+def _batch_multiplier(words, topics, p_word, p_topic):
+    if any(any(m != 1 for m in n.plates_multiplier) for n in (p_word, p_topic)):
+        return 'a Dirichlet carries a plates_multiplier'
+    mw, mt = _scalar_multiplier(words), _scalar_multiplier(topics)
+    if mw is None or mt is None or not (mw > 0 and mt > 0):
+        return ('the plates_multiplier of words / topics is not one positive factor: %s, %s'
+                % (tuple(words.plates_multiplier), tuple(topics.plates_multiplier)))
+    if mw != mt:
+        return ('words and topics carry unequal plates_multiplier (%r and %r)' % (mw, mt))
+    return None
+
+
+def _match(nodes, why, multiplier_rule):
+    """The roles of the first latent-Dirichlet-allocation structure among ``nodes`` that meets
+    every condition of the block, or None; ``multiplier_rule`` says what plate multipliers may
+    be there (a reason, or None)."""
+    for words in nodes:
+        r = _structure(words)
+        if r is None:
+            continue
+
+        def no(msg, words=words):
+            if why is not None:
+                why.append('fused LDA block, observed node %s: %s'
+                           % (words.name or '<unnamed>', msg))
+        topics, p_word, p_topic = r['topics'], r['p_word'], r['p_topic']
+        g1, g2, idx = r['gate_topic'], r['gate_word'], r['document_indices']
+        four = (words, topics, p_word, p_topic)
+        if not all(any(n is m for m in nodes) for n in four):
+            continue
+        bad = multiplier_rule(words, topics, p_word, p_topic)
+        if bad:
+            no(bad)
+            continue
+        if any(getattr(n, '_shard_axis', None) is not None for n in r.values()):
+            no('a plate is sharded over ranks')
+            continue
+        if not words.observed:
+            no('it is not observed')
+            continue
+        if words._mask is not True:
+            no('it has a mask')
+            continue
+        bad = [n for n in (p_topic, p_word) if not isinstance(n.parents[0], Constant)]
+        if bad:
+            no('the concentration of %s is a node (%s), not a constant'
+               % (bad[0].name, type(bad[0].parents[0]).__name__))
+            continue
+        if len(topics.plates) != 1 or idx.value.ndim != 1:
+            no('it needs one token plate axis, topics has plates %s and the indices have '
+               'shape %s' % (topics.plates, idx.value.shape))
+            continue
+        n, K = topics.plates[0], topics.categories
+        if g1.gated_plate != -1 or g2.gated_plate != -1 or len(p_topic.plates) != 1 \
+                or p_word.plates != (K,) or idx.value.shape != (n,) or words.plates != (n,):
+            no('plates of p_topic / p_word / indices are not (D,), (K,), (n,)')
+            continue
+        if K > LDA_MAX_K:
+            no('n_topics = %d exceeds the limit of the block (K <= %d)' % (K, LDA_MAX_K))
+            continue
+        kids = ((p_topic, [g1]), (g1, [topics]), (topics, [g2]), (p_word, [g2]),
+                (g2, [words]), (words, []))
+        if any([c for c, _ in n.children] != want for n, want in kids) \
+                or any(c is not g1 for c, _ in idx.children):
+            no('one of its roles has other children as well')
+            continue
+        if topics.observed or p_topic.observed or p_word.observed:
+            no('topics or a Dirichlet is observed')
+            continue
+        if topics._init is not None and topics._init[0] != 'value':
+            no('topics is initialised by %s' % topics._init[0])
+            continue
+        if any(n._init is not None and n._init[0] not in ('value', 'random')
+               for n in (p_topic, p_word)):
+            no('a Dirichlet is initialised from parameters')
+            continue
+        return r
+    return None
+
+
 class LDAPlan:
 
     @staticmethod
@@ -96,67 +205,10 @@ class LDAPlan:
 
     @staticmethod
     def match(nodes, why=None):
-        for words in nodes:
-            r = _structure(words)
-            if r is None:
-                continue
+        return _match(nodes, why, _no_multiplier)
 
-            def no(msg, words=words):
-                if why is not None:
-                    why.append('fused LDA block, observed node %s: %s'
-                               % (words.name or '<unnamed>', msg))
-            topics, p_word, p_topic = r['topics'], r['p_word'], r['p_topic']
-            g1, g2, idx = r['gate_topic'], r['gate_word'], r['document_indices']
-            four = (words, topics, p_word, p_topic)
-            if not all(any(n is m for m in nodes) for n in four):
-                continue
-            if any(any(m != 1 for m in n.plates_multiplier) for n in four):
-                no('plates_multiplier (mini-batches) goes through the generic engine')
-                continue
-            if any(getattr(n, '_shard_axis', None) is not None for n in r.values()):
-                no('a plate is sharded over ranks')
-                continue
-            if not words.observed:
-                no('it is not observed')
-                continue
-            if words._mask is not True:
-                no('it has a mask')
-                continue
-            bad = [n for n in (p_topic, p_word) if not isinstance(n.parents[0], Constant)]
-            if bad:
-                no('the concentration of %s is a node (%s), not a constant'
-                   % (bad[0].name, type(bad[0].parents[0]).__name__))
-                continue
-            if len(topics.plates) != 1 or idx.value.ndim != 1:
-                no('it needs one token plate axis, topics has plates %s and the indices have '
-                   'shape %s' % (topics.plates, idx.value.shape))
-                continue
-            n, K = topics.plates[0], topics.categories
-            if g1.gated_plate != -1 or g2.gated_plate != -1 or len(p_topic.plates) != 1 \
-                    or p_word.plates != (K,) or idx.value.shape != (n,) or words.plates != (n,):
-                no('plates of p_topic / p_word / indices are not (D,), (K,), (n,)')
-                continue
-            if K > LDA_MAX_K:
-                no('n_topics = %d exceeds the limit of the block (K <= %d)' % (K, LDA_MAX_K))
-                continue
-            kids = ((p_topic, [g1]), (g1, [topics]), (topics, [g2]), (p_word, [g2]),
-                    (g2, [words]), (words, []))
-            if any([c for c, _ in n.children] != want for n, want in kids) \
-                    or any(c is not g1 for c, _ in idx.children):
-                no('one of its roles has other children as well')
-                continue
-            if topics.observed or p_topic.observed or p_word.observed:
-                no('topics or a Dirichlet is observed')
-                continue
-            if topics._init is not None and topics._init[0] != 'value':
-                no('topics is initialised by %s' % topics._init[0])
-                continue
-            if any(n._init is not None and n._init[0] not in ('value', 'random')
-                   for n in (p_topic, p_word)):
-                no('a Dirichlet is initialised from parameters')
-                continue
-            return r
-        return None
+    def _token_multiplier(self):
+        return 1.0
 
     def __init__(self, roles, runtime=None, kernels=None):
         self.roles = roles
@@ -170,6 +222,7 @@ class LDAPlan:
         self._rt, self._kernels = runtime, kernels
         self._ready = False
         self._layout_stale = False
+        self._lazy_recount = False
         self._version = 0
         self._L_version = -1
         self._L = None
@@ -214,15 +267,15 @@ class LDAPlan:
         self._version += 1
 
     # -- set-up ------------------------------------------------------------------------------------
-    def _indices(self, x, upper):
-        """int64 device tensor of the indices ``x`` after the reference's checks
-        (categorical.py:35-40)."""
+    def _index_tensor(self, x):
+        """(int64 device tensor of the n indices ``x``, device flag "a value is no integer" or
+        None): a host array is checked on the host, a tensor stays where it is."""
         torch = self.rt.torch
+        frac = None
         if isinstance(x, torch.Tensor):
             t = x.to(self.rt.device)
             if t.dtype.is_floating_point:
-                if bool((t != t.round()).any().item()):
-                    raise ValueError("Values must be integers")
+                frac = (t != t.round()).any()
             t = t.to(torch.int64)
         else:
             a = np.asarray(x)
@@ -236,9 +289,21 @@ class LDAPlan:
         t = t.reshape(-1)
         if t.numel() != self.n:
             t = t.expand(self.n).contiguous()
+        return t, frac
+
+    def _indices(self, x, upper):
+        """int64 device tensor of the indices ``x`` after the reference's checks
+        (categorical.py:35-40)."""
+        t, frac = self._index_tensor(x)
+        if frac is not None and bool(frac.item()):
+            raise ValueError("Values must be integers")
         if t.numel() and (int(t.min().item()) < 0 or int(t.max().item()) >= upper):
             raise ValueError("Invalid category index")
         return t
+
+    def _token_indices(self):
+        """(documents, words) of the tokens as checked int64 device tensors."""
+        return self._indices(self.index.value, self.D), self._indices(self.words._data, self.V)
 
     def _build_layouts(self):
         """Tokens sorted by (document, word) with document offsets, and sorted by (word, document)
@@ -247,8 +312,7 @@ class LDAPlan:
         torch = rt.torch
         if self.words._data is None:
             raise ValueError('Node %s has not been observed' % self.words.name)
-        doc = self._indices(self.index.value, self.D)
-        word = self._indices(self.words._data, self.V)
+        doc, word = self._token_indices()
         n, D, V = self.n, self.D, self.V
         order = torch.argsort(doc * V + word, stable=True)
         doc_d, word_d = doc[order], word[order]
@@ -286,11 +350,13 @@ class LDAPlan:
         with np.errstate(divide='ignore'):
             return np.log(x)
 
-    def _materialize(self):
+    def _materialize(self, recount=True):
+        """``recount=False``: the caller forms the counts on the new layouts itself."""
         if self._ready:
             if self._layout_stale:
                 self._build_layouts()
-                self._recount()
+                if recount:
+                    self._recount()
             return
         self._delta = _delta.delta_roles(self.roles)
         rt, k = self.rt, self.kernels
@@ -350,7 +416,7 @@ class LDAPlan:
 
     # -- operations ----------------------------------------------------------------------------------
     def update(self, node):
-        self._materialize()
+        self._materialize(recount=not (self._lazy_recount and node is self.topics))
         _delta.updated(self._delta, self.roles, node)
         rt, k = self.rt, self.kernels
         rt.sync_stream()
@@ -363,15 +429,21 @@ class LDAPlan:
             self.has_word_term = True
             k.token_pass(self.n, D, V, K, self.lay, None, self.used_theta, self.used_beta_t, 7,
                          self.lse, self.ws, self.Ndk, self.Nvk, self.scal)
-        elif node is self.p_topic:
-            k.dirichlet(D, K, K, 1, self.prior_theta, self.Ndk, self.alpha_theta, self.elog_theta,
-                        self.ws_small, self.scal[3:4])
-        elif node is self.p_word:
-            k.dirichlet(K, V, 1, K, self.prior_beta_t, self.Nvk, self.alpha_beta_t,
-                        self.elog_beta_t, self.ws_small, self.scal[4:5])
+        elif node is self.p_topic or node is self.p_word:
+            self._update_dirichlet(node)
         else:
             return
         self._version += 1
+
+    def _update_dirichlet(self, node):
+        k = self.kernels
+        D, V, K = self.D, self.V, self.K
+        if node is self.p_topic:
+            k.dirichlet(D, K, K, 1, self.prior_theta, self.Ndk, self.alpha_theta, self.elog_theta,
+                        self.ws_small, self.scal[3:4])
+        else:
+            k.dirichlet(K, V, 1, K, self.prior_beta_t, self.Nvk, self.alpha_beta_t,
+                        self.elog_beta_t, self.ws_small, self.scal[4:5])
 
     def _lower_bound_terms(self):
         self._materialize()
@@ -382,8 +454,9 @@ class LDAPlan:
             k.dot(self.V * self.K, self.Nvk, self.elog_beta_t, self.ws_small, self.scal[6:7])
             s = self.scal.cpu().numpy()
             entropy = 0.0 if self.labels is not None else float(s[0] - s[1] - s[2])
-            t = dict(words=float(s[6]), topics=float(s[5]) + entropy, p_topic=float(s[3]),
-                     p_word=float(s[4]))
+            m = self._token_multiplier()
+            t = dict(words=m * float(s[6]), topics=m * (float(s[5]) + entropy),
+                     p_topic=float(s[3]), p_word=float(s[4]))
             t['total'] = t['words'] + t['topics'] + t['p_topic'] + t['p_word']
             self._L = t
             self._L_version = self._version
@@ -469,4 +542,123 @@ class LDAPlan:
         for name in self._SAVED:
             getattr(self, name).copy_(torch.from_numpy(
                 np.array(reader.get(base + name), dtype=np.float64)).to(self.rt.device))
+        self._version += 1
+
+
+class LDASVIPlan(LDAPlan):
+    """The block under stochastic variational inference (lda.rst, second half): ``words`` and
+    ``topics`` hold a mini-batch of n tokens that stands for ``m`` times as many
+    (``plates_multiplier``), every step re-observes ``words``, sets the document indices and updates
+    ``topics`` -- one token pass over the batch -- and ``gradient_step`` moves the two corpus-sized
+    Dirichlet tables along their natural gradients (``vmp_lda_dirichlet_step``).  Opt-in:
+    ``VB(..., engine='fused')``."""
+
+    @staticmethod
+    def describe():
+        return LDAPlan.describe() + ('; words and topics may carry one equal plates_multiplier '
+                                     '(mini-batches of tokens)')
+
+    @staticmethod
+    def match(nodes, why=None):
+        return _match(nodes, why, _batch_multiplier)
+
+    def __init__(self, roles, runtime=None, kernels=None):
+        super().__init__(roles, runtime=runtime, kernels=kernels)
+        self._lazy_recount = True
+        self._ws_step = None
+        self._m_seen = _scalar_multiplier(self.topics)
+
+    def _token_multiplier(self):
+        """The multiplier of the token plate as the nodes carry it now (it has a setter)."""
+        bad = _batch_multiplier(self.words, self.topics, self.p_word, self.p_topic)
+        if bad:
+            raise ValueError('fused LDA block: ' + bad)
+        return _scalar_multiplier(self.topics)
+
+    def invalidate(self, node):
+        if node is self.words and node.observed and node._mask is True:
+            self._layout_stale = True
+            self._version += 1
+            return
+        if (node is self.words or node is self.topics) \
+                and LDASVIPlan.match(self.nodes()) is not None \
+                and _scalar_multiplier(self.topics) != self._m_seen:
+            # the setter of plates_multiplier: the state stays, the next operation reads the factor
+            self._m_seen = _scalar_multiplier(self.topics)
+            self._version += 1
+            return
+        _delta.warn_state_discarded(self, node)
+        self._ready = False
+        self._version += 1
+        if LDASVIPlan.match(self.nodes()) is None:
+            from .generic import GenericPlan
+            GenericPlan(self.nodes())
+
+    def _token_indices(self):
+        """Both index arrays with ONE device -> host read for all of the reference's checks."""
+        torch = self.rt.torch
+        index = getattr(self.index, 'device_value', None)
+        doc, f1 = self._index_tensor(self.index.value if index is None else index)
+        word, f2 = self._index_tensor(self.words._data)
+        if self.n:
+            no = torch.zeros((), dtype=torch.bool, device=doc.device)
+            flags = torch.stack([f1 if f1 is not None else no, f2 if f2 is not None else no,
+                                 (doc.min() < 0) | (doc.max() >= self.D),
+                                 (word.min() < 0) | (word.max() >= self.V)]).cpu().numpy()
+            if flags[0] or flags[1]:
+                raise ValueError("Values must be integers")
+            if flags[2] or flags[3]:
+                raise ValueError("Invalid category index")
+        return doc, word
+
+    def _step_ws(self):
+        if self._ws_step is None:
+            k = self.kernels
+            self._ws_step = self.rt.empty(max(
+                k.dirichlet_step_ws(self.D, self.K, self.K, 1),
+                k.dirichlet_step_ws(self.K, self.V, 1, self.K), 1))
+        return self._ws_step
+
+    def _step(self, node, mult, scale):
+        k, ws = self.kernels, self._step_ws()
+        D, V, K = self.D, self.V, self.K
+        if node is self.p_topic:
+            k.dirichlet_step(D, K, K, 1, self.prior_theta, self.Ndk, mult, scale, self.alpha_theta,
+                             self.elog_theta, ws, self.scal[3:4])
+        else:
+            k.dirichlet_step(K, V, 1, K, self.prior_beta_t, self.Nvk, mult, scale,
+                             self.alpha_beta_t, self.elog_beta_t, ws, self.scal[4:5])
+
+    def _update_dirichlet(self, node):
+        self._step(node, self._token_multiplier(), 1.0)
+
+    def gradient_step(self, nodes, scale=1.0):
+        """alpha <- alpha + scale * (prior + m * counts - alpha) for the Dirichlets among ``nodes``:
+        the counts are those of the present ``topics`` state, so every optimum is taken before
+        any node moves.  A Dirichlet that is still a point mass steps from its prior, as on the
+        generic engine (its parameters there are the prior's until the first update)."""
+        from ...nodes.node import Stochastic
+        todo = []
+        for node in nodes:
+            if not isinstance(node, Stochastic) or node.observed:
+                continue
+            if node is self.topics:
+                raise NotImplementedError(
+                    'gradient step of %s: the fused LDA block keeps no responsibilities to step '
+                    'from; update it (Q.update(%r)), or use VB(..., engine="generic")'
+                    % (node.name, node.name))
+            if node is self.p_topic or node is self.p_word:
+                todo.append(node)
+        if not todo:
+            return
+        self._materialize()
+        m = self._token_multiplier()
+        self.rt.sync_stream()
+        for node in todo:
+            key = 'p_topic' if node is self.p_topic else 'p_word'
+            if key in self._delta and float(scale) != 1.0:
+                (self.alpha_theta if node is self.p_topic else self.alpha_beta_t).copy_(
+                    self.prior_theta if node is self.p_topic else self.prior_beta_t)
+            _delta.updated(self._delta, self.roles, node)
+            self._step(node, m, scale)
         self._version += 1

@@ -117,6 +117,8 @@ class Constant(Node):
 
     def __init__(self, value, *rest, name=None):
         self.moments = None
+        self.device_value = None
+        self._indices = None
         if len(rest) == 1 and isinstance(rest[0], str) and name is None:
             name, rest = rest[0], ()
         if len(rest) > 1:
@@ -131,23 +133,61 @@ class Constant(Node):
                     'Constant(moments, value) is built for CategoricalMoments(K) only, not for %s; '
                     'give other constants as Constant(value)' % type(moments).__name__)
             self.moments = moments
-            self.indices = moments.check_fixed_value(value)
-            value = self.indices
+            value = moments.check_fixed_value(value)
+            self._indices = value
         self.value = np.asarray(value, dtype=np.float64)
         super().__init__(plates=self.value.shape, dims=((),), name=name)
 
+    @property
+    def value(self):
+        """The host array.  After ``set_value`` with a device tensor it is formed (and checked)
+        on first use: a plan that reads ``device_value`` never causes the copy."""
+        if self._value is None:
+            x = self.moments.check_fixed_value(self.device_value.cpu().numpy())
+            self.indices = x
+            self._value = np.asarray(x, dtype=np.float64)
+        return self._value
+
+    @value.setter
+    def value(self, x):
+        self._value = x
+
+    @property
+    def indices(self):
+        """The class indices of a ``Constant(CategoricalMoments(K), ...)`` as a host array."""
+        if self.moments is None:
+            raise AttributeError('indices')
+        if self._value is None:
+            self.value                  # forms the host copy of a device value
+        return self._indices
+
+    @indices.setter
+    def indices(self, x):
+        self._indices = x
+
     def set_value(self, x):
         """Replace the value by one of the same shape (constant.py:64-76); the plans that read
-        this constant form their copies again."""
-        if self.moments is not None:
-            x = self.moments.check_fixed_value(x)
-        x = np.asarray(x)
-        if x.shape != self.value.shape:
-            raise ValueError("Incorrect shape {0} for the array, expected {1}"
-                             .format(x.shape, self.value.shape))
-        if self.moments is not None:
-            self.indices = x
-        self.value = np.asarray(x, dtype=np.float64)
+        this constant form their copies again.  Class indices (``CategoricalMoments``) may be
+        given as an integer tensor that lives on the device: it is kept there
+        (``device_value``), and the plan that reads it checks the indices."""
+        if self.moments is not None and getattr(x, 'is_cuda', False) \
+                and not x.dtype.is_floating_point:
+            if tuple(x.shape) != self.plates:
+                raise ValueError("Incorrect shape {0} for the array, expected {1}"
+                                 .format(tuple(x.shape), self.plates))
+            self.device_value = x
+            self._value = None
+        else:
+            if self.moments is not None:
+                x = self.moments.check_fixed_value(x)
+            x = np.asarray(x)
+            if x.shape != self.value.shape:
+                raise ValueError("Incorrect shape {0} for the array, expected {1}"
+                                 .format(x.shape, self.value.shape))
+            if self.moments is not None:
+                self.indices = x
+            self.device_value = None
+            self.value = np.asarray(x, dtype=np.float64)
         seen = []
         for c, _ in self.children:
             for n in [c] + [g for g, _ in c.children]:

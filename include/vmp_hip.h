@@ -817,6 +817,17 @@ int32_t vmp_chain_pair_stats(vmp_ctx *ctx, int64_t ny, int32_t N, int32_t D, con
  *     psi(alpha) - psi(sum_c alpha), *bound = sum over rows of the node's lower-bound term
  *     sum_c (prior - alpha) elog + [lgamma(sum prior) - sum lgamma(prior)] - [the same of alpha]
  *     (dirichlet.py:107-231).  ws: at least `rows` doubles.
+ *   vmp_lda_dirichlet_step: the same rows after a step of length `scale` along the natural gradient
+ *     (expfamily.py:296-340), with the counts of a mini-batch standing for `mult` times as many
+ *     tokens: q = prior + mult * counts (counts NULL: the prior); scale == 1: alpha = q, the old
+ *     alpha is not read and may be NaN; otherwise alpha = a + scale * (q - a) from the alpha `a`
+ *     that is there.  elog and *bound as in vmp_lda_dirichlet, taken with the new alpha.  A table
+ *     stored transposed with at most 64 rows (row_stride == 1, col_stride == rows: p_word as V x K)
+ *     is walked along its memory by a kernel pair with a fixed-order combine between them; other
+ *     strides use the kernels of vmp_lda_dirichlet.  No atomics: the bits of every output depend on
+ *     the inputs and the shape only.  rows == 0: *bound = 0.  Null / negative arguments, mult <= 0
+ *     or a NaN: VMP_ERR_INVALID.
+ *   vmp_lda_dirichlet_step_workspace (host only): the doubles of `ws` that call needs.
  *   vmp_lda_dot: *out = sum a * b over m elements, added in an order that depends on m alone
  *     (ws: 1024 doubles). */
 int32_t vmp_lda_limits(int32_t *max_K, int32_t *max_chunk);
@@ -832,6 +843,12 @@ int32_t vmp_lda_token_pass(vmp_ctx *ctx, int64_t n, int64_t D, int64_t V, int32_
 int32_t vmp_lda_dirichlet(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t row_stride,
                           int64_t col_stride, const double *prior, const double *counts,
                           double *alpha, double *elog, double *ws, double *bound);
+int32_t vmp_lda_dirichlet_step_workspace(int64_t rows, int64_t cols, int64_t row_stride,
+                                         int64_t col_stride, int64_t *workspace_doubles);
+int32_t vmp_lda_dirichlet_step(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t row_stride,
+                               int64_t col_stride, const double *prior, const double *counts,
+                               double mult, double scale, double *alpha, double *elog, double *ws,
+                               double *bound);
 int32_t vmp_lda_dot(vmp_ctx *ctx, int64_t m, const double *a, const double *b, double *ws,
                     double *out);
 

@@ -18,6 +18,20 @@ parts of the token pass are timed one by one through the ``phases`` argument of
                           = 36 B, table rows (cached) not counted
   hbm_fraction            bytes_per_token * tokens / (ms_pass_doc + ms_pass_word) / peak bandwidth
   generic_ms_per_sweep    engine='generic' on the same model (--generic-max-tokens bounds its size)
+
+    python tools/bench_lda.py --svi                 # stochastic VI: the mini-batch form of the block
+
+``--svi`` times whole SVI steps (``observe`` and ``set_value`` of a new batch that lives on the
+device, ``update('topics')``, ``gradient_step`` on both Dirichlets) with ``engine='fused'`` and,
+where the generic engine can hold the batch, ``engine='generic'``; then the transposed step kernel
+of ``vmp_lda_dirichlet_step`` against ``vmp_lda_dirichlet`` on the same V x K table (scale = 1,
+mult = 1: the same work).  One JSON line per size:
+
+  ms_per_step / _min / _max / _spread   median, extremes and (max - min) / median of the timed steps
+  generic_ms_per_step ...               the same for engine='generic'
+  ms_step_kernel, ms_dirichlet          the two kernels on a V x K table; step_bytes_per_s against
+                                        hbm_fraction = bytes / s / 8 TB/s, bytes = 8 V K (prior +
+                                        counts + alpha read and written + elog) = 40 V K
 """
 import argparse
 import json
@@ -114,8 +128,126 @@ def run(n, D, V, K, warmup, steps, generic):
     return res
 
 
+def build_svi(n, S, D, V, K, docs, corpus, engine):
+    from bayespy_amd import nodes
+    from bayespy_amd.inference import VB
+    from bayespy_amd.inference.vmp.nodes.categorical import CategoricalMoments
+    p_topic = nodes.Dirichlet(np.ones(K), plates=(D,), name='p_topic')
+    p_word = nodes.Dirichlet(np.ones(V), plates=(K,), name='p_word')
+    idx = nodes.Constant(CategoricalMoments(D), docs[:S], name='document_indices')
+    topics = nodes.Categorical(nodes.Gate(idx, p_topic), plates=(S,), plates_multiplier=(n / S,),
+                               name='topics')
+    words = nodes.Categorical(nodes.Gate(topics, p_word), name='words')
+    words.observe(corpus[:S])
+    np.random.seed(1)
+    p_topic.initialize_from_random()
+    p_word.initialize_from_random()
+    Q = VB(words, topics, p_word, p_topic, idx, engine=engine)
+    Q.ignore_bound_checks = True
+    return Q
+
+
+def time_svi_steps(Q, n, S, docs_d, corpus_d, warmup, steps, device_batches):
+    """Median / min / max milliseconds of whole SVI steps on seeded batches."""
+    import torch
+    g = torch.Generator(device='cuda')
+    g.manual_seed(7)
+    Q.update(verbose=False)
+    ms = []
+    for it in range(warmup + steps):
+        subset = torch.randint(n, (S,), generator=g, device='cuda')
+        bw, bd = corpus_d[subset], docs_d[subset]
+        if not device_batches:
+            bw, bd = bw.cpu().numpy(), bd.cpu().numpy()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(torch.cuda.current_stream())
+        Q['words'].observe(bw)
+        Q['document_indices'].set_value(bd)
+        Q.update('topics', verbose=False)
+        Q.gradient_step('p_topic', 'p_word', scale=(it + 1) ** (-0.7))
+        b.record(torch.cuda.current_stream())
+        b.synchronize()
+        if it >= warmup:
+            ms.append(a.elapsed_time(b))
+    med = float(np.median(ms))
+    return dict(ms_per_step=med, ms_per_step_min=float(np.min(ms)),
+                ms_per_step_max=float(np.max(ms)),
+                ms_per_step_spread=float((np.max(ms) - np.min(ms)) / med)), float(Q.L[Q.iter - 1])
+
+
+def run_svi(n, S, D, V, K, warmup, steps, generic):
+    import torch
+    from bayespy_amd.inference.plans.lda import LDASVIPlan
+    rs = np.random.RandomState(12345)
+    docs = rs.randint(D, size=n)
+    corpus = (rs.zipf(1.2, size=n) - 1) % V
+    docs_d, corpus_d = torch.from_numpy(docs).cuda(), torch.from_numpy(corpus).cuda()
+    Q = build_svi(n, S, D, V, K, docs, corpus, 'fused')
+    assert type(Q.plans[0]) is LDASVIPlan
+    res = dict(mode='svi', tokens=n, batch=S, documents=D, vocabulary=V, topics=K)
+    t, L = time_svi_steps(Q, n, S, docs_d, corpus_d, warmup, steps, True)
+    res.update(t)
+    res['L'] = L
+    del Q
+    if generic:
+        Qg = build_svi(n, S, D, V, K, docs, corpus, 'generic')
+        t, L = time_svi_steps(Qg, n, S, docs_d, corpus_d, warmup, steps, False)
+        res.update({'generic_' + k: v for k, v in t.items()})
+        res['generic_L'] = L
+        del Qg
+    torch.cuda.empty_cache()
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def run_step_kernel(V, K, warmup, steps):
+    """The transposed step kernel against vmp_lda_dirichlet on the same V x K table."""
+    import torch
+    from bayespy_amd.device import get_runtime
+    from bayespy_amd.inference.plans.lda import LDAKernels
+    rt = get_runtime()
+    k = LDAKernels(rt)
+    g = torch.Generator(device='cuda')
+    g.manual_seed(3)
+    prior = torch.rand(V, K, generator=g, device='cuda', dtype=torch.float64) + 0.05
+    counts = torch.rand(V, K, generator=g, device='cuda', dtype=torch.float64) * 30.0
+    alpha, elog = torch.empty_like(prior), torch.empty_like(prior)
+    out = rt.zeros(1)
+    ws = rt.empty(max(k.dirichlet_step_ws(K, V, 1, K), 1024))
+
+    def timed(fn):
+        ms = []
+        for it in range(warmup + steps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            rt.sync_stream()
+            a.record(torch.cuda.current_stream())
+            fn()
+            b.record(torch.cuda.current_stream())
+            b.synchronize()
+            if it >= warmup:
+                ms.append(a.elapsed_time(b))
+        return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+    new = timed(lambda: k.dirichlet_step(K, V, 1, K, prior, counts, 1.0, 1.0, alpha, elog, ws, out))
+    a_new, b_new = alpha.clone(), float(out.item())
+    old = timed(lambda: k.dirichlet(K, V, 1, K, prior, counts, alpha, elog, ws, out))
+    same = bool(torch.equal(a_new, alpha)) and abs(b_new - float(out.item())) \
+        <= 1e-10 * abs(b_new) + 1e-9
+    nbytes = 8.0 * V * K * 5
+    res = dict(mode='step_kernel', vocabulary=V, topics=K, ms_step_kernel=new[0],
+               ms_step_kernel_min=new[1], ms_step_kernel_max=new[2], ms_dirichlet=old[0],
+               ms_dirichlet_min=old[1], ms_dirichlet_max=old[2], bytes=nbytes,
+               step_bytes_per_s=nbytes / (new[0] * 1e-3),
+               hbm_fraction=nbytes / (new[0] * 1e-3) / HBM_BYTES_PER_S, same_result=same)
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    ap.add_argument('--svi', action='store_true',
+                    help='time stochastic-VI steps (engine="fused") and the Dirichlet step kernel')
+    ap.add_argument('--batch', type=int, help='tokens per mini-batch (with --svi --tokens)')
     ap.add_argument('--tokens', type=int)
     ap.add_argument('--documents', type=int)
     ap.add_argument('--vocabulary', type=int)
@@ -126,6 +258,20 @@ def main():
     ap.add_argument('--generic-max-tokens', type=int, default=200000,
                     help='largest standard size at which the generic engine is timed too')
     a = ap.parse_args()
+    if a.svi:
+        steps = max(a.steps, 20)
+        if a.tokens:
+            run_svi(a.tokens, a.batch, a.documents, a.vocabulary, a.topics, a.warmup, steps,
+                    a.generic)
+            return
+        # the corpus of examples/lda.py with batches of 1e4 and 1e5 tokens, and a size at which the
+        # generic engine holds its tokens x V arrays (1e4 x 2e3 x 8 B = 160 MB each)
+        run_svi(200000, 10000, 2000, 2000, 16, a.warmup, steps, True)
+        run_svi(2000000, 10000, 20000, 20000, 20, a.warmup, steps, False)
+        run_svi(2000000, 100000, 20000, 20000, 20, a.warmup, steps, False)
+        for K in (16, 64):
+            run_step_kernel(100000, K, a.warmup, steps)
+        return
     if a.tokens:
         run(a.tokens, a.documents, a.vocabulary, a.topics, a.warmup, a.steps, a.generic)
         return
