@@ -228,6 +228,12 @@ SIGNATURES = {
     'vmp_lda_dirichlet_step': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_f64, c_f64,
                                        c_vp, c_vp, c_vp, c_vp]),
     'vmp_lda_dot': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    'vmp_bmm_limits': (c_i32, [P(c_i32), P(c_i32)]),
+    'vmp_bmm_plan': (c_i32, [c_i64, c_i32, c_i32, P(c_i64), P(c_i64)]),
+    'vmp_bmm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'vmp_bmm_tables': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'vmp_bmm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                             c_vp, c_vp, c_vp]),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_ensure_gram': (c_i32, [c_vp]),

@@ -9,10 +9,13 @@ from .gmm import GMMPlan
 from .lssm import LSSMPlan
 from .lssm_masked import MaskedLSSMPlan
 from .lda import LDAPlan, LDASVIPlan
+from .bmm import BernoulliMixturePlan
 
 PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
 # engine='fused': a block's opt-in form takes the place of its default form
 OPT_IN_FORMS = {LDAPlan: LDASVIPlan}
+# engine='fused': blocks that have no default form (their models run on the generic engine otherwise)
+OPT_IN_TYPES = [BernoulliMixturePlan]
 
 
 def _reusable_plans(nodes, engine, options=None):
@@ -36,7 +39,8 @@ def _reusable_plans(nodes, engine, options=None):
         return None
     if engine == 'fused' and any(isinstance(p, GenericPlan) for p in plans):
         return None
-    if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values() for p in plans):
+    if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values() or type(p) in OPT_IN_TYPES
+                                 for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
     if not all(id(n) in covered for n in nodes):
@@ -85,7 +89,8 @@ def compile_model(nodes, engine=None, **options):
         plan = GenericPlan(nodes)
         plan._engine_request = 'generic'
         return [plan]
-    types = [OPT_IN_FORMS.get(P, P) for P in PLAN_TYPES] if engine == 'fused' else PLAN_TYPES
+    types = [OPT_IN_FORMS.get(P, P) for P in PLAN_TYPES] + OPT_IN_TYPES if engine == 'fused' \
+        else PLAN_TYPES
     remaining = [n for n in nodes]
     plans = []
     progress = True

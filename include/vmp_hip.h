@@ -852,6 +852,47 @@ int32_t vmp_lda_dirichlet_step(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t
 int32_t vmp_lda_dot(vmp_ctx *ctx, int64_t m, const double *a, const double *b, double *ws,
                     double *out);
 
+/* Bernoulli mixture: the plate pass of the fused block (doc/source/examples/bmm.rst; details:
+ * bayespy_amd/csrc/vmp_bmm.hip, vmp_bmm_dev.h).  N rows of D binary observations, K clusters; x is
+ * kept as bits, no (N, D, K) or (N, K) array exists.
+ *   vmp_bmm_limits (host only): *max_K = 64, *max_D = 1024.
+ *   vmp_bmm_plan (host only): for (N, D, K) the rows of a chunk *chunk_rows (one workgroup, a
+ *     function of (N, D, K) alone) and the scratch *workspace_doubles of the pass (below 2^25 + a
+ *     few thousand doubles at every size).
+ *   vmp_bmm_pack: x (N x D, row-major; dtype 0 = float64, 1 = int64, 2 = bool / uint8) to
+ *     ceil(D / 64) 64-bit words per row, bit d of a row in bit d & 63 of word d >> 6, unused high
+ *     bits zero; *flag (device int32, cleared by the caller) is set when a value is neither 0 nor
+ *     1 -- the check of Bernoulli's observe (binomial.py: "Invalid count").
+ *   vmp_bmm_tables: from the Beta moments elog_p ((D K, 2): <log p>, <log(1 - p)>; NULL = no
+ *     observation term, the moments of Z under its prior) and elog_pi (K) the tables of the pass,
+ *     w[d, k] = <log p> - <log(1 - p)> (D x K) and c[k] = <log pi_k> + sum_d <log(1 - p_dk)> --
+ *     what mixture.py's (N, D, K) broadcast of x <log p> + (1 - x) <log(1 - p)> summed over D and
+ *     the message of the Categorical parent amount to for binary x.  c is written less its largest
+ *     element: r, the statistics and the entropy sum lse - sum Nk c - sum S w do not depend on a
+ *     constant in c, and a <log pi> near -1e5 (a Dirichlet prior of 1e-5) stays out of the
+ *     rounding of every logit; lse is relative to that constant.
+ *   vmp_bmm_pass: for every row logit = c + x w, lse = max + log sum exp(logit - max), r =
+ *     exp(logit - lse) (categorical.py: the update of Z), both products on the fp64 matrix cores.
+ *     Out: S (D x K) = sum_n r_nk x_nd and Nk (K) = sum_n r_nk; counts ((D K, 2)) = (S, Nk - S),
+ *     the message of the mixture to the Beta parent (mixture.py, bernoulli.py / binomial.py);
+ *     scal[0] = sum lse, scal[1] = sum Nk c, scal[2] = sum S w; with r_out (N x K, the caller's
+ *     row order) also r itself.  `labels` (N int32) non-NULL: r is the one-hot array of these
+ *     classes instead and lse = 0.  ws: vmp_bmm_plan's doubles.  No atomics: the bits of every
+ *     output depend on the inputs and (N, D, K) only, with or without r_out.  N = 0 gives zeros.
+ *     Tables that are not finite (a point mass at p = 0 or 1) are outside the contract: the
+ *     reference forms 0 * -inf = NaN there as well.  K or D above the limits:
+ *     VMP_ERR_UNSUPPORTED; null / negative arguments: VMP_ERR_INVALID. */
+int32_t vmp_bmm_limits(int32_t *max_K, int32_t *max_D);
+int32_t vmp_bmm_plan(int64_t N, int32_t D, int32_t K, int64_t *chunk_rows,
+                     int64_t *workspace_doubles);
+int32_t vmp_bmm_pack(vmp_ctx *ctx, int64_t N, int32_t D, int32_t dtype, const void *x,
+                     uint64_t *xw, int32_t *flag);
+int32_t vmp_bmm_tables(vmp_ctx *ctx, int32_t D, int32_t K, const double *elog_p,
+                       const double *elog_pi, double *w, double *c);
+int32_t vmp_bmm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, const uint64_t *xw,
+                     const int32_t *labels, const double *w, const double *c, double *ws,
+                     double *S, double *Nk, double *counts, double *scal, double *r_out);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
