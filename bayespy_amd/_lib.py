@@ -236,6 +236,8 @@ SIGNATURES = {
                              c_vp, c_vp, c_vp]),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
+    'vmp_pca_hold_passes': (c_i32, [c_vp, c_i32]),
+    'vmp_pca_pass_counts': (c_i32, [c_vp, P(c_i64), P(c_i64)]),
     'vmp_pca_ensure_gram': (c_i32, [c_vp]),
     'vmp_pca_small_ops': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_f64, c_f64, c_f64, c_f64, c_f64,
                                   c_i32, P(c_i32), c_vp]),

@@ -13,6 +13,18 @@
 
 constexpr int VMP_NME = 16;     // side-stream events of a context (vmp_mpca / vmp_lssm pipelines)
 
+// one Gram-form latent pass X <- A Y as run_xpass (vmp_pca.hip) issues it
+struct vmp_xpass_desc {
+    const double *Y;
+    int64_t ldy, N;
+    int D, K;
+    double *X;
+    int64_t ldx;
+    int lay;
+    const double *A;           // the state's A, or the plate stream's private copy `buf` of it
+    int buf;
+};
+
 struct vmp_ctx {
     int device;
     hipStream_t stream;
@@ -32,6 +44,12 @@ struct vmp_ctx {
     int x_buf_pending[2];
     int64_t x_count;
     int xs_cus;                // compute units the plate stream may use
+    // vmp_pca_hold_passes: while x_hold is set a Gram-form latent pass is not launched but kept
+    // in x_desc (x_held) until something can read its X (vmp_pca_launch_held) -- or until the
+    // next pass, which overwrites every element it would have written, takes its place
+    int x_hold, x_held;
+    vmp_xpass_desc x_desc;
+    int64_t x_launched, x_superseded;
     // streams / events of the pipelined plate pass of the missing-data PCA block (vmp_mpca.hip)
     hipStream_t ms[3];
     hipEvent_t me[VMP_NME];
@@ -54,6 +72,9 @@ struct vmp_ctx {
 
 // forms the pending S = [G A^T; A G A^T] of the Gram-form PCA block, if any (vmp_pca.hip)
 int32_t vmp_pca_ensure_gram(vmp_ctx *ctx);
+// launches the held latent pass of the Gram-form PCA block, if any, on the plate stream
+// (vmp_pca.hip); every entry point after which X may be read or released calls it
+int32_t vmp_pca_launch_held(vmp_ctx *ctx);
 
 // every entry point that puts work on ctx->stream behind the caller's back of the queue calls this
 // first: queued small operations run before anything that may read what they write

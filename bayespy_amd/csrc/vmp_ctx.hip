@@ -93,6 +93,8 @@ int32_t vmp_ctx_create(int32_t device, void *stream, vmp_ctx **out)
     ctx->x_count = 0;
     ctx->ev_xbuf[0] = ctx->ev_xbuf[1] = nullptr;
     ctx->xs_cus = 0;
+    ctx->x_hold = ctx->x_held = 0;
+    ctx->x_launched = ctx->x_superseded = 0;
     for (int i = 0; i < 3; ++i) ctx->ms[i] = nullptr;
     for (int i = 0; i < VMP_NME; ++i) ctx->me[i] = nullptr;
     ctx->comm = nullptr;
@@ -112,6 +114,7 @@ int32_t vmp_ctx_destroy(vmp_ctx *ctx)
     if (!ctx) return VMP_OK;
     (void)destroy_small_queue(ctx);
     (void)vmp_comm_destroy(ctx);
+    (void)vmp_pca_launch_held(ctx);     // its X is the caller's, who may read it after this call
     for (int i = 0; i < 3 * VMP_EV_RING; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->xs) {
@@ -148,6 +151,8 @@ int32_t vmp_ctx_sync(vmp_ctx *ctx)
     {
         const int32_t rcg = vmp_pca_ensure_gram(ctx);
         if (rcg != VMP_OK) return rcg;
+        const int32_t rch = vmp_pca_launch_held(ctx);
+        if (rch != VMP_OK) return rch;
     }
     VMP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->xs) VMP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->xs));
@@ -248,6 +253,10 @@ int32_t vmp_pass_times_ms(vmp_ctx *ctx, double *ms_pass, double *ms_reduce, int3
     VMP_REQUIRE(ctx, ctx && count && cap >= 0, VMP_ERR_INVALID, "null argument");
     VMP_REQUIRE(ctx, ctx->timing && ctx->ev[0], VMP_ERR_INVALID,
                 "timing not enabled (vmp_ctx_set_timing)");
+    {
+        const int32_t rch = vmp_pca_launch_held(ctx);       // a held pass has no events yet
+        if (rch != VMP_OK) return rch;
+    }
     int64_t n = ctx->ev_n < VMP_EV_RING ? ctx->ev_n : VMP_EV_RING;
     if (n > cap) n = cap;
     for (int64_t i = 0; i < n; ++i) {

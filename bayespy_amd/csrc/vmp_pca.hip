@@ -744,9 +744,12 @@ double *plate_stream_A(vmp_ctx *ctx, const vmp_pca_layout &L, void *workspace)
     return reinterpret_cast<double *>(workspace) + plate_stream_A_offset(ctx, L);
 }
 
-// anything on the main stream that touches X must follow the outstanding latent pass
+// anything on the main stream that touches X must follow the outstanding latent pass -- a held
+// one (vmp_pca_hold_passes) is launched first
 int32_t join_plate_stream(vmp_ctx *ctx)
 {
+    const int32_t rc = vmp_pca_launch_held(ctx);
+    if (rc != VMP_OK) return rc;
     if (ctx->x_pending) {
         VMP_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_xdone, 0));
         ctx->x_pending = 0;
@@ -809,10 +812,14 @@ pca_tile_kernel(double *__restrict__ R, int64_t ld, int64_t N, int rows, int RP,
 }
 
 // lay: 0 = row-major Y and X; 1 = tile-major Y, row-major X with KP rows; 3 = both tile-major
-int32_t run_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N, int D, int K, double *X,
-                  int64_t ldx, double *state, void *workspace, int lay)
+// The kernels of one latent pass, on the plate stream (from the private copy d.buf of A) or, with
+// VMP_PCA_PLATE_STREAM=0, in order on the caller's stream.
+int32_t launch_xpass(vmp_ctx *ctx, const vmp_xpass_desc &d, bool on_plate)
 {
-    int32_t rc;
+    const double *Y = d.Y, *A = d.A;
+    double *X = d.X;
+    const int64_t ldy = d.ldy, N = d.N, ldx = d.ldx;
+    const int D = d.D, K = d.K, lay = d.lay;
     vmp_pca_layout L;
     fill_layout(D, K, &L);
     const int DB = (int)(L.DP / 32), KT = (int)(L.KP / 16);
@@ -826,39 +833,8 @@ int32_t run_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N, int D, 
     const int occ = xpass_occupancy();
     const int ntm = vmp_tune_get("xpass_nt", env_int("VMP_PCA_XPASS_NT", 3, 0, 3));
     const int mf4 = vmp_tune_get("xpass_mfma4", env_int("VMP_PCA_XPASS_MFMA4", 0, 0, 1));
-    hipStream_t m = ctx->stream;
-    // VMP_PCA_PLATE_STREAM=0: everything in order on the caller's stream (A/B measurements)
-    const int overlap = vmp_tune_get("plate_stream", env_int("VMP_PCA_PLATE_STREAM", 1, 0, 1));
-    hipStream_t s = m;
-    const double *A = state + L.off_A;
-    int64_t gmax = (int64_t)ctx->num_cu * xpass_wgs_per_cu();
-    if (overlap) {
-        rc = ensure_plate_stream(ctx);
-        if (rc != VMP_OK) return rc;
-        gmax = (int64_t)ctx->xs_cus * xpass_wgs_per_cu();
-        // Nothing in a Gram-form iteration reads X: the latent pass is a pure by-product of
-        // (A, Y).  It runs on the plate stream from a private copy of A, so the
-        // replicated-node kernels of the NEXT iteration (main stream, reserved CUs) overlap
-        // it; the only ordering kept is pass(i) before pass(i+1) and before anything that
-        // touches X.
-        // TWO private copies, used in turn: the copy for pass i+1 is made while pass i still
-        // reads the other one, so the main stream never waits for the pass in flight (only for
-        // the one before it) and consecutive passes run back to back
-        const int b = (int)(ctx->x_count & 1);
-        ctx->x_count += 1;
-        double *Ax = plate_stream_A(ctx, L, workspace) + (int64_t)b * L.KP * L.DP;
-        if (ctx->x_buf_pending[b]) {
-            VMP_HIP_CHECK(ctx, hipStreamWaitEvent(m, ctx->ev_xbuf[b], 0));
-            ctx->x_buf_pending[b] = 0;
-        }
-        VMP_HIP_CHECK(ctx, hipMemcpyAsync(Ax, state + L.off_A,
-                                          (size_t)(L.KP * L.DP) * sizeof(double),
-                                          hipMemcpyDeviceToDevice, m));
-        VMP_HIP_CHECK(ctx, hipEventRecord(ctx->ev_xfork, m));
-        VMP_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->xs, ctx->ev_xfork, 0));
-        s = ctx->xs;
-        A = Ax;
-    }
+    hipStream_t s = on_plate ? ctx->xs : ctx->stream;
+    const int64_t gmax = (int64_t)(on_plate ? ctx->xs_cus : ctx->num_cu) * xpass_wgs_per_cu();
     hipEvent_t *ev = ctx->timing ? vmp_next_events(ctx) : nullptr;
     if (ev) VMP_HIP_CHECK(ctx, hipEventRecord(ev[0], s));
     for (int pass = 0; pass < 2; ++pass) {
@@ -918,12 +894,97 @@ int32_t run_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N, int D, 
         VMP_HIP_CHECK(ctx, hipEventRecord(ev[1], s));
         VMP_HIP_CHECK(ctx, hipEventRecord(ev[2], s));
     }
-    if (overlap) {
+    if (on_plate) {
         VMP_HIP_CHECK(ctx, hipEventRecord(ctx->ev_xdone, s));
         ctx->x_pending = 1;
-        const int b = (int)((ctx->x_count - 1) & 1);
-        VMP_HIP_CHECK(ctx, hipEventRecord(ctx->ev_xbuf[b], s));
-        ctx->x_buf_pending[b] = 1;
+        VMP_HIP_CHECK(ctx, hipEventRecord(ctx->ev_xbuf[d.buf], s));
+        ctx->x_buf_pending[d.buf] = 1;
+    }
+    ctx->x_launched += 1;
+    return VMP_OK;
+}
+
+// Columns of X that pass d writes (rows: KP with a tile-major Y, else K -- fixed by D, K, lay).
+// Whole tiles with a tile-major Y or the predication-free instance on padded arrays, else
+// (GUARD / ragged last tile) exactly the columns < N.
+int64_t xpass_written_cols(const vmp_xpass_desc &d)
+{
+    vmp_pca_layout L;
+    fill_layout(d.D, d.K, &L);
+    const int64_t whole = (d.N + TN - 1) / TN * TN;
+    const bool exact = (d.D == L.DP && d.K == L.KP);
+    return (d.lay || (exact && d.ldy >= whole && d.ldx >= whole)) ? whole : d.N;
+}
+
+// A held pass that `d` takes the place of would have been overwritten completely before anybody
+// could read it: same array, same shape and layout (so the same rows, the same element
+// addresses), and at least the columns the old pass would have written -- every instance, GUARD
+// included, writes all of X[:K, :N]; only the pad columns [N, 32 ceil(N / 32)) depend on ldy.
+bool xpass_supersedes(const vmp_xpass_desc &d, const vmp_xpass_desc &old)
+{
+    return d.X == old.X && d.N == old.N && d.D == old.D && d.K == old.K && d.ldx == old.ldx &&
+           d.lay == old.lay && xpass_written_cols(d) >= xpass_written_cols(old);
+}
+
+int32_t run_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N, int D, int K, double *X,
+                  int64_t ldx, double *state, void *workspace, int lay)
+{
+    int32_t rc;
+    vmp_pca_layout L;
+    fill_layout(D, K, &L);
+    hipStream_t m = ctx->stream;
+    // VMP_PCA_PLATE_STREAM=0: everything in order on the caller's stream (A/B measurements)
+    const int overlap = vmp_tune_get("plate_stream", env_int("VMP_PCA_PLATE_STREAM", 1, 0, 1));
+    vmp_xpass_desc d = {Y, ldy, N, D, K, X, ldx, lay, state + L.off_A, -1};
+    if (!overlap) {
+        rc = join_plate_stream(ctx);        // (a pass issued before the switch was turned)
+        if (rc != VMP_OK) return rc;
+    } else {
+        rc = ensure_plate_stream(ctx);
+        if (rc != VMP_OK) return rc;
+        if (ctx->x_held) {
+            if (xpass_supersedes(d, ctx->x_desc)) {
+                ctx->x_held = 0;
+                ctx->x_superseded += 1;
+            } else {
+                rc = vmp_pca_launch_held(ctx);
+                if (rc != VMP_OK) return rc;
+            }
+        }
+        // Nothing in a Gram-form iteration reads X: the latent pass is a pure by-product of
+        // (A, Y).  It runs on the plate stream from a private copy of A, so the
+        // replicated-node kernels of the NEXT iteration (main stream, reserved CUs) overlap
+        // it; the only ordering kept is pass(i) before pass(i+1) and before anything that
+        // touches X.
+        // TWO private copies, used in turn: the copy for pass i+1 is made while pass i still
+        // reads the other one, so the main stream never waits for the pass in flight (only for
+        // the one before it) and consecutive passes run back to back.
+        // (A held pass has not read its copy, and no event stands for it: x_buf_pending[b] is
+        // set by launched passes only.  Its copy is safe all the same -- the pass is launched
+        // or dropped above, before the next call, which writes the OTHER copy.)
+        const int b = (int)(ctx->x_count & 1);
+        ctx->x_count += 1;
+        double *Ax = plate_stream_A(ctx, L, workspace) + (int64_t)b * L.KP * L.DP;
+        if (ctx->x_buf_pending[b]) {
+            VMP_HIP_CHECK(ctx, hipStreamWaitEvent(m, ctx->ev_xbuf[b], 0));
+            ctx->x_buf_pending[b] = 0;
+        }
+        VMP_HIP_CHECK(ctx, hipMemcpyAsync(Ax, state + L.off_A,
+                                          (size_t)(L.KP * L.DP) * sizeof(double),
+                                          hipMemcpyDeviceToDevice, m));
+        VMP_HIP_CHECK(ctx, hipEventRecord(ctx->ev_xfork, m));
+        VMP_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->xs, ctx->ev_xfork, 0));
+        d.A = Ax;
+        d.buf = b;
+    }
+    if (overlap && ctx->x_hold) {
+        // every pass overwrites all of <x>: this one is launched only if something can read its
+        // result before the next one replaces it (vmp_pca_launch_held)
+        ctx->x_desc = d;
+        ctx->x_held = 1;
+    } else {
+        rc = launch_xpass(ctx, d, overlap != 0);
+        if (rc != VMP_OK) return rc;
     }
     // messages to W from (G, A): main stream, concurrent with the pass.  Where the LDS-resident
     // tail kernel applies they are left to it (pca_tail_fast_kernel<KP, true> forms S itself: one
@@ -945,6 +1006,13 @@ int32_t run_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N, int D, 
 }
 
 }  // namespace
+
+int32_t vmp_pca_launch_held(vmp_ctx *ctx)
+{
+    if (!ctx || !ctx->x_held) return VMP_OK;
+    ctx->x_held = 0;
+    return launch_xpass(ctx, ctx->x_desc, true);
+}
 
 int32_t vmp_pca_ensure_gram(vmp_ctx *ctx)
 {
@@ -1170,16 +1238,39 @@ int32_t vmp_pca_xjoin(vmp_ctx *ctx)
         if (rcg != VMP_OK) return rcg;
     }
     VMP_REQUIRE(ctx, ctx, VMP_ERR_INVALID, "null argument");
-    if (ctx->x_pending) {
-        VMP_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_xdone, 0));
-        ctx->x_pending = 0;
+    return join_plate_stream(ctx);
+}
+
+int32_t vmp_pca_hold_passes(vmp_ctx *ctx, int32_t on)
+{
+    VMP_REQUIRE(ctx, ctx, VMP_ERR_INVALID, "null argument");
+    if (on) {
+        // VMP_PCA_HOLD_PASSES=0: every pass is launched where it is issued (A/B measurements)
+        if (vmp_tune_get("pca_hold_passes", env_int("VMP_PCA_HOLD_PASSES", 1, 0, 1)))
+            ctx->x_hold = 1;
+        return VMP_OK;
     }
+    ctx->x_hold = 0;
+    // no join: the pass overlaps whatever the caller's stream does next
+    return vmp_pca_launch_held(ctx);
+}
+
+int32_t vmp_pca_pass_counts(vmp_ctx *ctx, int64_t *launched, int64_t *superseded)
+{
+    VMP_REQUIRE(ctx, ctx, VMP_ERR_INVALID, "null argument");
+    if (launched) *launched = ctx->x_launched;
+    if (superseded) *superseded = ctx->x_superseded;
     return VMP_OK;
 }
 
 int32_t vmp_pca_last_pass_ms(vmp_ctx *ctx, double *ms_pass, double *ms_reduce)
 {
-    VMP_REQUIRE(ctx, ctx && ctx->timing && ctx->ev[0] && ctx->ev_n > 0, VMP_ERR_INVALID,
+    VMP_REQUIRE(ctx, ctx != nullptr, VMP_ERR_INVALID, "null argument");
+    {
+        const int32_t rch = vmp_pca_launch_held(ctx);       // a held pass has no events yet
+        if (rch != VMP_OK) return rch;
+    }
+    VMP_REQUIRE(ctx, ctx->timing && ctx->ev[0] && ctx->ev_n > 0, VMP_ERR_INVALID,
                 "no timed pass (vmp_ctx_set_timing)");
     hipEvent_t *e = ctx->ev + 3 * ((ctx->ev_n - 1) % VMP_EV_RING);
     VMP_HIP_CHECK(ctx, hipEventSynchronize(e[2]));

@@ -112,6 +112,17 @@ class HIPKernels:
     def xjoin(self):
         self.rt.check(self.lib.vmp_pca_xjoin(self.ctx))
 
+    def hold_passes(self, on):
+        """vmp_pca_hold_passes: while on, a latent pass is launched only when something can read
+        its <x> before the next pass overwrites it."""
+        self.rt.check(self.lib.vmp_pca_hold_passes(self.ctx, 1 if on else 0))
+
+    def pass_counts(self):
+        """(launched, superseded) latent passes of the context (vmp_pca_pass_counts)."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        self.rt.check(self.lib.vmp_pca_pass_counts(self.ctx, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     def ensure_gram(self):
         """The Gram-form messages to W are formed lazily by the library (vmp_pca_ensure_gram):
         before the state block is read directly."""
@@ -666,6 +677,7 @@ class PCAPlan:
                         k.xpass_tiled(self.Yt, N, D, K, self.Xd, self.ldx, self.state, self.ws)
                 else:
                     k.xpass(self.Yd, self.ldy, N, D, K, self.Xd, self.ldx, self.state, self.ws)
+                self._end_hold()
             else:
                 k.pass_(self.Yd, self.ldy, N, D, K, self.Xd, self.ldx, self.state, self.ws)
                 # child -> parent message sum over the sharded plate (node.py:650, dot.py:581)
@@ -677,6 +689,32 @@ class PCAPlan:
         else:
             return
         self._version += 1
+
+    # -- latent passes whose result nobody reads -------------------------------------------------
+    # Every Gram-form pass overwrites all of <x>, and nothing in a sweep reads it: while the loop
+    # says that another sweep follows, the library holds the pass (vmp_pca_hold_passes) and the
+    # next one takes its place.  Whatever reads or releases <x> goes through finish() / xjoin,
+    # which launches a held pass first.
+    defer_passes = True         # False: every pass is launched where it is issued
+    _hold = False               # the loop's latest hint: another sweep follows this one
+    _lib_hold = False           # this plan has switched the library to holding
+
+    def hold_passes(self, more_follow):
+        """Hint from ``VB.update`` before a sweep.  Holding starts at once; it ends only AFTER
+        this sweep's pass has been issued (``_end_hold``), so that the last pass of an ``update``
+        call takes the place of the one before it and is launched where it always was, beside
+        the tau / alpha / bound kernels."""
+        self._hold = bool(more_follow) and self.defer_passes and self.stats == 'gram' \
+            and hasattr(self.kernels, 'hold_passes')
+        if self._hold and not self._lib_hold:
+            self.kernels.hold_passes(True)
+            self._lib_hold = True
+
+    def _end_hold(self):
+        """Unless another sweep follows: launch the held pass (no join) and hold no more."""
+        if self._lib_hold and not self._hold:
+            self.kernels.hold_passes(False)
+            self._lib_hold = False
 
     def place_plate_arrays(self):
         """The placement trial of :meth:`_place_plate_arrays` as an explicit set-up step (otherwise
@@ -733,6 +771,8 @@ class PCAPlan:
         x_cur = self._Xt if xt else self.Xd
 
         def timed(Yt, X):
+            if self._lib_hold:              # the trial times two LAUNCHED passes per pair
+                k.hold_passes(False)
             k.set_timing(True)
             for _ in range(2):
                 if xt:
@@ -742,6 +782,8 @@ class PCAPlan:
             k.xjoin()
             ms = min(a for a, _ in k.pass_times_ms(8))
             k.set_timing(bool(getattr(self, 'timing', False)))
+            if self._lib_hold:
+                k.hold_passes(True)
             return ms
 
         # the placement of <x> (the write stream) decides most of the spread and its candidates are
@@ -833,6 +875,7 @@ class PCAPlan:
         if self._ready:
             self._flush()
         self._pending = []
+        self._end_hold()
         if (self._Xrows is not None or self._Xt is not None) and self.stats == 'gram':
             self.kernels.xjoin()
 

@@ -163,6 +163,9 @@ class VB:
         i = 0
         try:
             while repeat is None or i < repeat:
+                # a plan may leave out plate-sized work of this sweep that the next sweep
+                # overwrites before anything reads it
+                self._hold_passes(repeat is None or i + 1 < repeat)
                 t = time.time()
                 if not self._graph_sweep(nodes):
                     for node in nodes:
@@ -178,10 +181,17 @@ class VB:
         finally:
             # plans may keep plate-sized work in flight on their own streams across
             # iterations; order the caller's stream after it before handing back control
+            self._hold_passes(False)        # (an early stop by tol: no sweep follows after all)
             for p in self.plans:
                 fin = getattr(p, 'finish', None)
                 if fin is not None:
                     fin()
+
+    def _hold_passes(self, more_follow):
+        for p in self.plans:
+            hold = getattr(p, 'hold_passes', None)
+            if hold is not None:
+                hold(more_follow)
 
     def _graph_sweep(self, nodes):
         """A sweep over ``nodes`` and the bound terms of the model as ONE recorded HIP graph, when

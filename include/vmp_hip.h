@@ -196,6 +196,22 @@ int32_t vmp_pca_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N,
 
 /* Make the context's stream wait for the outstanding vmp_pca_xpass (no host block). */
 int32_t vmp_pca_xjoin(vmp_ctx *ctx);
+/* Every Gram-form latent pass overwrites all of <x>, and nothing in an iteration reads it.  With
+ * on != 0 (default off), vmp_pca_xpass / vmp_pca_xpass_tiled on the plate stream still do their
+ * main-stream part (private copy of A, S or its pending flag) but HOLD the pass kernel: it is
+ * launched, on the plate stream and bit for bit as it would have been, by whatever may read or
+ * release its X next -- vmp_pca_xjoin and every call that joins implicitly (vmp_pca_pass,
+ * vmp_pca_stats_from_x, vmp_pca_tile_x), vmp_ctx_sync, vmp_ctx_destroy, the pass timing read-outs
+ * and vmp_pca_hold_passes(ctx, 0) (which launches without joining).  A later pass into the same X
+ * with the same N, D, K, ldx and layout, which writes at least the same elements, takes the place
+ * of a held one (the held one is dropped: superseded); a pass that targets anything else launches
+ * the held one first.  The arrays a held pass names (Y, X, the workspace) must stay allocated and
+ * unchanged until one of the calls above; X must not be read before one of them.
+ * VMP_PCA_HOLD_PASSES=0 / tune key "pca_hold_passes" = 0 turn on != 0 into a no-op; so does
+ * VMP_PCA_PLATE_STREAM=0. */
+int32_t vmp_pca_hold_passes(vmp_ctx *ctx, int32_t on);
+/* Latent passes (vmp_pca_xpass*) launched / superseded on this context since it was created. */
+int32_t vmp_pca_pass_counts(vmp_ctx *ctx, int64_t *launched, int64_t *superseded);
 /* Gram form: the messages to W of the latest latent pass, S = [G A^T ; A G A^T] in the state block
  * (dot.py:581 collapsed onto the Gram matrix), are formed lazily -- by the fused tau / alpha / bound
  * kernel when it comes next, else by this call, which every other entry point that reads S makes
