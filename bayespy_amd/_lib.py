@@ -21,6 +21,7 @@ VMP_ERR_HIP = -3
 VMP_ERR_UNSUPPORTED = -4
 VMP_ERR_FLOATING = -5
 VMP_ERR_NOT_POSITIVE = -6
+VMP_PCA_SWEEPS_NOT_BUILT = 1      # vmp_pca_sweeps: not an error, the caller runs the sweeps one by one
 
 
 class NotPositiveDefiniteError(Exception):
@@ -239,6 +240,10 @@ SIGNATURES = {
     'vmp_pca_hold_passes': (c_i32, [c_vp, c_i32]),
     'vmp_pca_pass_counts': (c_i32, [c_vp, P(c_i64), P(c_i64)]),
     'vmp_pca_ensure_gram': (c_i32, [c_vp]),
+    'vmp_pca_sweeps': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_f64, c_f64, c_f64, c_f64, c_f64, c_vp,
+                               c_i64, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_f64,
+                               c_i32, c_f64, c_i32, P(c_i32)]),
+    'vmp_pca_sweep_counts': (c_i32, [c_vp, P(c_i64), P(c_i64), P(c_i64)]),
     'vmp_pca_small_ops': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_f64, c_f64, c_f64, c_f64, c_f64,
                                   c_i32, P(c_i32), c_vp]),
     'vmp_pca_small_ops_mean': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_f64, c_f64, c_f64, c_f64, c_f64,

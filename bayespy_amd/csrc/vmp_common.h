@@ -50,6 +50,11 @@ struct vmp_ctx {
     int x_hold, x_held;
     vmp_xpass_desc x_desc;
     int64_t x_launched, x_superseded;
+    // vmp_pca_sweeps: device control block of a batch of sweeps (allocated on first use) -- the
+    // stop word, the bound the next sweep compares with, and the executed / skipped counters the
+    // tail kernel keeps -- and the sweeps enqueued so far
+    double *sweep_ctl;
+    int64_t sweeps_enqueued;
     // streams / events of the pipelined plate pass of the missing-data PCA block (vmp_mpca.hip)
     hipStream_t ms[3];
     hipEvent_t me[VMP_NME];
@@ -69,6 +74,34 @@ struct vmp_ctx {
     void *queue;
     char err[512];
 };
+
+// control block of vmp_pca_sweeps (vmp_ctx::sweep_ctl), in doubles
+enum { VMP_SWEEP_STOP = 0, VMP_SWEEP_L = 1, VMP_SWEEP_EXECUTED = 2, VMP_SWEEP_SKIPPED = 3,
+       VMP_SWEEP_CTL_LEN = 8 };
+
+// what the tail kernel of a batched sweep needs beyond the node updates (vmp_pca_small.hip)
+struct vmp_sweep_tail {
+    const double *P;        // the DP / 8 partial sums of sum <x><x>^T (pca_gram_stats_kernel)
+    int nb;
+    double *ctl;            // vmp_ctx::sweep_ctl
+    double *slot;           // ring slot of this sweep
+    int first;              // first sweep of the batch: the stop word is not read, L0 is l0
+    int compare;            // bounds are compared (the host's ignore_bound_checks / annealing / iter > 0)
+    double l0, tol;
+    int norder;
+    int order[8];
+};
+
+// the LDS-resident kernels of one batched sweep (vmp_pca_small.hip): VMP_OK, or VMP_PCA_SWEEPS_NOT_BUILT
+// for shapes they do not cover.  `stop` (null: not read) is the stop word every kernel of a later
+// sweep of the batch reads first.
+int32_t vmp_pca_sweep_covered(int32_t D, int32_t K);
+int32_t vmp_pca_launch_sweep_head(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                                  double a0t, double b0t, double a0a, double b0a, double *state,
+                                  const double *stop);
+int32_t vmp_pca_launch_sweep_tail(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                                  double a0t, double b0t, double a0a, double b0a, double *state,
+                                  const vmp_sweep_tail &t);
 
 // forms the pending S = [G A^T; A G A^T] of the Gram-form PCA block, if any (vmp_pca.hip)
 int32_t vmp_pca_ensure_gram(vmp_ctx *ctx);

@@ -28,6 +28,7 @@
 //   role 2:  S     += Z_tile * X_tile^T     (contraction over n)
 // with the S accumulators resident in registers for the whole kernel.
 #include "vmp_common.h"
+#include "vmp_stop_rule.h"
 
 namespace {
 
@@ -531,9 +532,11 @@ pca_init_state_kernel(vmp_pca_layout L, int K, double a0t, double b0t, double a0
 constexpr int GR = 8;
 __global__ void __launch_bounds__(NT)
 pca_gram_stats_kernel(vmp_pca_layout L, int D, int K, const double *__restrict__ st_in,
-                      double *__restrict__ st, double *__restrict__ P)
+                      double *__restrict__ st, double *__restrict__ P, const double *stop)
 {
     extern __shared__ double lds[];
+    // batched sweeps (vmp_pca_sweeps): an earlier sweep of the batch has stopped the loop
+    if (stop && stop[VMP_SWEEP_STOP] != 0.0) return;
     const int DP = (int)L.DP, KP = (int)L.KP;
     const int LA = DP + 1;
     double *As = lds;                    // KP x LA
@@ -757,8 +760,10 @@ int32_t join_plate_stream(vmp_ctx *ctx)
     return VMP_OK;
 }
 
+// vmp_pca_sweeps: `stop` is the stop word of the batch (null: not read), and with reduce = false
+// the partial sums are left in P for the sweep's tail kernel, which adds them itself
 int32_t run_gram_stats(vmp_ctx *ctx, const vmp_pca_layout &L, int D, int K, double *state,
-                       double *P, hipStream_t s)
+                       double *P, hipStream_t s, const double *stop = nullptr, bool reduce = true)
 {
     const int nb = (int)(L.DP / GR);
     const size_t lds = ((size_t)L.KP * (L.DP + 1) + (size_t)GR * L.DP + (size_t)GR * LD)
@@ -771,8 +776,9 @@ int32_t run_gram_stats(vmp_ctx *ctx, const vmp_pca_layout &L, int D, int K, doub
         attr_set = true;
     }
     hipLaunchKernelGGL(pca_gram_stats_kernel, dim3(nb), dim3(NT), lds, s, L, D, K, state, state,
-                       P);
+                       P, stop);
     VMP_HIP_CHECK(ctx, hipGetLastError());
+    if (!reduce) return VMP_OK;
     const int len = (int)(L.KP * L.KP);
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((len + NT - 1) / NT), dim3(NT), 0, s, P, nb,
                        len, state + L.off_S + L.DP * L.KP);
@@ -926,8 +932,10 @@ bool xpass_supersedes(const vmp_xpass_desc &d, const vmp_xpass_desc &old)
            d.lay == old.lay && xpass_written_cols(d) >= xpass_written_cols(old);
 }
 
-int32_t run_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N, int D, int K, double *X,
-                  int64_t ldx, double *state, void *workspace, int lay)
+// The latent pass X <- A Y with the A the state holds at this point of the caller's stream:
+// launched, or held (vmp_pca_hold_passes), on the plate stream from a private copy of A.
+int32_t issue_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N, int D, int K, double *X,
+                    int64_t ldx, double *state, void *workspace, int lay)
 {
     int32_t rc;
     vmp_pca_layout L;
@@ -986,6 +994,17 @@ int32_t run_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N, int D, 
         rc = launch_xpass(ctx, d, overlap != 0);
         if (rc != VMP_OK) return rc;
     }
+    return VMP_OK;
+}
+
+int32_t run_xpass(vmp_ctx *ctx, const double *Y, int64_t ldy, int64_t N, int D, int K, double *X,
+                  int64_t ldx, double *state, void *workspace, int lay)
+{
+    int32_t rc = issue_xpass(ctx, Y, ldy, N, D, K, X, ldx, state, workspace, lay);
+    if (rc != VMP_OK) return rc;
+    vmp_pca_layout L;
+    fill_layout(D, K, &L);
+    hipStream_t m = ctx->stream;
     // messages to W from (G, A): main stream, concurrent with the pass.  Where the LDS-resident
     // tail kernel applies they are left to it (pca_tail_fast_kernel<KP, true> forms S itself: one
     // launch instead of three beside the pass); anything else that reads S first
@@ -1260,6 +1279,100 @@ int32_t vmp_pca_pass_counts(vmp_ctx *ctx, int64_t *launched, int64_t *superseded
     VMP_REQUIRE(ctx, ctx, VMP_ERR_INVALID, "null argument");
     if (launched) *launched = ctx->x_launched;
     if (superseded) *superseded = ctx->x_superseded;
+    return VMP_OK;
+}
+
+int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                       double a0_tau, double b0_tau, double a0_alpha, double b0_alpha,
+                       const double *Y, int64_t ldy, int64_t N, double *X, int64_t ldx, int32_t lay,
+                       double *state, void *workspace, int32_t n, double *ring, double tol,
+                       int32_t compare, double l0, int32_t norder, const int32_t *order)
+{
+    VMP_REQUIRE(ctx, ctx != nullptr, VMP_ERR_INVALID, "null context");
+    if (!vmp_tune_get("pca_sweeps", env_int("VMP_PCA_SWEEPS", 1, 0, 1)))
+        return VMP_PCA_SWEEPS_NOT_BUILT;
+    if (vmp_pca_sweep_covered(D, K) != VMP_OK) return VMP_PCA_SWEEPS_NOT_BUILT;
+    VMP_REQUIRE(ctx, ring && order, VMP_ERR_INVALID, "null pointer argument");
+    VMP_REQUIRE(ctx, n >= 1 && n <= VMP_PCA_MAX_SWEEPS, VMP_ERR_INVALID,
+                "between 1 and %d sweeps per call", VMP_PCA_MAX_SWEEPS);
+    VMP_REQUIRE(ctx, norder >= 1 && norder <= VMP_BOUND_MAX_ORDER, VMP_ERR_INVALID,
+                "between 1 and %d bound terms", VMP_BOUND_MAX_ORDER);
+    for (int i = 0; i < norder; ++i)
+        VMP_REQUIRE(ctx, order[i] >= -1 && order[i] < VMP_BOUND_TERMS, VMP_ERR_INVALID,
+                    "bound term %d out of range", order[i]);
+    VMP_REQUIRE(ctx, lay == 0 || lay == 1 || lay == 3, VMP_ERR_INVALID, "unknown layout %d", lay);
+    VMP_REQUIRE(ctx, x_prec > 0 && a0_tau > 0 && b0_tau > 0 && a0_alpha > 0 && b0_alpha > 0,
+                VMP_ERR_INVALID, "x_prec and the Gamma prior parameters must be positive");
+    int32_t rc;
+    if (lay == 0) {
+        rc = check_pass_args(ctx, Y, X, state, workspace, ldy, ldx, N, D, K);
+        if (rc != VMP_OK) return rc;
+    } else {
+        VMP_REQUIRE(ctx, Y && X && state && workspace && N >= 0, VMP_ERR_INVALID,
+                    "null pointer argument");
+        VMP_REQUIRE(ctx, ((uintptr_t)Y % 16) == 0 && ((uintptr_t)X % 16) == 0, VMP_ERR_INVALID,
+                    "tile-major arrays must be 16-byte aligned");
+        if (lay == 1)
+            VMP_REQUIRE(ctx, (ldx % 2) == 0 && ldx >= (N + TN - 1) / TN * TN && ldx < (int64_t)170000000,
+                        VMP_ERR_INVALID, "row-major X beside a tile-major Y needs KP rows of an even "
+                        "leading dimension >= 32 ceil(N/32) (ldx=%lld)", (long long)ldx);
+    }
+    rc = vmp_pca_ensure_gram(ctx);      // (a pass issued outside this entry may have left S pending)
+    if (rc != VMP_OK) return rc;
+    if (!ctx->sweep_ctl) {
+        VMP_HIP_CHECK(ctx, hipMalloc(&ctx->sweep_ctl, VMP_SWEEP_CTL_LEN * sizeof(double)));
+        VMP_HIP_CHECK(ctx, hipMemsetAsync(ctx->sweep_ctl, 0, VMP_SWEEP_CTL_LEN * sizeof(double),
+                                          ctx->stream));
+    }
+    vmp_pca_layout L;
+    fill_layout(D, K, &L);
+    double *P = reinterpret_cast<double *>(workspace);
+    vmp_sweep_tail t;
+    t.P = P;
+    t.nb = (int)(L.DP / GR);
+    t.ctl = ctx->sweep_ctl;
+    t.compare = compare ? 1 : 0;
+    t.l0 = l0;
+    t.tol = tol;
+    t.norder = norder;
+    for (int i = 0; i < 8; ++i) t.order[i] = i < norder ? order[i] : -1;
+    for (int i = 0; i < n; ++i) {
+        // the first sweep of the batch reads no stop word: whatever an earlier batch left is stale
+        const double *stop = i == 0 ? nullptr : ctx->sweep_ctl;
+        rc = vmp_pca_launch_sweep_head(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
+                                       b0_alpha, state, stop);
+        if (rc != VMP_OK) return rc;
+        if (i + 1 == n) {
+            // the one pass of the batch that anything can read: from the A of the last EXECUTED
+            // sweep (after a stop the head kernels have left the state alone)
+            rc = issue_xpass(ctx, Y, ldy, N, D, K, X, ldx, state, workspace, lay);
+            if (rc != VMP_OK) return rc;
+        } else {
+            ctx->x_superseded += 1;      // never described, copied for or forked
+        }
+        rc = run_gram_stats(ctx, L, D, K, state, P, ctx->stream, stop, false);
+        if (rc != VMP_OK) return rc;
+        t.slot = ring + (int64_t)i * VMP_PCA_SWEEP_SLOT;
+        t.first = i == 0;
+        rc = vmp_pca_launch_sweep_tail(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha, b0_alpha,
+                                       state, t);
+        if (rc != VMP_OK) return rc;
+        ctx->sweeps_enqueued += 1;
+    }
+    return VMP_OK;
+}
+
+int32_t vmp_pca_sweep_counts(vmp_ctx *ctx, int64_t *enqueued, int64_t *executed, int64_t *skipped)
+{
+    VMP_REQUIRE(ctx, ctx, VMP_ERR_INVALID, "null argument");
+    double c[VMP_SWEEP_CTL_LEN] = {0.0};
+    if (ctx->sweep_ctl) {
+        VMP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        VMP_HIP_CHECK(ctx, hipMemcpy(c, ctx->sweep_ctl, sizeof(c), hipMemcpyDeviceToHost));
+    }
+    if (enqueued) *enqueued = ctx->sweeps_enqueued;
+    if (executed) *executed = (int64_t)c[VMP_SWEEP_EXECUTED];
+    if (skipped) *skipped = (int64_t)c[VMP_SWEEP_SKIPPED];
     return VMP_OK;
 }
 

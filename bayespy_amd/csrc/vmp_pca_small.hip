@@ -14,6 +14,7 @@
 // expfamily.py:400-480 (lower bound), utils/linalg.py:31-223 (chol, chol_inv, chol_logdet).
 #include "vmp_common.h"
 #include "vmp_sweep.h"
+#include "vmp_stop_rule.h"
 
 #include <stdlib.h>
 
@@ -522,8 +523,10 @@ __device__ __forceinline__ v4f64 wave_tile_mma_acc(v4f64 acc, const double *As, 
 // 25.6 KB, 96 VGPRs, no AGPRs, no scratch.
 template <int KP>
 __global__ void __launch_bounds__(NTF, 4)
-pca_head_fast_kernel(small_args a, double *st)
+pca_head_fast_kernel(small_args a, double *st, const double *stop)
 {
+    // batched sweeps (vmp_pca_sweeps): an earlier sweep of the batch has stopped the loop
+    if (stop && stop[VMP_SWEEP_STOP] != 0.0) return;
     constexpr int LDM = KP + 1, E = KP * KP / NTF, RB = 32;
     constexpr int KT = KP / 16;
     constexpr int NB = FAST_D / RB;               // row blocks
@@ -742,11 +745,17 @@ pca_head_fast_kernel(small_args a, double *st)
 // LDS in batches of GB rows, A resident -- instead of by pca_gram_stats_kernel + reduce_partials_kernel
 // in front of this kernel: one launch of the replicated-node chain instead of three beside the plate
 // pass (BASELINE config 2: the chain, not the pass, set the iteration time).
+// SWEEP (vmp_pca_sweeps): one sweep of a batch that runs without the host.  The kernel first reads the
+// stop word an earlier sweep may have set and returns at once if it is set; it adds the DP / 8
+// partial sums of sum <x><x>^T itself, in the fixed order of reduce_partials_kernel (no launch of
+// that kernel); and after the bound it writes the sweep's ring slot, evaluates the loop's stop
+// rule (vmp_stop_rule.h) and leaves the stop word and the bound for the next sweep.
 constexpr int GB = 32;            // rows of G per batch
-template <int KP, bool GRAM>
-__global__ void __launch_bounds__(NTF)
-pca_tail_fast_kernel(small_args a, double *st)
+constexpr int TAIL_PLAIN = 0, TAIL_GRAM = 1, TAIL_SWEEP = 2;
+template <int KP, int MODE>
+__device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, const vmp_sweep_tail *sw)
 {
+    constexpr bool GRAM = (MODE == TAIL_GRAM);
     constexpr int LDM = KP + 1, E = KP * KP / NTF;
     extern __shared__ double gl[];          // GRAM: A (KP x (DP+1)) | G batch (GB x (DP+1)) | S batch (GB x LDM)
     __shared__ double Sw[KP * LDM];         // Sww
@@ -757,11 +766,40 @@ pca_tail_fast_kernel(small_args a, double *st)
     __shared__ double red[NTF / 64 + 1];
     const lay32 L(a.L);
     const int tid = threadIdx.x, D = a.D, K = a.K;
+    if constexpr (MODE == TAIL_SWEEP) {
+        if (!sw->first && sw->ctl[VMP_SWEEP_STOP] != 0.0) {
+            if (tid == 0) {
+                sw->slot[7] = 0.0;                     // not executed
+                sw->ctl[VMP_SWEEP_SKIPPED] += 1.0;
+            }
+            return;
+        }
+    }
     __builtin_amdgcn_s_setprio(3);   // latency-critical: win issue arbitration on a shared CU
     double t1 = 0.0;
     double sxx[E];
 #pragma unroll
     for (int m = 0; m < E; ++m) sxx[m] = 0.0;
+    if constexpr (MODE == TAIL_SWEEP) {
+        // sum <x><x>^T = sum_b P[b] in the order of reduce_partials_kernel (vmp_pca.hip): the same bits
+        const int nb = sw->nb;
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            const int e = tid + m * NTF;
+            const double *p = sw->P + e;
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+            int b = 0;
+            for (; b + 3 < nb; b += 4) {
+                s0 += p[b * (KP * KP)];
+                s1 += p[(b + 1) * (KP * KP)];
+                s2 += p[(b + 2) * (KP * KP)];
+                s3 += p[(b + 3) * (KP * KP)];
+            }
+            for (; b < nb; ++b) s0 += p[b * (KP * KP)];
+            sxx[m] = (s0 + s1) + (s2 + s3);
+            st[L.off_S + L.DP * KP + e] = sxx[m];
+        }
+    }
     if constexpr (GRAM) {
         const int DP = L.DP, LA = DP + 1;
         double *As = gl, *Gs = As + KP * LA, *Ss = Gs + GB * LA;
@@ -823,7 +861,7 @@ pca_tail_fast_kernel(small_args a, double *st)
             const bool in = (i < K && j < K);
             v0[m] = in ? st[L.off_Sww + i * KP + j] : 0.0;
             v1[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
-            if constexpr (GRAM) v2[m] = in ? sxx[m] : 0.0;
+            if constexpr (MODE != TAIL_PLAIN) v2[m] = in ? sxx[m] : 0.0;
             else v2[m] = in ? st[L.off_S + (L.DP + i) * KP + j] : 0.0;
         }
         if (tid == 0) {
@@ -885,6 +923,9 @@ pca_tail_fast_kernel(small_args a, double *st)
         st[L.off_tau + 3] = sc[3];
         st[L.off_scal + 2] = resid;
         if (!(tb > 0.0)) st[L.off_scal + 3] = (double)VMP_ERR_FLOATING;
+        // the status word as the host would read it after this kernel
+        if constexpr (MODE == TAIL_SWEEP)
+            sc[7] = !(tb > 0.0) ? (double)VMP_ERR_FLOATING : st[L.off_scal + 3];
     }
     if (tid < K) {
         const double aa = a.a0a + 0.5 * (double)D;
@@ -934,7 +975,66 @@ pca_tail_fast_kernel(small_args a, double *st)
         st[L.off_L + 3] = Lt;
         st[L.off_L + 4] = lal;
         st[L.off_L + 5] = LY + LX + LW + Lt + lal;
+        if constexpr (MODE == TAIL_SWEEP) {
+            const double status = sc[7];
+            double *slot = sw->slot;
+            slot[0] = LY;
+            slot[1] = LX;
+            slot[2] = LW;
+            slot[3] = Lt;
+            slot[4] = lal;
+            slot[5] = LY + LX + LW + Lt + lal;
+            slot[6] = status;
+            slot[7] = 1.0;                             // executed
+            // the terms go through LDS: indexed by the order the host adds them in
+            al[0] = LY;
+            al[1] = LX;
+            al[2] = LW;
+            al[3] = Lt;
+            al[4] = lal;
+            const double Lb = vmp_bound_sum(al, sw->order, sw->norder);
+            const double L0 = sw->first ? sw->l0 : sw->ctl[VMP_SWEEP_L];
+            int stop = status != 0.0;
+            if (sw->compare && vmp_stop_rule(Lb, L0, sw->tol)) stop = 1;
+            sw->ctl[VMP_SWEEP_STOP] = stop ? 1.0 : 0.0;
+            sw->ctl[VMP_SWEEP_L] = Lb;
+            sw->ctl[VMP_SWEEP_EXECUTED] += 1.0;
+        }
     }
+}
+
+template <int KP, bool GRAM>
+__global__ void __launch_bounds__(NTF)
+pca_tail_fast_kernel(small_args a, double *st)
+{
+    pca_tail_body<KP, GRAM ? TAIL_GRAM : TAIL_PLAIN>(a, st, nullptr);
+}
+
+template <int KP>
+__global__ void __launch_bounds__(NTF)
+pca_tail_sweep_kernel(small_args a, double *st, vmp_sweep_tail sw)
+{
+    pca_tail_body<KP, TAIL_SWEEP>(a, st, &sw);
+}
+
+bool fast_small_enabled()
+{
+    static const int v = getenv("VMP_PCA_FAST_SMALL") ? atoi(getenv("VMP_PCA_FAST_SMALL")) : 1;
+    return v != 0;
+}
+
+int32_t fill_small_args(vmp_ctx *ctx, small_args &a, int32_t D, int32_t K, int64_t n_total,
+                        double x_prec, double a0t, double b0t, double a0a, double b0a)
+{
+    const int32_t rc = vmp_pca_get_layout(D, K, &a.L);
+    VMP_REQUIRE(ctx, rc == VMP_OK, rc, "unsupported dims D=%d K=%d", D, K);
+    a.D = D;
+    a.K = K;
+    a.n_total = (double)n_total;
+    a.x_prec = x_prec;
+    a.a0t = a0t; a.b0t = b0t; a.a0a = a0a; a.b0a = b0a;
+    a.has_mean = 0;
+    return VMP_OK;
 }
 
 template <int O0, int O1, int O2>
@@ -987,7 +1087,7 @@ int32_t launch_small(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double
     // greedy: the two sequences a VB iteration produces are single launches (LDS-resident
     // forms when K <= 32 and D <= 128; VMP_PCA_FAST_SMALL=0 disables them), anything else
     // falls back to one launch per operation
-    static const int fast_enabled = getenv("VMP_PCA_FAST_SMALL") ? atoi(getenv("VMP_PCA_FAST_SMALL")) : 1;
+    const bool fast_enabled = fast_small_enabled();
     // (the LDS-resident forms are built for the zero prior mean of the demo model)
     const bool fast = fast_enabled && a.L.KP <= 32 && D <= FAST_D && !a.has_mean;
     // the Gram-form messages to W of the latest latent pass may still be pending (vmp_pca.hip
@@ -1011,10 +1111,10 @@ int32_t launch_small(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double
         if (o0 == VMP_PCA_OP_W && o1 == VMP_PCA_OP_XPREP) {
             if (fast && a.L.KP == 16)
                 hipLaunchKernelGGL(pca_head_fast_kernel<16>, dim3(1), dim3(NTF), 0, ctx->stream, a,
-                                   state);
+                                   state, (const double *)nullptr);
             else if (fast)
                 hipLaunchKernelGGL(pca_head_fast_kernel<32>, dim3(1), dim3(NTF), 0, ctx->stream, a,
-                                   state);
+                                   state, (const double *)nullptr);
             else
                 launch_sequence<VMP_PCA_OP_W, VMP_PCA_OP_XPREP, 0>(ctx, a, state);
             i += 2;
@@ -1066,6 +1166,43 @@ int32_t launch_small(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double
 }
 
 }  // namespace
+
+int32_t vmp_pca_sweep_covered(int32_t D, int32_t K)
+{
+    vmp_pca_layout L;
+    if (vmp_pca_get_layout(D, K, &L) != VMP_OK) return VMP_PCA_SWEEPS_NOT_BUILT;
+    return (fast_small_enabled() && L.KP <= 32 && D <= FAST_D) ? VMP_OK : VMP_PCA_SWEEPS_NOT_BUILT;
+}
+
+int32_t vmp_pca_launch_sweep_head(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                                  double a0t, double b0t, double a0a, double b0a, double *state,
+                                  const double *stop)
+{
+    small_args a;
+    const int32_t rc = fill_small_args(ctx, a, D, K, n_total, x_prec, a0t, b0t, a0a, b0a);
+    if (rc != VMP_OK) return rc;
+    if (a.L.KP == 16)
+        hipLaunchKernelGGL(pca_head_fast_kernel<16>, dim3(1), dim3(NTF), 0, ctx->stream, a, state, stop);
+    else
+        hipLaunchKernelGGL(pca_head_fast_kernel<32>, dim3(1), dim3(NTF), 0, ctx->stream, a, state, stop);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+int32_t vmp_pca_launch_sweep_tail(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                                  double a0t, double b0t, double a0a, double b0a, double *state,
+                                  const vmp_sweep_tail &t)
+{
+    small_args a;
+    const int32_t rc = fill_small_args(ctx, a, D, K, n_total, x_prec, a0t, b0t, a0a, b0a);
+    if (rc != VMP_OK) return rc;
+    if (a.L.KP == 16)
+        hipLaunchKernelGGL(pca_tail_sweep_kernel<16>, dim3(1), dim3(NTF), 0, ctx->stream, a, state, t);
+    else
+        hipLaunchKernelGGL(pca_tail_sweep_kernel<32>, dim3(1), dim3(NTF), 0, ctx->stream, a, state, t);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
 
 extern "C" {
 

@@ -123,6 +123,27 @@ class HIPKernels:
         self.rt.check(self.lib.vmp_pca_pass_counts(self.ctx, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    def sweeps(self, D, K, n_total, x_prec, a0t, b0t, a0a, b0a, Y, ldy, N, X, ldx, lay, state, ws,
+               n, ring, tol, compare, l0, order):
+        """vmp_pca_sweeps: n sweeps (W, X, tau, alpha, bound) enqueued without a host read between
+        them; ``ring`` receives 8 doubles per sweep.  False: the library does not run this shape as
+        a batch (or the path is switched off) and has done nothing."""
+        arr = (ctypes.c_int32 * len(order))(*order)
+        rc = self.lib.vmp_pca_sweeps(self.ctx, D, K, n_total, x_prec, a0t, b0t, a0a, b0a, ptr(Y),
+                                     ldy, N, ptr(X), ldx, lay, ptr(state), ptr(ws), n, ptr(ring),
+                                     tol, 1 if compare else 0, l0, len(order), arr)
+        if rc == _lib.VMP_PCA_SWEEPS_NOT_BUILT:
+            return False
+        self.rt.check(rc)
+        return True
+
+    def sweep_counts(self):
+        """(enqueued, executed, skipped) sweeps of vmp_pca_sweeps on the context."""
+        a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        self.rt.check(self.lib.vmp_pca_sweep_counts(self.ctx, ctypes.byref(a), ctypes.byref(b),
+                                                    ctypes.byref(c)))
+        return a.value, b.value, c.value
+
     def ensure_gram(self):
         """The Gram-form messages to W are formed lazily by the library (vmp_pca_ensure_gram):
         before the state block is read directly."""
@@ -715,6 +736,89 @@ class PCAPlan:
         if self._lib_hold and not self._hold:
             self.kernels.hold_passes(False)
             self._lib_hold = False
+
+    # -- batches of sweeps that need no host ------------------------------------------------------
+    # ``VB.update`` hands whole sweeps (W, X, tau, alpha, bound) to the library in chunks: the stop
+    # rule runs on the device, the host reads one ring of bound terms per chunk and replays its
+    # bookkeeping from it.
+    sweep_chunk = int(os.environ.get('BAYESPY_AMD_PCA_SWEEP_CHUNK', '32'))
+    BOUND_ORDER = ('Y', 'X', 'W', 'tau', 'alpha')      # the ring's term order (vmp_pca_sweeps)
+
+    def sweep_batch_ready(self, nodes):
+        """``nodes`` (the nodes of a sweep that have an ``update``) can run as a batch now: the
+        sweep is exactly W, X, tau, alpha, the Gram form with held passes, a zero prior mean,
+        device state and placed plate arrays exist (the first sweep of a fresh plan runs node by
+        node), and the kernels have the entry."""
+        if self.stats != 'gram' or not self.defer_passes or self.mu0 is not None \
+                or not self._ready or self._pending or self.sweep_chunk < 1 \
+                or not hasattr(self.kernels, 'sweeps'):
+            return False
+        if self.plate_layout == 'tiled' and self.Yt is None:
+            return False
+        if self.unsupported_state(self.roles) is not None:
+            return False
+        upd = [n for n in nodes if n is not self.Y and n is not self.F]
+        want = [self.W, self.X, self.tau, self.alpha]
+        if len(upd) != 4 or any(a is not b for a, b in zip(upd, want)):
+            return False
+        return self._delta <= {'W', 'X', 'tau', 'alpha'}
+
+    def bound_order(self, model):
+        """For every node of ``model``: the index of its bound term in a ring slot, -1 for a node
+        that contributes the constant 0.0."""
+        out = []
+        for n in model:
+            idx = -1
+            for i, key in enumerate(self.BOUND_ORDER):
+                if n is self.roles[key]:
+                    idx = i
+            out.append(idx)
+        return out
+
+    def run_sweeps(self, n, tol, compare, l0, order):
+        """Enqueue ``n`` sweeps, wait once, and return the ring as an (n, 8) host array -- per
+        sweep the bound terms Y, X, W, tau, alpha, their total, the status word and the
+        "executed" mark -- or None when the library runs nothing as a batch here."""
+        rt, k = self.rt, self.kernels
+        D, N, K = self.D, self.N, self.K
+        torch = rt.torch
+        rt.sync_stream()
+        ring = getattr(self, '_sweep_ring', None)
+        if ring is None or ring.numel() < 8 * n:
+            ring = self._sweep_ring = rt.zeros(8 * max(n, self.sweep_chunk))
+            self._sweep_ring_host = None
+        if self.plate_layout == 'tiled':
+            tiled_x = self._Xt is not None
+            Y, ldy, X, lay = self.Yt, 0, (self._Xt if tiled_x else self.Xd), (3 if tiled_x else 1)
+        else:
+            tiled_x = False
+            Y, ldy, X, lay = self.Yd, self.ldy, self.Xd, 0
+        if not k.sweeps(D, K, self.n_total, self.x_prec, self.a0t, self.b0t, self.a0a, self.b0a,
+                        Y, ldy, N, X, self.ldx, lay, self.state, self.ws, n, ring, tol, compare,
+                        l0, order):
+            return None
+        if tiled_x:
+            self._x_form, self._xrows_valid = 'tiled', False
+        self._delta -= {'W', 'X', 'tau', 'alpha'}
+        self._end_hold()
+        if rt.device.type != 'cuda':
+            host = ring[:8 * n].numpy().copy()
+        else:
+            if getattr(self, '_sweep_ring_host', None) is None:
+                self._sweep_ring_host = torch.empty(ring.numel(), dtype=torch.float64,
+                                                    pin_memory=True)
+            self._sweep_ring_host[:8 * n].copy_(ring[:8 * n], non_blocking=True)
+            torch.cuda.current_stream(rt.device).synchronize()
+            host = self._sweep_ring_host[:8 * n].numpy().copy()
+        host = host.reshape(n, 8)
+        self._version += 1
+        done = [i for i in range(n) if host[i, 7] != 0.0]
+        if done and int(host[done[-1], 6]) == 0:
+            t = host[done[-1]]
+            self._L = dict(Y=float(t[0]), X=float(t[1]), W=float(t[2]), tau=float(t[3]),
+                           alpha=float(t[4]), total=float(t[5]))
+            self._L_version = self._version
+        return host
 
     def place_plate_arrays(self):
         """The placement trial of :meth:`_place_plate_arrays` as an explicit set-up step (otherwise

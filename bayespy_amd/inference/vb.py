@@ -163,6 +163,15 @@ class VB:
         i = 0
         try:
             while repeat is None or i < repeat:
+                # whole sweeps that need nothing from the host run as one batch on the device
+                plan = self._sweep_plan(nodes)
+                if plan is not None:
+                    done, stop = self._run_sweep_batch(plan, repeat, i, tol, verbose, tqdm)
+                    i += done
+                    if stop:
+                        return
+                    if done:
+                        continue
                 # a plan may leave out plate-sized work of this sweep that the next sweep
                 # overwrites before anything reads it
                 self._hold_passes(repeat is None or i + 1 < repeat)
@@ -186,6 +195,78 @@ class VB:
                 fin = getattr(p, 'finish', None)
                 if fin is not None:
                     fin()
+
+    # -- batches of sweeps (plans/pca.py run_sweeps) -----------------------------------------------
+    def _sweep_plan(self, nodes):
+        """The plan that can run the next sweeps over ``nodes`` as a batch: a single plan owns the
+        whole model, nothing (a callback) needs the host between two sweeps, and the plan agrees
+        (``sweep_batch_ready``).  None: the nodes are visited one by one."""
+        if callable(self.callback):
+            return None
+        plan = None
+        for n in self.model:
+            p = n._plan
+            if p is None or (plan is not None and p is not plan):
+                return None
+            plan = p
+        ready = getattr(plan, 'sweep_batch_ready', None)
+        if ready is None or len(self.model) > 8:
+            return None
+        upd = []
+        for node in nodes:
+            X = self[node]
+            if hasattr(X, 'update') and callable(X.update):
+                upd.append(X)
+        return plan if ready(upd) else None
+
+    def _run_sweep_batch(self, plan, repeat, i, tol, verbose, tqdm):
+        """One chunk of sweeps on the device, then the bookkeeping of ``_end_iteration_step`` replayed
+        for every sweep that ran.  A chunk ends at ``repeat`` and at the next auto-save iteration.
+        Every sweep of a chunk is given an equal share of the chunk's wall time in ``cputime``.
+        Returns (sweeps done, stop)."""
+        n = plan.sweep_chunk
+        if repeat is not None:
+            n = min(n, repeat - i)
+        if self.autosave_iterations > 0:
+            n = min(n, self.autosave_iterations - self.iter % self.autosave_iterations)
+        self._hold_passes(repeat is None or i + n < repeat)
+        if tol is None:
+            tol = self.tol
+        compare = not self.ignore_bound_checks
+        l0 = float(self.L[self.iter - 1]) if self.iter > 0 and not self.annealing_changed \
+            else float('nan')
+        order = plan.bound_order(self.model)
+        t = time.time()
+        ring = plan.run_sweeps(n, float(tol), compare, l0, order)
+        if ring is None:
+            return 0, False
+        executed = int(np.count_nonzero(ring[:, 7]))
+        share = (time.time() - t) / max(executed, 1)
+        done = 0
+        for k in range(n):
+            slot = ring[k]
+            # the host's own stop decision must be the device's: a mismatch is a bug
+            assert slot[7] != 0.0, 'sweep %d of a batch was skipped by the device only' % k
+            status = int(slot[6])
+            if status != 0:
+                from .. import _lib
+                assert not np.any(ring[k + 1:, 7]), 'the device went on after a failed sweep'
+                _lib.raise_for_status(status)
+            if self.iter >= len(self.L):
+                self._append_iterations(100)
+            L = 0.0
+            for node, idx in zip(self.model, order):
+                lp = float(slot[idx]) if idx >= 0 else 0.0
+                L += lp
+                self.l[node][self.iter] = lp
+            stop = self._record_iteration(None, L, share, tol, verbose)
+            done += 1
+            if tqdm is not None:
+                tqdm.update()
+            if stop:
+                assert not np.any(ring[k + 1:, 7]), 'the device went on after the host stopped'
+                return done, True
+        return done, False
 
     def _hold_passes(self, more_follow):
         for p in self.plans:
@@ -586,6 +667,11 @@ class VB:
         t = time.time()
         L = self.loglikelihood_lowerbound()      # device -> host sync point
         cputime += time.time() - t
+        return self._record_iteration(method, L, cputime, tol, verbose)
+
+    def _record_iteration(self, method, L, cputime, tol, verbose):
+        """The bookkeeping of an iteration whose bound ``L`` (and ``self.l``) is known: trace, log
+        line, decrease warning, convergence test, auto-save."""
         self.cputime[self.iter] = cputime
         self.L[self.iter] = L
         if verbose:

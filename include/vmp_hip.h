@@ -212,6 +212,42 @@ int32_t vmp_pca_xjoin(vmp_ctx *ctx);
 int32_t vmp_pca_hold_passes(vmp_ctx *ctx, int32_t on);
 /* Latent passes (vmp_pca_xpass*) launched / superseded on this context since it was created. */
 int32_t vmp_pca_pass_counts(vmp_ctx *ctx, int64_t *launched, int64_t *superseded);
+/* A batch of n VB sweeps over (W, X, tau, alpha) in the Gram form, enqueued on the context's stream
+ * with NO synchronisation and no host read between them: per sweep the sequence W, XPREP,
+ * S = [G A^T ; A G A^T], TAU, ALPHA, ELBO of vmp_pca_small_ops / vmp_pca_xpass* as at most three
+ * launches and no copies.  Results are bit for bit those of n per-sweep calls.
+ *
+ * ring: n slots of VMP_PCA_SWEEP_SLOT doubles on the device.  Every sweep writes its slot: the bound
+ * terms [Y, X, W, tau, alpha, total], the status word (0 or a VMP_ERR_* code) and 1.0 for "executed";
+ * a sweep that was skipped writes 0.0 for "executed" only.
+ *
+ * Stopping: after its slot the last kernel of a sweep forms L = 0.0 + t[order[0]] + ... (the order
+ * the caller adds the terms in; order[i] = -1 stands for a constant 0.0) and stops the batch when
+ * the status is non-zero or, with compare != 0, when (L - L0) / (0.5 (|L0| + |L|)) < tol in fp64
+ * (csrc/vmp_stop_rule.h; a NaN compares false).  L0 is l0 for the first sweep -- pass NaN for
+ * "none" -- and the previous sweep's L after it.  Every kernel of a sweep after a stop returns at
+ * once: the state is what the stopping sweep left.
+ *
+ * The latent pass: only the last sweep of the batch issues one, after its W / XPREP kernel, exactly
+ * as vmp_pca_xpass (lay = 0: Y row-major with ldy), vmp_pca_xpass_tiled (lay = 1: tile-major Y,
+ * lay = 3: tile-major X as well; ldy unused) would -- so it is held under vmp_pca_hold_passes and
+ * it reads the A of the last EXECUTED sweep.  The passes of the other sweeps are counted as
+ * superseded (vmp_pca_pass_counts).
+ *
+ * Covers the shapes of the LDS-resident kernels (K <= 32, D <= 128, zero prior mean of W); returns
+ * VMP_PCA_SWEEPS_NOT_BUILT, having done nothing, for anything else and when VMP_PCA_SWEEPS=0 / tune
+ * key "pca_sweeps" = 0 turns the entry off: the caller then runs the sweeps one by one. */
+#define VMP_PCA_SWEEPS_NOT_BUILT 1
+#define VMP_PCA_SWEEP_SLOT 8
+#define VMP_PCA_MAX_SWEEPS 4096
+int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                       double a0_tau, double b0_tau, double a0_alpha, double b0_alpha,
+                       const double *Y, int64_t ldy, int64_t N, double *X, int64_t ldx, int32_t lay,
+                       double *state, void *workspace, int32_t n, double *ring, double tol,
+                       int32_t compare, double l0, int32_t norder, const int32_t *order);
+/* Sweeps enqueued by vmp_pca_sweeps on this context since it was created, and how many of them the
+ * device executed / skipped after a stop (waits for the context's stream). */
+int32_t vmp_pca_sweep_counts(vmp_ctx *ctx, int64_t *enqueued, int64_t *executed, int64_t *skipped);
 /* Gram form: the messages to W of the latest latent pass, S = [G A^T ; A G A^T] in the state block
  * (dot.py:581 collapsed onto the Gram matrix), are formed lazily -- by the fused tau / alpha / bound
  * kernel when it comes next, else by this call, which every other entry point that reads S makes
