@@ -1,0 +1,159 @@
+// vmp_hmm_fused_dev.h -- per-step arithmetic of the chain pass of the fused hidden-Markov-model
+// block (csrc/vmp_hmm_fused.hip), shared with the host build of the CPU tests
+// (tests/host/hmm_fused_host.cpp).
+//
+// A chain b has T time instances with observations y_t (D doubles) and K states.  With the
+// emission log-likelihoods e_t[j] = sum_f C[j][f] phi_f(y_t) (features phi in the compact order of
+// vmp_gmm_prepare_z: y_a y_b for a <= b, then y_d, then 1) the reference builds
+//     logp0[j] = <log a0_j> + e_0[j],    logP[n, i, j] = <log A_ij> + e_{n+1}[j],   n = 0 .. T-2,
+// and runs random.alpha_beta_recursion on it.  Here nothing of size K x K exists per step:
+//
+//   forward   la_0 = logp0 (not normalised, as in the reference); for n = 0 .. T-2
+//                 m_j = max_i (la_n[i] + A_ij),  s_j = sum_i exp(la_n[i] + A_ij - m_j)
+//                 q_j = m_j + log s_j + e_{n+1}[j]        (log of column j's sum)
+//                 c_n = lse_j q_j,  la_{n+1} = q - c_n,   log Z_b = sum_n c_n
+//             la_n (K doubles) goes to the workspace: the only thing kept per step.
+//   backward  lb_{T-1} = 0; for n = T-2 .. 0, with u_j = e_{n+1}[j] + lb_{n+1}[j]
+//                 gamma_{n+1} = softmax_j (la_{n+1}[j] + lb_{n+1}[j])
+//                 xi_n[i, j]  = gamma_{n+1}[j] exp(la_n[i] + A_ij - m_j) / s_j   (m, s as above)
+//                 lb_n[i]     = lse_j (A_ij + u_j), less its largest element
+//             and gamma_0 = softmax_i (la_0[i] + lb_0[i]) (= the normalised row sums of xi_0).
+//
+// Everything is a logarithm until the last exponential, whose argument is <= 0: tables such as
+// <log A_ij> = -985 everywhere (Dirichlet(1e-3) rows at K = 64) or one row near 0 and the others
+// near -670 never pass through exp(<log A>).  exp(-inf - m) counts as 0, so a state with -inf in
+// <log a0> or in a column of <log A> gets 0; a step whose logits are ALL -inf gives
+// c = -inf and la = -inf - (-inf) = NaN, as in the reference.
+//
+// ORDER OF THE ADDITIONS (what the host build restates):
+//   * K is padded to KP = 2, 4, ..., 64 lanes per chain, lane j owns column j (forward, xi,
+//     gamma, the statistics of state j) and row j (lb);  64 / KP chains share a wavefront;
+//   * sums over i (or over j for lb) run in ascending order inside the lane; maxima and sums over
+//     the lanes of a chain are butterflies with partner j ^ 1, j ^ 2, ..., j ^ (KP / 2);
+//   * e = sum over the features in compact order, starting from zero;
+//   * a workgroup (one wavefront) owns vmp_hmmf_chains_per_wg(B, D, K) consecutive chains;
+//     chain c of its range belongs to lane group c % (64 / KP), which walks its chains in
+//     ascending order and adds each chain's steps in the order of the backward sweep
+//     (t = T-1 ... 1, then t = 0);  the groups are added in group order, then the workgroups'
+//     partials in workgroup order by a second kernel.
+// The bits of every output therefore depend on the inputs and (B, T, D, K) only.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#define VMP_HMMF_MAX_K 64
+#define VMP_HMMF_MAX_D 8
+#define VMP_HMMF_MAX_WGS 4096
+#define VMP_HMMF_MAX_NF 45        // features of D = 8
+
+__host__ __device__ inline int vmp_hmmf_kpad(int K)
+{
+    int p = 2;
+    while (p < K) p <<= 1;
+    return p;
+}
+
+// compact features: y_a y_b (a <= b), y_d, 1
+__host__ __device__ inline int vmp_hmmf_nfeat(int D) { return D * (D + 1) / 2 + D + 1; }
+
+// doubles one workgroup leaves behind: sum gamma_0 (K), sum xi (K x K), the feature sums
+// (K x NF, compact), sum log Z, sum gamma . e
+__host__ __device__ inline int64_t vmp_hmmf_partial_doubles(int D, int K)
+{
+    return (int64_t)K + (int64_t)K * K + (int64_t)K * vmp_hmmf_nfeat(D) + 2;
+}
+
+// chains of a workgroup: a function of the shape alone; a multiple of the 64 / KP chains that
+// share the wavefront, at most VMP_HMMF_MAX_WGS workgroups and 2^24 doubles of partials
+__host__ __device__ inline int64_t vmp_hmmf_chains_per_wg(int64_t B, int D, int K)
+{
+    const int64_t groups = 64 / vmp_hmmf_kpad(K);
+    int64_t maxw = ((int64_t)1 << 24) / vmp_hmmf_partial_doubles(D, K);
+    if (maxw > VMP_HMMF_MAX_WGS) maxw = VMP_HMMF_MAX_WGS;
+    if (maxw < 1) maxw = 1;
+    int64_t c = (B + maxw - 1) / maxw;
+    c = (c + groups - 1) / groups * groups;
+    if (c < groups) c = groups;
+    return c;
+}
+
+__host__ __device__ inline int64_t vmp_hmmf_wgs(int64_t B, int D, int K)
+{
+    const int64_t c = vmp_hmmf_chains_per_wg(B, D, K);
+    return B > 0 ? (B + c - 1) / c : 0;
+}
+
+// workspace of the pass: la (B T K), the partials, 1024 doubles for the dot products
+__host__ __device__ inline int64_t vmp_hmmf_workspace_doubles(int64_t B, int T, int D, int K)
+{
+    return B * (int64_t)T * K + vmp_hmmf_wgs(B, D, K) * vmp_hmmf_partial_doubles(D, K) + 1024;
+}
+
+// the two factors of feature f as indices into (y_0 .. y_{D-1}, 1)
+__host__ __device__ inline void vmp_hmmf_feature(int D, int f, int *pa, int *pb)
+{
+    const int npair = D * (D + 1) / 2;
+    if (f < npair) {
+        int rem = f, a = 0;
+        while (rem >= D - a) { rem -= D - a; ++a; }
+        *pa = a;
+        *pb = a + rem;
+    } else {
+        *pa = f - npair;          // y_d, and D for the constant
+        *pb = D;
+    }
+}
+
+// exp(x - m) with the conventions of a masked softmax: -inf gives 0 whatever m is
+__host__ __device__ inline double vmp_hmmf_exp_shift(double x, double m)
+{
+    return (x == -INFINITY) ? 0.0 : exp(x - m);
+}
+
+// e = sum_f C[f * ldc] phi[f], from zero in ascending f
+__host__ __device__ inline double vmp_hmmf_emit(const double *C, int ldc, const double *phi, int NF)
+{
+    double e = 0.0;
+    for (int f = 0; f < NF; ++f) e += C[f * ldc] * phi[f];
+    return e;
+}
+
+// column (or row) j of the recursion: m = max_i (v[i] + a[i * lda]), s = sum_i exp(. - m)
+__host__ __device__ inline void vmp_hmmf_column(const double *v, const double *a, int lda, int K,
+                                                double *m, double *s)
+{
+    double mm = -INFINITY;
+    for (int i = 0; i < K; ++i) mm = fmax(mm, v[i] + a[i * lda]);
+    double ss = 0.0;
+    for (int i = 0; i < K; ++i) ss += vmp_hmmf_exp_shift(v[i] + a[i * lda], mm);
+    *m = mm;
+    *s = ss;
+}
+
+// xi = gamma p / s; a state that cannot be reached (gamma == 0) contributes exact zeros
+__host__ __device__ inline double vmp_hmmf_ratio(double gamma, double s)
+{
+    return gamma == 0.0 ? 0.0 : gamma / s;
+}
+
+#ifndef __HIPCC__
+// butterflies over the KP lanes of a chain; every element ends with the result
+inline void vmp_hmmf_group_max_host(double *v, int KP)
+{
+    double t[VMP_HMMF_MAX_K];
+    for (int off = 1; off < KP; off <<= 1) {
+        for (int l = 0; l < KP; ++l) t[l] = fmax(v[l], v[l ^ off]);
+        for (int l = 0; l < KP; ++l) v[l] = t[l];
+    }
+}
+
+inline void vmp_hmmf_group_sum_host(double *v, int KP)
+{
+    double t[VMP_HMMF_MAX_K];
+    for (int off = 1; off < KP; off <<= 1) {
+        for (int l = 0; l < KP; ++l) t[l] = v[l] + v[l ^ off];
+        for (int l = 0; l < KP; ++l) v[l] = t[l];
+    }
+}
+#endif

@@ -945,6 +945,43 @@ int32_t vmp_bmm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, const uint64
                      const int32_t *labels, const double *w, const double *c, double *ws,
                      double *S, double *Nk, double *counts, double *scal, double *r_out);
 
+/* Hidden Markov model with Gaussian emissions: the chain pass of the fused block
+ * (doc/source/examples/hmm.rst; details: bayespy_amd/csrc/vmp_hmm_fused.hip, vmp_hmm_fused_dev.h).
+ * B chains of T time instances, D-dimensional observations, K states.  No (B, T-1, K, K) array is
+ * read or written unless `zz` is asked for; the forward state kept per step is K doubles.
+ *   vmp_hmm_fused_limits (host only): *max_K = 64, *max_D = 8.
+ *   vmp_hmm_fused_plan (host only): for (B, T, D, K) the chains of a workgroup *chains_per_wg (a
+ *     function of the shape alone) and the scratch *workspace_doubles of the pass
+ *     (B T K + partials + 1024).
+ *   vmp_hmm_fused_pass: Y (B, T, D) row-major; C (K rows of stride ldc) the coefficients of
+ *     e_t[k] = E[log p(y_t | k)] in the compact feature order of vmp_gmm_prepare_z (y_a y_b for
+ *     a <= b, then y_d, then 1: the C table of a vmp_gmm_layout state whose <log pi> slot is
+ *     zero), or NULL for no emission term (the moments of Z under its prior); elog_a0 (K),
+ *     elog_A (K x K).  The forward-backward recursion of random.alpha_beta_recursion on
+ *     logp0 = elog_a0 + e_0, logP[n] = elog_A + e_{n+1}, in the log domain throughout.
+ *     Out: z0sum (K) = sum_b gamma_{b,0}; xisum (K x K) = sum_{b,t} xi_{b,t}; Tstat (K rows
+ *     [sum gamma, sum gamma y, sum gamma y y^T] of length 1 + D + D^2: the T of vmp_gmm_layout);
+ *     scal[0] = sum_b log Z_b, scal[1] = sum gamma . e, scal[2] = z0sum . elog_a0,
+ *     scal[3] = xisum . elog_A.  With gamma (B, T, K), z0 (B, K), zz (B, T-1, K, K) non-NULL also
+ *     these.  `labels` (B x T int32) non-NULL: gamma and xi are the one-hot arrays of these states
+ *     instead, log Z = 0 and scal[1] = 0.  ws: vmp_hmm_fused_plan's doubles.  No atomics: the bits
+ *     of every output depend on the inputs and (B, T, D, K) only, with or without the optional
+ *     outputs.  A state with -inf in elog_a0 or in a column of elog_A gets 0 in gamma, xi and the
+ *     sums; scal[2] and scal[3] are plain dot products with the tables as given, so they are
+ *     0 * -inf = NaN for such tables (the tables of a Dirichlet node are finite).  A step whose
+ *     logits are all -inf gives NaN, as in the reference.  B = 0 gives zeros.  The shape is judged
+ *     before the pointers: T < 2 or a negative size: VMP_ERR_INVALID; K or D above the limits:
+ *     VMP_ERR_UNSUPPORTED; then ldc below the number of features or a null argument:
+ *     VMP_ERR_INVALID.  Nothing is launched after a refusal. */
+int32_t vmp_hmm_fused_limits(int32_t *max_K, int32_t *max_D);
+int32_t vmp_hmm_fused_plan(int64_t B, int32_t T, int32_t D, int32_t K, int64_t *chains_per_wg,
+                           int64_t *workspace_doubles);
+int32_t vmp_hmm_fused_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t K,
+                           const double *Y, const double *C, int32_t ldc, const double *elog_a0,
+                           const double *elog_A, const int32_t *labels, double *ws,
+                           double *z0sum, double *xisum, double *Tstat, double *scal,
+                           double *gamma, double *z0, double *zz);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
