@@ -36,6 +36,7 @@ struct HmmfArgs {
     double *aw;               // B x T x K forward state
     double *part;             // workgroups x vmp_hmmf_partial_doubles
     double *gamma, *z0, *zz;  // optional outputs
+    const uint8_t *mask;      // B x T, 1 = observed (the MASKED instances only)
 };
 
 template <int KP>
@@ -64,8 +65,18 @@ __device__ __forceinline__ double across_groups(double v, int lane)
     return t;
 }
 
-template <int KP>
-__global__ __launch_bounds__(64) void hmmf_pass_kernel(HmmfArgs a)
+// MASKED: a step with mask[b, t] == 0 has e = 0 and adds nothing to the feature sums or to
+// sum gamma . e, and its y is never read; a chain without an observed step adds nothing to any sum.
+// Lane groups hold chains with different masks, so the mask only selects values and skips a lane's
+// own accumulation: every fence and shuffle stays in wavefront-uniform control flow.
+//
+// The MASKED instances are asked for 3, 3, 3, 2, 1, 1 wavefronts per SIMD at KP = 2 ... 64, those
+// of their unmasked twins but for KP = 2: left alone, KP = 8 takes 169 registers, one more than
+// three wavefronts allow; KP = 2 at the four of its twin would need scratch memory.
+template <int KP, bool MASKED>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
+    MASKED ? (KP <= 8 ? 3 : KP == 16 ? 2 : 1) : 1)))
+void hmmf_pass_kernel(HmmfArgs a)
 {
     extern __shared__ double hmmf_lds[];
     constexpr int G = 64 / KP;
@@ -108,15 +119,24 @@ __global__ __launch_bounds__(64) void hmmf_pass_kernel(HmmfArgs a)
     for (int i = 0; i < KP; ++i) xi[i] = 0.0;
     double z0acc = 0.0, logZ = 0.0, ge = 0.0;
 
-    // features of y_t of this group's chain into myphi; returns this lane's e_t[j]
-    auto features = [&](const double *yt) -> double {
-        for (int d = j; d < D; d += KP) myy[d] = yt[d];
+    // features of y_t of this group's chain into myphi; returns this lane's e_t[j].  A masked
+    // step (o false) loads zeros in place of y_t and returns 0.
+    auto features = [&](const double *yt, bool o) -> double {
+        if constexpr (MASKED) {
+            for (int d = j; d < D; d += KP) myy[d] = o ? yt[d] : 0.0;
+        } else {
+            for (int d = j; d < D; d += KP) myy[d] = yt[d];
+        }
         lds_fence();
         for (int f = j; f < NF; f += KP) myphi[f] = myy[fa[f]] * myy[fb[f]];
         lds_fence();
-        return a.C ? vmp_hmmf_emit(Ccol, KP, myphi, NF) : 0.0;
+        const double e = a.C ? vmp_hmmf_emit(Ccol, KP, myphi, NF) : 0.0;
+        if constexpr (MASKED) return vmp_hmmf_observed_or_zero(o, e);
+        return e;
     };
-    auto accumulate = [&](double g, double e) {
+    // a lane's own sums: no fence and no shuffle in here, so a masked step may skip it
+    auto accumulate = [&](double g, double e, bool o) {
+        if (MASKED && !o) return;
         if (g != 0.0) ge += g * e;
         for (int f = 0; f < NF; ++f) facc[f * 64 + lane] += g * myphi[f];
     };
@@ -127,9 +147,21 @@ __global__ __launch_bounds__(64) void hmmf_pass_kernel(HmmfArgs a)
         const int64_t c = c0 + grp;
         const bool live = c < c_end;
         const int64_t cc = live ? c : c_begin;
-        const double w = live ? 1.0 : 0.0;
+        const double wlive = live ? 1.0 : 0.0;
         const bool store = live && act;
         const double *Yc = a.Y + cc * (int64_t)T * D;
+        // the chain's weight: 0 past the end of the range and, MASKED, without an observed step
+        const uint8_t *mrow = MASKED ? a.mask + cc * (int64_t)T : nullptr;
+        double wchain = wlive;
+        if constexpr (MASKED) {
+            int any = 0;
+            for (int t = j; t < T; t += KP) any |= mrow[t];
+#pragma unroll
+            for (int m = 1; m < KP; m <<= 1) any |= __shfl_xor(any, m, 64);
+            if (any == 0) wchain = 0.0;
+        }
+        const double w = wchain;
+        auto obs = [&](int t) -> bool { return MASKED ? mrow[t] != 0 : true; };
 
         if (a.labels) {
             // fixed states: gamma and xi are one-hot, log Z = 0
@@ -137,9 +169,10 @@ __global__ __launch_bounds__(64) void hmmf_pass_kernel(HmmfArgs a)
             int prev = -1;
             for (int t = 0; t < T; ++t) {
                 const int cur = lab[t];
-                features(Yc + (int64_t)t * D);
+                const bool o = obs(t);
+                features(Yc + (int64_t)t * D, o);
                 const double g = (j == cur) ? 1.0 : 0.0;
-                accumulate(g * w, 0.0);
+                accumulate(g * w, 0.0, o);
                 if (t == 0) {
                     z0acc += g * w;
                     if (a.z0 && store) a.z0[cc * K + j] = g;
@@ -161,12 +194,12 @@ __global__ __launch_bounds__(64) void hmmf_pass_kernel(HmmfArgs a)
 
         double *aw = a.aw + cc * (int64_t)T * K;
         // ---- forward ---------------------------------------------------------------------------
-        double la = la0 + features(Yc);
+        double la = la0 + features(Yc, obs(0));
         if (!act) la = -INFINITY;
         if (store) aw[j] = la;
         for (int n = 1; n < T; ++n) {
             myv[j] = la;
-            const double e = features(Yc + (int64_t)n * D);      // fences the LDS writes
+            const double e = features(Yc + (int64_t)n * D, obs(n));      // fences the LDS writes
             double m, s;
             vmp_hmmf_column(myv, Acol, KP, K, &m, &s);
             const double q = act ? m + log(s) + e : -INFINITY;
@@ -185,7 +218,8 @@ __global__ __launch_bounds__(64) void hmmf_pass_kernel(HmmfArgs a)
         double la_next = la;
         for (int n = T - 2; n >= 0; --n) {
             const double lan = act ? aw[(int64_t)n * K + j] : -INFINITY;
-            const double e = features(Yc + (int64_t)(n + 1) * D);
+            const bool o = obs(n + 1);
+            const double e = features(Yc + (int64_t)(n + 1) * D, o);
             const double gl = act ? la_next + lb : -INFINITY;
             const double M = grp_max<KP>(gl);
             const double ex = vmp_hmmf_exp_shift(gl, M);
@@ -211,7 +245,7 @@ __global__ __launch_bounds__(64) void hmmf_pass_kernel(HmmfArgs a)
                 if (a.zz && store && i < K)
                     a.zz[((cc * (int64_t)(T - 1) + n) * K + i) * K + j] = x;
             }
-            accumulate(gamma * w, e);
+            accumulate(gamma * w, e, o);
             if (a.gamma && store) a.gamma[(cc * (int64_t)T + n + 1) * K + j] = gamma;
             // lb_n[i] on lane i: the row of <log A> is a column of its transpose
             double mr, sr;
@@ -222,13 +256,14 @@ __global__ __launch_bounds__(64) void hmmf_pass_kernel(HmmfArgs a)
             lds_fence();
         }
         {
-            const double e = features(Yc);
+            const bool o = obs(0);
+            const double e = features(Yc, o);
             const double gl = act ? la_next + lb : -INFINITY;
             const double M = grp_max<KP>(gl);
             const double ex = vmp_hmmf_exp_shift(gl, M);
             const double gamma = ex / grp_sum<KP>(ex);
             z0acc += gamma * w;
-            accumulate(gamma * w, e);
+            accumulate(gamma * w, e, o);
             if (a.gamma && store) a.gamma[cc * (int64_t)T * K + j] = gamma;
             if (a.z0 && store) a.z0[cc * K + j] = gamma;
             lds_fence();
@@ -300,7 +335,7 @@ hmmf_combine_kernel(int64_t nw, int D, int K, const double *__restrict__ part,
     }
 }
 
-template <int KP>
+template <int KP, bool MASKED>
 int32_t launch_pass(vmp_ctx *ctx, int64_t nw, const HmmfArgs &a)
 {
     constexpr int G = 64 / KP;
@@ -309,12 +344,12 @@ int32_t launch_pass(vmp_ctx *ctx, int64_t nw, const HmmfArgs &a)
     static bool raised[64] = {false};
     const int dev = ctx->device & 63;
     if (lds > 48 * 1024 && !raised[dev]) {
-        VMP_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)hmmf_pass_kernel<KP>,
+        VMP_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)hmmf_pass_kernel<KP, MASKED>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                                160 * 1024));
         raised[dev] = true;
     }
-    hipLaunchKernelGGL(hmmf_pass_kernel<KP>, dim3((unsigned)nw), dim3(64), lds, ctx->stream, a);
+    hipLaunchKernelGGL((hmmf_pass_kernel<KP, MASKED>), dim3((unsigned)nw), dim3(64), lds, ctx->stream, a);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }
@@ -342,11 +377,12 @@ int32_t vmp_hmm_fused_plan(int64_t B, int32_t T, int32_t D, int32_t K, int64_t *
     return VMP_OK;
 }
 
-int32_t vmp_hmm_fused_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t K,
-                           const double *Y, const double *C, int32_t ldc, const double *elog_a0,
-                           const double *elog_A, const int32_t *labels, double *ws,
-                           double *z0sum, double *xisum, double *Tstat, double *scal,
-                           double *gamma, double *z0, double *zz)
+int32_t vmp_hmm_fused_pass_masked(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t K,
+                                  const double *Y, const double *C, int32_t ldc,
+                                  const double *elog_a0, const double *elog_A,
+                                  const int32_t *labels, const uint8_t *mask, double *ws,
+                                  double *z0sum, double *xisum, double *Tstat, double *scal,
+                                  double *gamma, double *z0, double *zz)
 {
     // the shape first, so that the answer for a shape does not depend on the other arguments
     VMP_REQUIRE(ctx, B >= 0 && T >= 2 && D >= 1 && K >= 1, VMP_ERR_INVALID, "bad arguments");
@@ -362,15 +398,26 @@ int32_t vmp_hmm_fused_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_
     double *part = ws + B * (int64_t)T * K;
     if (nw > 0) {
         HmmfArgs a = {B, vmp_hmmf_chains_per_wg(B, D, K), T, D, K, NF, ldc, Y, C, elog_a0,
-                      elog_A, labels, ws, part, gamma, z0, zz};
+                      elog_A, labels, ws, part, gamma, z0, zz, mask};
         int32_t rc;
-        switch (vmp_hmmf_kpad(K)) {
-        case 2: rc = launch_pass<2>(ctx, nw, a); break;
-        case 4: rc = launch_pass<4>(ctx, nw, a); break;
-        case 8: rc = launch_pass<8>(ctx, nw, a); break;
-        case 16: rc = launch_pass<16>(ctx, nw, a); break;
-        case 32: rc = launch_pass<32>(ctx, nw, a); break;
-        default: rc = launch_pass<64>(ctx, nw, a); break;
+        if (mask) {
+            switch (vmp_hmmf_kpad(K)) {
+            case 2: rc = launch_pass<2, true>(ctx, nw, a); break;
+            case 4: rc = launch_pass<4, true>(ctx, nw, a); break;
+            case 8: rc = launch_pass<8, true>(ctx, nw, a); break;
+            case 16: rc = launch_pass<16, true>(ctx, nw, a); break;
+            case 32: rc = launch_pass<32, true>(ctx, nw, a); break;
+            default: rc = launch_pass<64, true>(ctx, nw, a); break;
+            }
+        } else {
+            switch (vmp_hmmf_kpad(K)) {
+            case 2: rc = launch_pass<2, false>(ctx, nw, a); break;
+            case 4: rc = launch_pass<4, false>(ctx, nw, a); break;
+            case 8: rc = launch_pass<8, false>(ctx, nw, a); break;
+            case 16: rc = launch_pass<16, false>(ctx, nw, a); break;
+            case 32: rc = launch_pass<32, false>(ctx, nw, a); break;
+            default: rc = launch_pass<64, false>(ctx, nw, a); break;
+            }
         }
         if (rc != VMP_OK) return rc;
     }
@@ -381,6 +428,16 @@ int32_t vmp_hmm_fused_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_
     int32_t rc = vmp_lda_dot(ctx, K, z0sum, elog_a0, dot_ws, scal + 2);
     if (rc != VMP_OK) return rc;
     return vmp_lda_dot(ctx, (int64_t)K * K, xisum, elog_A, dot_ws, scal + 3);
+}
+
+int32_t vmp_hmm_fused_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t K,
+                           const double *Y, const double *C, int32_t ldc, const double *elog_a0,
+                           const double *elog_A, const int32_t *labels, double *ws,
+                           double *z0sum, double *xisum, double *Tstat, double *scal,
+                           double *gamma, double *z0, double *zz)
+{
+    return vmp_hmm_fused_pass_masked(ctx, B, T, D, K, Y, C, ldc, elog_a0, elog_A, labels, nullptr,
+                                     ws, z0sum, xisum, Tstat, scal, gamma, z0, zz);
 }
 
 }  // extern "C"

@@ -37,6 +37,19 @@
 //     (t = T-1 ... 1, then t = 0);  the groups are added in group order, then the workgroups'
 //     partials in workgroup order by a second kernel.
 // The bits of every output therefore depend on the inputs and (B, T, D, K) only.
+//
+// MASKS (vmp_hmm_fused_pass_masked; mask[b, t] = 1 where y_{b,t} is observed).  A masked step
+// sends a zero message: e_t = 0 for every state.  The step stays in the chain: the recursion above
+// runs over all T steps with that e, trailing masked steps propagate through <log A> and their xi
+// counts.  y_t of a masked step is never read (the pass selects, it does not multiply by zero), so
+// NaN may stand there.  Chain b has the weight o_b = "any step of b observed"; the sums are
+//     sum gamma_0 = sum_b o_b gamma_{b,0},   sum xi = sum_b o_b sum_n xi_{b,n},
+//     sum log Z = sum_b o_b log Z_b,   T_k and sum gamma . e over the observed (b, t) only.
+// The order of the additions is the one above with the masked steps absent from the feature sums
+// and from sum gamma . e, and with the terms of a chain that has o_b = 0 multiplied by 0 (as those
+// of the chains past the end of a workgroup's range are).  A mask of ones gives the bits of the
+// unmasked pass.  gamma, z0 and zz of a chain with o_b = 0 are what the recursion gives with
+// e = 0 throughout (the reference leaves the moments of such a chain at their initial values).
 #pragma once
 
 #include <math.h>
@@ -117,6 +130,20 @@ __host__ __device__ inline double vmp_hmmf_emit(const double *C, int ldc, const 
     double e = 0.0;
     for (int f = 0; f < NF; ++f) e += C[f * ldc] * phi[f];
     return e;
+}
+
+// the emission term of a step: 0 where it is masked, whatever e holds (NaN included)
+__host__ __device__ inline double vmp_hmmf_observed_or_zero(bool observed, double e)
+{
+    return observed ? e : 0.0;
+}
+
+// the weight of a chain: 1 if any of its T steps is observed
+__host__ __device__ inline int vmp_hmmf_chain_observed(const uint8_t *row, int T)
+{
+    int any = 0;
+    for (int t = 0; t < T; ++t) any |= row[t];
+    return any != 0;
 }
 
 // column (or row) j of the recursion: m = max_i (v[i] + a[i * lda]), s = sum_i exp(. - m)

@@ -7,8 +7,8 @@ Execution plan of the hidden-Markov-model block (doc/source/examples/hmm.rst, se
 
 with (a) constant emission parameters ``mu`` (K, D) and ``Lambda`` (D, D) or (K, D, D), or (b)
 ``mu = GaussianARD(0, const, shape=(D,), plates=(K,))`` and ``Lambda = Wishart(const, const (D, D),
-plates=(K,))`` -- the priors of the Gaussian-mixture block; constant priors, a fully observed ``Y``,
-T >= 2, K <= 64 and D <= 8.  Opt-in: ``VB(..., engine='fused')``;
+plates=(K,))`` -- the priors of the Gaussian-mixture block; constant priors, ``Y`` observed without
+a mask or with a mask of the full shape of its plates (below), T >= 2, K <= 64 and D <= 8.  Opt-in: ``VB(..., engine='fused')``;
 the default engine runs this model on the generic engine as before.  The plan owns, in HBM: ``y``
 (B, T, D), the coefficient table ``C`` of the emission log-likelihoods (filled once from the
 constants), the Dirichlet parameters and <log> tables of ``a0`` and ``A``, the tables the last
@@ -29,6 +29,16 @@ Form (b) keeps ``mu`` and ``Lambda`` in a ``vmp_gmm_layout`` state whose <log pi
 state, ``vmp_gmm_update_mu`` / ``vmp_gmm_update_lambda`` update from ``T`` and
 ``vmp_gmm_lower_bound`` gives <log p(Y)> (with the present ``mu`` and ``Lambda``) and the terms of
 ``mu`` and ``Lambda``.  No kernel of the mixture block is copied.
+
+Masks: ``Y.observe(y, mask=m)`` with a boolean host array or a ``DeviceMask`` of shape ``Y.plates``
+exactly.  The mask is kept as ``uint8`` (B, T) in HBM and the pass becomes
+``vmp_hmm_fused_pass_masked``: a masked step sends a zero message to ``Z`` but stays a step of the
+chain, contributes nothing to ``T_k``, sum gamma . e or <log p(Y)>, and its ``y`` is never read (NaN
+is fine there).  ``Z.mask[b]`` is "any step of chain b observed"; a chain without one contributes
+nothing to sum gamma_0, sum xi, sum log Z or the entropy, so the formulas above hold unchanged on
+the masked sums.  Deviation: the reference leaves the moments of such a chain at their initial
+values; here ``Z.get_moments()`` returns for it what the recursion gives without any emission term.
+A scalar mask or one that broadcasts over a plate is declined.
 """
 import ctypes
 
@@ -38,7 +48,7 @@ from . import _delta
 
 from ... import _lib
 from ...device import get_runtime, ptr
-from ...nodes.node import Constant
+from ...nodes.node import Constant, DeviceMask
 from ...nodes.dirichlet import Dirichlet
 from ...nodes.gaussian import Gaussian, GaussianARD
 from ...nodes.wishart import Wishart
@@ -114,6 +124,15 @@ class HMMKernels:
             self.ctx, B, T, D, K, p(Y), p(C), ldc, p(elog_a0), p(elog_A), p(labels), p(ws),
             p(z0sum), p(xisum), p(Tstat), p(scal), p(gamma), p(z0), p(zz)))
 
+    def pass_masked(self, B, T, D, K, Y, C, ldc, elog_a0, elog_A, labels, mask, ws, z0sum, xisum,
+                    Tstat, scal, gamma=None, z0=None, zz=None):
+        """``pass_`` with ``mask`` (B, T) uint8, 1 = observed."""
+        def p(t):
+            return ptr(t) if t is not None else None
+        self.rt.check(self.lib.vmp_hmm_fused_pass_masked(
+            self.ctx, B, T, D, K, p(Y), p(C), ldc, p(elog_a0), p(elog_A), p(labels), p(mask), p(ws),
+            p(z0sum), p(xisum), p(Tstat), p(scal), p(gamma), p(z0), p(zz)))
+
     def dirichlet(self, rows, cols, rs, cs, prior, counts, alpha, elog, ws, bound):
         self.rt.check(self.lib.vmp_lda_dirichlet(
             self.ctx, rows, cols, rs, cs, ptr(prior), ptr(counts) if counts is not None else None,
@@ -121,6 +140,15 @@ class HMMKernels:
 
     def dot(self, m, a, b, ws, out):
         self.rt.check(self.lib.vmp_lda_dot(self.ctx, m, ptr(a), ptr(b), ptr(ws), ptr(out)))
+
+
+def _mask_shape(mask):
+    return tuple(mask.shape) if isinstance(mask, DeviceMask) else np.shape(mask)
+
+
+def _takes_mask(Y):
+    """No mask, or one of the full shape of the plates of ``Y``."""
+    return Y._mask is True or _mask_shape(Y._mask) == tuple(Y.plates)
 
 
 def _match(nodes, why):
@@ -156,8 +184,11 @@ def _match(nodes, why):
         if any(getattr(n, '_shard_axis', None) is not None for n in chain):
             no('a plate is sharded over ranks')
             continue
-        if Y._mask is not True:
-            no('it has a mask')
+        if not _takes_mask(Y):
+            no('it has a mask of shape %s: the block takes no mask or a mask of the full shape of '
+               'the plates of Y, here %s ((T,) for one chain, (B, T) for a batch); a scalar mask '
+               'or one that broadcasts over a plate goes through the generic engine'
+               % (_mask_shape(Y._mask), tuple(Y.plates)))
             continue
         bad = [n for n in (a0, A) if not isinstance(n.parents[0], Constant)]
         if bad:
@@ -248,7 +279,8 @@ class HMMPlan:
         return ("Mixture(CategoricalMarkovChain(Dirichlet(const), Dirichlet(const, plates=(K,)), "
                 "states=T), Gaussian, mu, Lambda) with constant mu and Lambda or GaussianARD(0, const, "
                 "shape=(D,), plates=(K,)) and Wishart(const, const, plates=(K,)), plates (T,) or "
-                "(B, T), fully observed, T >= 2, D <= %d, K <= %d" % (hmm_limits()[1], hmm_limits()[0]))
+                "(B, T), observed without a mask or with a boolean mask of exactly that shape "
+                "(missing observations, ragged lengths), T >= 2, D <= %d, K <= %d" % (hmm_limits()[1], hmm_limits()[0]))
 
     @staticmethod
     def match(nodes, why=None):
@@ -266,6 +298,7 @@ class HMMPlan:
         self._rt, self._kernels = runtime, kernels
         self._ready = False
         self._y_stale = False
+        self.maskd = None                # uint8 (B, T) in HBM, or None without a mask
         self._version = 0
         self._L_version = -1
         self._L = None
@@ -291,8 +324,9 @@ class HMMPlan:
         return bool(self._ready)
 
     def invalidate(self, node):
-        if node is self.Y and node.observed and node._mask is True:
-            # new observations of the same shape: the sums are formed again, the posteriors stay
+        if node is self.Y and node.observed and _takes_mask(node):
+            # new observations of the same shape, with a mask of the full shape or none: y and the
+            # mask are uploaded and the sums formed again, the posteriors stay
             self._y_stale = True
             self._version += 1
             return
@@ -317,6 +351,14 @@ class HMMPlan:
             a = np.broadcast_to(np.asarray(y, dtype=np.float64), self.Y.plates + (self.D,))
             t = torch.from_numpy(np.array(a.reshape(shape), order='C')).to(rt.device)
         self.Yd = t
+        m = self.Y._mask
+        if m is True:
+            self.maskd = None
+        elif isinstance(m, DeviceMask):
+            self.maskd = m.tensor.to(rt.device).reshape(self.B, self.T).to(torch.uint8).contiguous()
+        else:
+            self.maskd = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(m, dtype=bool).reshape(self.B, self.T).astype(np.uint8))).to(rt.device)
         self._y_stale = False
 
     @staticmethod
@@ -406,10 +448,15 @@ class HMMPlan:
         if refresh:
             self.used_a0.copy_(self.elog_a0)
             self.used_A.copy_(self.elog_A)
-        self.kernels.pass_(self.B, self.T, self.D, self.K, self.Yd,
-                           self.C if self._with_emissions else None, self.ldc, self.used_a0,
-                           self.used_A, self.labels, self.ws, self.z0sum, self.xisum, self.Tstat,
-                           self.scal, gamma, z0, zz)
+        C = self.C if self._with_emissions else None
+        if self.maskd is None:
+            self.kernels.pass_(self.B, self.T, self.D, self.K, self.Yd, C, self.ldc, self.used_a0,
+                               self.used_A, self.labels, self.ws, self.z0sum, self.xisum,
+                               self.Tstat, self.scal, gamma, z0, zz)
+        else:
+            self.kernels.pass_masked(self.B, self.T, self.D, self.K, self.Yd, C, self.ldc,
+                                     self.used_a0, self.used_A, self.labels, self.maskd, self.ws,
+                                     self.z0sum, self.xisum, self.Tstat, self.scal, gamma, z0, zz)
         if refresh or gamma is None:
             self._version += 1              # writing gamma / z0 / zz out changes no sum
 
@@ -517,6 +564,22 @@ class HMMPlan:
             return [y, y[..., :, None] * y[..., None, :]]
         raise NotImplementedError
 
+    def _host_mask(self):
+        """The mask as a boolean host array of shape ``Y.plates``, or None without one."""
+        m = self.Y._mask
+        return None if m is True else np.asarray(m, dtype=bool).reshape(self.Y.plates)
+
+    def get_mask(self, node):
+        """``Y``: its mask; ``Z``: any step of the chain observed; every other node: True."""
+        m = self._host_mask()
+        if m is None:
+            return np.array(True)
+        if node is self.Y or node is self.Zc:
+            return m.copy()
+        if node is self.Z:
+            return np.asarray(m.any(axis=-1))
+        return np.array(True)
+
     # -- persistence -----------------------------------------------------------------------------------
     _SAVED_BOTH = ('alpha_a0', 'elog_a0', 'alpha_A', 'elog_A', 'used_a0', 'used_A', 'z0sum',
                    'xisum', 'scal', 'bnd')
@@ -537,6 +600,8 @@ class HMMPlan:
                                       1 if self._with_emissions else 0], dtype=np.int64))
         if self.labels is not None:
             put(base + 'labels', self.labels.cpu().numpy())
+        if self.maskd is not None:
+            put(base + 'mask', self.maskd.cpu().numpy())
         for name in self._SAVED:
             put(base + name, getattr(self, name).cpu().numpy())
 
@@ -551,6 +616,16 @@ class HMMPlan:
         if dims != (self.B, self.T, self.D, self.K, int(self.learned)):
             raise ValueError('checkpoint is for (B, T, D, K, learned emissions) = %s, the model '
                              'has %s' % (dims, (self.B, self.T, self.D, self.K, int(self.learned))))
+        saved = np.asarray(reader.get(base + 'mask'), dtype=np.uint8).reshape(-1) \
+            if reader.has(base + 'mask') else None
+        mine = None if self.maskd is None else self.maskd.cpu().numpy().reshape(-1)
+        if (saved is None) != (mine is None) or (saved is not None
+                                                 and not np.array_equal(saved != 0, mine != 0)):
+            raise ValueError('checkpoint was saved with %s, the model has %s: observe Y with the '
+                             'mask of the checkpoint before loading it'
+                             % tuple('no mask on Y' if m is None else
+                                     'a mask on Y with %d of %d steps observed'
+                                     % (int(np.count_nonzero(m)), m.size) for m in (saved, mine)))
         torch = self.rt.torch
         self._delta = _delta.load(reader, base)
         flags = np.asarray(reader.get(base + 'flags')).ravel()

@@ -972,7 +972,17 @@ int32_t vmp_bmm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, const uint64
  *     logits are all -inf gives NaN, as in the reference.  B = 0 gives zeros.  The shape is judged
  *     before the pointers: T < 2 or a negative size: VMP_ERR_INVALID; K or D above the limits:
  *     VMP_ERR_UNSUPPORTED; then ldc below the number of features or a null argument:
- *     VMP_ERR_INVALID.  Nothing is launched after a refusal. */
+ *     VMP_ERR_INVALID.  Nothing is launched after a refusal.
+ *   vmp_hmm_fused_pass_masked: the same pass with missing observations.  mask (B x T bytes,
+ *     1 = observed) or NULL, which is vmp_hmm_fused_pass.  A masked step has e_t = 0 (a zero
+ *     message to Z) and adds nothing to Tstat or scal[1]; it stays a step of the chain, so
+ *     trailing masked steps propagate through elog_A and their xi counts.  Y at a masked step is
+ *     never read: NaN may stand there.  A chain without an observed step adds nothing to z0sum,
+ *     xisum, scal[0] or scal[1]; its gamma, z0 and zz are what the recursion gives with e = 0
+ *     throughout.  With `labels` the one-hot sums of Tstat run over the observed steps, and z0sum
+ *     and xisum skip the chains without one.  A mask of ones gives the bits of
+ *     vmp_hmm_fused_pass.  The same limits (64, 8), the same workspace, the same checks in the
+ *     same order; no atomics. */
 int32_t vmp_hmm_fused_limits(int32_t *max_K, int32_t *max_D);
 int32_t vmp_hmm_fused_plan(int64_t B, int32_t T, int32_t D, int32_t K, int64_t *chains_per_wg,
                            int64_t *workspace_doubles);
@@ -981,6 +991,12 @@ int32_t vmp_hmm_fused_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_
                            const double *elog_A, const int32_t *labels, double *ws,
                            double *z0sum, double *xisum, double *Tstat, double *scal,
                            double *gamma, double *z0, double *zz);
+int32_t vmp_hmm_fused_pass_masked(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t K,
+                                  const double *Y, const double *C, int32_t ldc,
+                                  const double *elog_a0, const double *elog_A,
+                                  const int32_t *labels, const uint8_t *mask, double *ws,
+                                  double *z0sum, double *xisum, double *Tstat, double *scal,
+                                  double *gamma, double *z0, double *zz);
 
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",

@@ -1,0 +1,232 @@
+// TEST DOUBLE: the masked chain pass of csrc/vmp_hmm_fused.hip (vmp_hmm_fused_pass_masked) on the
+// host, built with g++ from the very header the kernels include (csrc/vmp_hmm_fused_dev.h), in the
+// manner of hmm_fused_host.cpp: workgroups one after the other, a workgroup's chains by lane group,
+// the lanes of a chain as an array reduced by the header's butterflies.  mask (B x T bytes, 1 =
+// observed) or null.  A masked step has e = 0, adds nothing to the feature sums or to
+// sum gamma . e, and its y is never read; a chain without an observed step has weight 0 in
+// sum gamma_0, sum xi and sum log Z -- the header's section MASKS.
+#include <math.h>
+#include <stdint.h>
+#include <vector>
+
+#define __host__
+#define __device__
+#include "../../bayespy_amd/csrc/vmp_hmm_fused_dev.h"
+
+namespace {
+
+double group_lse_parts(const double *q, int KP, double *M)
+{
+    double v[VMP_HMMF_MAX_K];
+    for (int j = 0; j < KP; ++j) v[j] = q[j];
+    vmp_hmmf_group_max_host(v, KP);
+    *M = v[0];
+    for (int j = 0; j < KP; ++j) v[j] = vmp_hmmf_exp_shift(q[j], *M);
+    vmp_hmmf_group_sum_host(v, KP);
+    return v[0];
+}
+
+void softmax(const double *g, int KP, double *out)
+{
+    double M;
+    const double S = group_lse_parts(g, KP, &M);
+    for (int j = 0; j < KP; ++j) out[j] = vmp_hmmf_exp_shift(g[j], M) / S;
+}
+
+}  // namespace
+
+extern "C" {
+
+// z0sum (K), xisum (K x K), Tstat (K x FS), scal[0] = sum log Z, scal[1] = sum gamma . e;
+// gamma (B T K), z0 (B K), zz (B (T-1) K K) or null
+void hmmf_pass_masked(int64_t B, int T, int D, int K, const double *Y, const double *C, int ldc,
+                      const double *la0, const double *lA, const int32_t *labels,
+                      const uint8_t *mask, double *z0sum, double *xisum, double *Tstat,
+                      double *scal, double *gamma_out, double *z0_out, double *zz_out)
+{
+    const int KP = vmp_hmmf_kpad(K), G = 64 / KP, NF = vmp_hmmf_nfeat(D), FS = 1 + D + D * D;
+    const int64_t cpw = vmp_hmmf_chains_per_wg(B, D, K), nw = vmp_hmmf_wgs(B, D, K);
+    const int64_t per = vmp_hmmf_partial_doubles(D, K);
+    std::vector<double> part((size_t)(nw * per), 0.0);
+    std::vector<double> As(KP * KP, -INFINITY), ATs(KP * KP, -INFINITY), Cs(NF * KP, 0.0);
+    for (int i = 0; i < K; ++i)
+        for (int j = 0; j < K; ++j) As[i * KP + j] = ATs[j * KP + i] = lA[i * K + j];
+    if (C)
+        for (int f = 0; f < NF; ++f)
+            for (int j = 0; j < K; ++j) Cs[f * KP + j] = C[(int64_t)j * ldc + f];
+    std::vector<int> fa(NF), fb(NF);
+    for (int f = 0; f < NF; ++f) vmp_hmmf_feature(D, f, &fa[f], &fb[f]);
+    std::vector<double> la((size_t)T * KP);
+    double phi[VMP_HMMF_MAX_NF], yy[VMP_HMMF_MAX_D + 1], e[VMP_HMMF_MAX_K], q[VMP_HMMF_MAX_K];
+    double lb[VMP_HMMF_MAX_K], gl[VMP_HMMF_MAX_K], gam[VMP_HMMF_MAX_K], u[VMP_HMMF_MAX_K];
+    double p[VMP_HMMF_MAX_K], gw[VMP_HMMF_MAX_K];
+
+    for (int64_t wg = 0; wg < nw; ++wg) {
+        const int64_t cb = wg * cpw, ce = cb + cpw < B ? cb + cpw : B;
+        std::vector<double> xi((size_t)G * KP * KP, 0.0), facc((size_t)G * KP * NF, 0.0);
+        std::vector<double> z0a(G * KP, 0.0), ge(G * KP, 0.0), lz(G, 0.0);
+        for (int64_t c = cb; c < ce; ++c) {
+            const int g = (int)((c - cb) % G);
+            double *xg = xi.data() + (size_t)g * KP * KP;          // [i * KP + j]
+            double *fg = facc.data() + (size_t)g * KP * NF;         // [j * NF + f]
+            const double *Yc = Y + c * (int64_t)T * D;
+            const uint8_t *mrow = mask ? mask + c * (int64_t)T : nullptr;
+            const double w = (!mask || vmp_hmmf_chain_observed(mrow, T)) ? 1.0 : 0.0;
+            bool o = true;                                  // of the step of the last features()
+            auto features = [&](int t) {
+                o = !mask || mrow[t] != 0;
+                for (int d = 0; d < D; ++d) yy[d] = o ? Yc[(int64_t)t * D + d] : 0.0;
+                yy[D] = 1.0;
+                for (int f = 0; f < NF; ++f) phi[f] = yy[fa[f]] * yy[fb[f]];
+                for (int j = 0; j < KP; ++j)
+                    e[j] = vmp_hmmf_observed_or_zero(
+                        o, C ? vmp_hmmf_emit(Cs.data() + j, KP, phi, NF) : 0.0);
+            };
+            // gm holds gamma * w, as in the kernel
+            auto accumulate = [&](const double *gm, bool with_e) {
+                if (!o) return;
+                for (int j = 0; j < KP; ++j) {
+                    if (with_e && gm[j] != 0.0) ge[g * KP + j] += gm[j] * e[j];
+                    for (int f = 0; f < NF; ++f) fg[j * NF + f] += gm[j] * phi[f];
+                }
+            };
+            if (labels) {
+                int prev = -1;
+                for (int t = 0; t < T; ++t) {
+                    const int cur = labels[c * T + t];
+                    features(t);
+                    for (int j = 0; j < KP; ++j) gam[j] = j == cur ? 1.0 : 0.0;
+                    for (int j = 0; j < KP; ++j) gw[j] = gam[j] * w;
+                    accumulate(gw, false);
+                    for (int j = 0; j < K; ++j) {
+                        if (t == 0) {
+                            z0a[g * KP + j] += gam[j] * w;
+                            if (z0_out) z0_out[c * K + j] = gam[j];
+                        } else {
+                            for (int i = 0; i < K; ++i) {
+                                const double x = i == prev ? gam[j] : 0.0;
+                                xg[i * KP + j] += x * w;
+                                if (zz_out)
+                                    zz_out[((c * (int64_t)(T - 1) + t - 1) * K + i) * K + j] = x;
+                            }
+                        }
+                        if (gamma_out) gamma_out[(c * (int64_t)T + t) * K + j] = gam[j];
+                    }
+                    prev = cur;
+                }
+                continue;
+            }
+            // forward
+            features(0);
+            for (int j = 0; j < KP; ++j) la[j] = j < K ? la0[j] + e[j] : -INFINITY;
+            for (int n = 1; n < T; ++n) {
+                features(n);
+                const double *v = la.data() + (size_t)(n - 1) * KP;
+                for (int j = 0; j < KP; ++j) {
+                    double m, s;
+                    vmp_hmmf_column(v, As.data() + j, KP, K, &m, &s);
+                    q[j] = j < K ? m + log(s) + e[j] : -INFINITY;
+                }
+                double M;
+                const double S = group_lse_parts(q, KP, &M);
+                const double cn = M + log(S);
+                lz[g] += cn * w;
+                for (int j = 0; j < KP; ++j) la[(size_t)n * KP + j] = q[j] - cn;
+            }
+            // backward
+            for (int j = 0; j < KP; ++j) lb[j] = 0.0;
+            for (int n = T - 2; n >= 0; --n) {
+                features(n + 1);
+                const double *lnext = la.data() + (size_t)(n + 1) * KP;
+                const double *v = la.data() + (size_t)n * KP;
+                for (int j = 0; j < KP; ++j) {
+                    gl[j] = j < K ? lnext[j] + lb[j] : -INFINITY;
+                    u[j] = j < K ? e[j] + lb[j] : -INFINITY;
+                }
+                softmax(gl, KP, gam);
+                for (int j = 0; j < KP; ++j) {
+                    double m = -INFINITY, s = 0.0;
+                    for (int i = 0; i < KP; ++i) m = fmax(m, v[i] + As[i * KP + j]);
+                    for (int i = 0; i < KP; ++i) {
+                        p[i] = vmp_hmmf_exp_shift(v[i] + As[i * KP + j], m);
+                        s += p[i];
+                    }
+                    const double r = vmp_hmmf_ratio(gam[j], s);
+                    for (int i = 0; i < KP; ++i) {
+                        const double x = p[i] * r;
+                        xg[i * KP + j] += x * w;
+                        if (zz_out && i < K && j < K)
+                            zz_out[((c * (int64_t)(T - 1) + n) * K + i) * K + j] = x;
+                    }
+                    if (gamma_out && j < K) gamma_out[(c * (int64_t)T + n + 1) * K + j] = gam[j];
+                }
+                for (int j = 0; j < KP; ++j) gw[j] = gam[j] * w;
+                accumulate(gw, true);
+                double lbn[VMP_HMMF_MAX_K], mx[VMP_HMMF_MAX_K];
+                for (int i = 0; i < KP; ++i) {
+                    double mr, sr;
+                    vmp_hmmf_column(u, ATs.data() + i, KP, K, &mr, &sr);
+                    lbn[i] = i < K ? mr + log(sr) : -INFINITY;
+                    mx[i] = lbn[i];
+                }
+                vmp_hmmf_group_max_host(mx, KP);
+                for (int i = 0; i < KP; ++i) lb[i] = lbn[i] - mx[0];
+            }
+            features(0);
+            for (int j = 0; j < KP; ++j) gl[j] = j < K ? la[j] + lb[j] : -INFINITY;
+            softmax(gl, KP, gam);
+            for (int j = 0; j < KP; ++j) gw[j] = gam[j] * w;
+            accumulate(gw, true);
+            for (int j = 0; j < K; ++j) {
+                z0a[g * KP + j] += gam[j] * w;
+                if (gamma_out) gamma_out[c * (int64_t)T * K + j] = gam[j];
+                if (z0_out) z0_out[c * K + j] = gam[j];
+            }
+        }
+        double *pt = part.data() + wg * per;
+        for (int j = 0; j < K; ++j) {
+            double t = z0a[j];
+            for (int g = 1; g < G; ++g) t += z0a[g * KP + j];
+            pt[j] = t;
+            for (int i = 0; i < K; ++i) {
+                double x = xi[i * KP + j];
+                for (int g = 1; g < G; ++g) x += xi[(size_t)g * KP * KP + i * KP + j];
+                pt[K + i * K + j] = x;
+            }
+            for (int f = 0; f < NF; ++f) {
+                double x = 0.0;
+                for (int g = 0; g < G; ++g) x += facc[(size_t)g * KP * NF + j * NF + f];
+                pt[K + K * K + j * NF + f] = x;
+            }
+        }
+        double zs = 0.0, gs = 0.0;
+        for (int g = 0; g < G; ++g) zs += lz[g];
+        for (int l = 0; l < G * KP; ++l) gs += ge[l];
+        pt[per - 2] = zs;
+        pt[per - 1] = gs;
+    }
+    for (int64_t el = 0; el < per; ++el) {
+        double v = 0.0;
+        for (int64_t w = 0; w < nw; ++w) v += part[w * per + el];
+        if (el < K) {
+            z0sum[el] = v;
+        } else if (el < K + (int64_t)K * K) {
+            xisum[el - K] = v;
+        } else if (el < per - 2) {
+            const int r = (int)(el - K - (int64_t)K * K), k = r / NF, f = r - k * NF;
+            double *Tk = Tstat + (int64_t)k * FS;
+            if (fb[f] < D) {
+                Tk[1 + D + fa[f] * D + fb[f]] = v;
+                Tk[1 + D + fb[f] * D + fa[f]] = v;
+            } else if (fa[f] < D) {
+                Tk[1 + fa[f]] = v;
+            } else {
+                Tk[0] = v;
+            }
+        } else {
+            scal[el - (per - 2)] = v;
+        }
+    }
+}
+
+}  // extern "C"

@@ -11,8 +11,15 @@ tests/hmm_models.py, Z from fixed random labels):
   generic  ms per ``Q.update()`` of the same script with engine='generic' (the yardstick: logP and
            zz of shape (B, T-1, K, K), 10 GB each).
 
+  masked   (with --observed and / or --ragged) ``vmp_hmm_fused_pass_masked`` on the same state
+           after ``Y.observe(y, mask=m)``: one line per mask -- a fraction of the steps observed at
+           random (1.0 is a mask of ones), or sequence lengths uniform in 1 ... T as trailing masks;
+           NaN stands at the masked positions.  Without --out these lines (and the unmasked pass
+           of the same build before them) go to profiles/hmm_fused/bench_hmm_masked.json.
+
     python tools/bench_hmm_fused.py [--legs fused,pass,generic] [--B 20000] [--T 1000] [--steps 5]
                                     [--warmup 2] [--out profiles/...json]
+    python tools/bench_hmm_fused.py --legs pass --observed 1.0,0.7 --ragged
 
 Every leg warms up, then times ``steps`` calls one by one between device synchronisations and
 reports the median and the extremes.
@@ -77,6 +84,10 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--observed', default=None,
+                    help='comma-separated fractions of observed steps for the masked pass')
+    ap.add_argument('--ragged', action='store_true',
+                    help='masked pass with sequence lengths uniform in 1 ... T')
     a = ap.parse_args()
     import torch
     B, T, D, K = a.B, a.T, a.D, a.K
@@ -90,6 +101,13 @@ def main():
         print(lines[-1], flush=True)
 
     legs = a.legs.split(',')
+    masks = [('observed %g' % float(f), float(f)) for f in (a.observed or '').split(',') if f]
+    if a.ragged:
+        masks.append(('ragged', None))
+    if masks and 'pass' not in legs:
+        legs.append('pass')
+    if masks and a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'hmm_fused', 'bench_hmm_masked.json')
     if 'fused' in legs or 'pass' in legs:
         Q = build(y, mu, z0, 'fused')
         plan = Q.plans[0]
@@ -108,6 +126,20 @@ def main():
                       GB_per_s=steps_total * (16 * D + 16 * K) / s / 1e9,
                       exp_per_chain_step=(3 * K + 2) * K,
                       Gexp_per_s=steps_total * (3 * K + 2) * K / s / 1e9, **r))
+        rs = np.random.RandomState(1)
+        for name, frac in masks:
+            if frac is None:
+                m = np.arange(T)[None, :] < rs.randint(1, T + 1, size=B)[:, None]
+            else:
+                m = rs.rand(B, T) < frac
+            plan.Y.observe(np.where(m[..., None], y, np.nan), mask=m)
+            assert plan.Y._plan is plan and plan.has_state()     # the posteriors stay
+            plan._materialize()
+            assert plan.maskd is not None
+            r = timed(lambda: plan._run_pass(refresh=False), a.steps, a.warmup)
+            emit(dict(leg='pass_masked', what='vmp_hmm_fused_pass_masked', mask=name,
+                      observed_fraction=float(m.mean()),
+                      chains_without_observation=int((~m.any(axis=1)).sum()), **r))
         del Q, plan
         torch.cuda.empty_cache()
     if 'generic' in legs:
