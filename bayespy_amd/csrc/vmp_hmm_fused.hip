@@ -354,6 +354,19 @@ int32_t launch_pass(vmp_ctx *ctx, int64_t nw, const HmmfArgs &a)
     return VMP_OK;
 }
 
+template <bool MASKED>
+int32_t launch_pass_kpad(vmp_ctx *ctx, int64_t nw, const HmmfArgs &a)
+{
+    switch (vmp_hmmf_kpad(a.K)) {
+    case 2: return launch_pass<2, MASKED>(ctx, nw, a);
+    case 4: return launch_pass<4, MASKED>(ctx, nw, a);
+    case 8: return launch_pass<8, MASKED>(ctx, nw, a);
+    case 16: return launch_pass<16, MASKED>(ctx, nw, a);
+    case 32: return launch_pass<32, MASKED>(ctx, nw, a);
+    default: return launch_pass<64, MASKED>(ctx, nw, a);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -399,26 +412,8 @@ int32_t vmp_hmm_fused_pass_masked(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D,
     if (nw > 0) {
         HmmfArgs a = {B, vmp_hmmf_chains_per_wg(B, D, K), T, D, K, NF, ldc, Y, C, elog_a0,
                       elog_A, labels, ws, part, gamma, z0, zz, mask};
-        int32_t rc;
-        if (mask) {
-            switch (vmp_hmmf_kpad(K)) {
-            case 2: rc = launch_pass<2, true>(ctx, nw, a); break;
-            case 4: rc = launch_pass<4, true>(ctx, nw, a); break;
-            case 8: rc = launch_pass<8, true>(ctx, nw, a); break;
-            case 16: rc = launch_pass<16, true>(ctx, nw, a); break;
-            case 32: rc = launch_pass<32, true>(ctx, nw, a); break;
-            default: rc = launch_pass<64, true>(ctx, nw, a); break;
-            }
-        } else {
-            switch (vmp_hmmf_kpad(K)) {
-            case 2: rc = launch_pass<2, false>(ctx, nw, a); break;
-            case 4: rc = launch_pass<4, false>(ctx, nw, a); break;
-            case 8: rc = launch_pass<8, false>(ctx, nw, a); break;
-            case 16: rc = launch_pass<16, false>(ctx, nw, a); break;
-            case 32: rc = launch_pass<32, false>(ctx, nw, a); break;
-            default: rc = launch_pass<64, false>(ctx, nw, a); break;
-            }
-        }
+        const int32_t rc = mask ? launch_pass_kpad<true>(ctx, nw, a)
+                                : launch_pass_kpad<false>(ctx, nw, a);
         if (rc != VMP_OK) return rc;
     }
     hipLaunchKernelGGL(hmmf_combine_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0,

@@ -16,15 +16,7 @@ PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan
 # engine='fused': a block's opt-in form takes the place of its default form
 OPT_IN_FORMS = {LDAPlan: LDASVIPlan}
 # engine='fused': blocks that have no default form (their models run on the generic engine otherwise)
-OPT_IN_TYPES = [BernoulliMixturePlan]
-# More of the same.  This second list exists ONLY because tests/test_bmm_host.py pins the list above
-# by equality and existing tests stay as they are; it carries no other meaning.  New opt-in blocks
-# go here; compile_model reads both through _opt_in_types().
-OPT_IN_CHAIN_TYPES = [HMMPlan]
-
-
-def _opt_in_types():
-    return OPT_IN_TYPES + OPT_IN_CHAIN_TYPES
+OPT_IN_TYPES = [BernoulliMixturePlan, HMMPlan]
 
 
 def _reusable_plans(nodes, engine, options=None):
@@ -48,8 +40,7 @@ def _reusable_plans(nodes, engine, options=None):
         return None
     if engine == 'fused' and any(isinstance(p, GenericPlan) for p in plans):
         return None
-    if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values()
-                                 or type(p) in _opt_in_types()
+    if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values() or type(p) in OPT_IN_TYPES
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -99,7 +90,7 @@ def compile_model(nodes, engine=None, **options):
         plan = GenericPlan(nodes)
         plan._engine_request = 'generic'
         return [plan]
-    types = [OPT_IN_FORMS.get(P, P) for P in PLAN_TYPES] + _opt_in_types() if engine == 'fused' \
+    types = [OPT_IN_FORMS.get(P, P) for P in PLAN_TYPES] + OPT_IN_TYPES if engine == 'fused' \
         else PLAN_TYPES
     remaining = [n for n in nodes]
     plans = []

@@ -1,0 +1,27 @@
+"""
+What the blocks with Dirichlet tables (LDA, Bernoulli mixture, HMM) share: the wrappers of
+``vmp_lda_dirichlet`` / ``vmp_lda_dot`` and the host table of a constant concentration.
+"""
+import numpy as np
+
+from ...device import ptr
+
+
+class DirichletKernels:
+    """Mixin of a kernels class that has ``rt``, ``lib`` and ``ctx``."""
+
+    def dirichlet(self, rows, cols, rs, cs, prior, counts, alpha, elog, ws, bound):
+        self.rt.check(self.lib.vmp_lda_dirichlet(
+            self.ctx, rows, cols, rs, cs, ptr(prior), ptr(counts) if counts is not None else None,
+            ptr(alpha), ptr(elog), ptr(ws), ptr(bound)))
+
+    def dot(self, m, a, b, ws, out):
+        self.rt.check(self.lib.vmp_lda_dot(self.ctx, m, ptr(a), ptr(b), ptr(ws), ptr(out)))
+
+
+def prior_table(node, shape):
+    """The constant concentration of the Dirichlet / Beta ``node``, broadcast to ``shape``."""
+    a = np.asarray(node.parents[0].value, dtype=np.float64)
+    if np.any(a <= 0):
+        raise ValueError("Natural parameters should be positive")
+    return np.ascontiguousarray(np.broadcast_to(a, shape))

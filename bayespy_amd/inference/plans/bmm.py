@@ -26,6 +26,7 @@ import ctypes
 import numpy as np
 
 from . import _delta
+from ._dirichlet import DirichletKernels, prior_table
 
 from ... import _lib
 from ...device import get_runtime, ptr
@@ -42,7 +43,7 @@ BMM_MAX_D = 1024
 _DTYPES = {'float64': 0, 'int64': 1, 'bool': 2, 'uint8': 2}
 
 
-class BMMKernels:
+class BMMKernels(DirichletKernels):
 
     def __init__(self, rt):
         self.rt, self.lib, self.ctx = rt, rt.lib, rt.ctx
@@ -69,14 +70,6 @@ class BMMKernels:
             return ptr(t) if t is not None else None
         self.rt.check(self.lib.vmp_bmm_pass(self.ctx, N, D, K, p(xw), p(labels), p(w), p(c), p(ws),
                                             p(S), p(Nk), p(counts), p(scal), p(r_out)))
-
-    def dirichlet(self, rows, cols, rs, cs, prior, counts, alpha, elog, ws, bound):
-        self.rt.check(self.lib.vmp_lda_dirichlet(
-            self.ctx, rows, cols, rs, cs, ptr(prior), ptr(counts) if counts is not None else None,
-            ptr(alpha), ptr(elog), ptr(ws), ptr(bound)))
-
-    def dot(self, m, a, b, ws, out):
-        self.rt.check(self.lib.vmp_lda_dot(self.ctx, m, ptr(a), ptr(b), ptr(ws), ptr(out)))
 
 
 def _match(nodes, why):
@@ -230,13 +223,6 @@ class BernoulliMixturePlan:
             raise ValueError("Invalid count")
         self._x_stale = False
 
-    @staticmethod
-    def _prior(node, shape):
-        a = np.asarray(node.parents[0].value, dtype=np.float64)
-        if np.any(a <= 0):
-            raise ValueError("Natural parameters should be positive")
-        return np.ascontiguousarray(np.broadcast_to(a, shape))
-
     def _materialize(self):
         if self._ready:
             if self._x_stale:
@@ -251,8 +237,8 @@ class BernoulliMixturePlan:
         self.chunk, wsd = k.plan(N, D, K)
         self._pack()
         up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(rt.device)  # noqa: E731
-        pp = self._prior(self.P, (D, K, 2)).reshape(D * K, 2)
-        pr = self._prior(self.R, (K,))
+        pp = prior_table(self.P, (D, K, 2)).reshape(D * K, 2)
+        pr = prior_table(self.R, (K,))
         self.prior_p, self.prior_r = up(pp), up(pr)
         self.alpha_p, self.elog_p = rt.empty(D * K, 2), rt.empty(D * K, 2)
         self.alpha_r, self.elog_r = rt.empty(K), rt.empty(K)

@@ -45,6 +45,7 @@ import ctypes
 import numpy as np
 
 from . import _delta
+from ._dirichlet import DirichletKernels, prior_table
 
 from ... import _lib
 from ...device import get_runtime, ptr
@@ -101,7 +102,7 @@ def emission_tables(mu, Lam):
     return C, Cn
 
 
-class HMMKernels:
+class HMMKernels(DirichletKernels):
 
     def __init__(self, rt):
         self.rt, self.lib, self.ctx = rt, rt.lib, rt.ctx
@@ -117,29 +118,16 @@ class HMMKernels:
         return c.value, w.value
 
     def pass_(self, B, T, D, K, Y, C, ldc, elog_a0, elog_A, labels, ws, z0sum, xisum, Tstat, scal,
-              gamma=None, z0=None, zz=None):
+              gamma=None, z0=None, zz=None, mask=None):
+        """``mask``: (B, T) uint8, 1 = observed; with one the pass is ``vmp_hmm_fused_pass_masked``."""
         def p(t):
             return ptr(t) if t is not None else None
-        self.rt.check(self.lib.vmp_hmm_fused_pass(
-            self.ctx, B, T, D, K, p(Y), p(C), ldc, p(elog_a0), p(elog_A), p(labels), p(ws),
-            p(z0sum), p(xisum), p(Tstat), p(scal), p(gamma), p(z0), p(zz)))
-
-    def pass_masked(self, B, T, D, K, Y, C, ldc, elog_a0, elog_A, labels, mask, ws, z0sum, xisum,
-                    Tstat, scal, gamma=None, z0=None, zz=None):
-        """``pass_`` with ``mask`` (B, T) uint8, 1 = observed."""
-        def p(t):
-            return ptr(t) if t is not None else None
-        self.rt.check(self.lib.vmp_hmm_fused_pass_masked(
-            self.ctx, B, T, D, K, p(Y), p(C), ldc, p(elog_a0), p(elog_A), p(labels), p(mask), p(ws),
-            p(z0sum), p(xisum), p(Tstat), p(scal), p(gamma), p(z0), p(zz)))
-
-    def dirichlet(self, rows, cols, rs, cs, prior, counts, alpha, elog, ws, bound):
-        self.rt.check(self.lib.vmp_lda_dirichlet(
-            self.ctx, rows, cols, rs, cs, ptr(prior), ptr(counts) if counts is not None else None,
-            ptr(alpha), ptr(elog), ptr(ws), ptr(bound)))
-
-    def dot(self, m, a, b, ws, out):
-        self.rt.check(self.lib.vmp_lda_dot(self.ctx, m, ptr(a), ptr(b), ptr(ws), ptr(out)))
+        head = (self.ctx, B, T, D, K, p(Y), p(C), ldc, p(elog_a0), p(elog_A), p(labels))
+        tail = (p(ws), p(z0sum), p(xisum), p(Tstat), p(scal), p(gamma), p(z0), p(zz))
+        if mask is None:
+            self.rt.check(self.lib.vmp_hmm_fused_pass(*head, *tail))
+        else:
+            self.rt.check(self.lib.vmp_hmm_fused_pass_masked(*head, ptr(mask), *tail))
 
 
 def _mask_shape(mask):
@@ -361,13 +349,6 @@ class HMMPlan:
                 np.asarray(m, dtype=bool).reshape(self.B, self.T).astype(np.uint8))).to(rt.device)
         self._y_stale = False
 
-    @staticmethod
-    def _prior(node, shape):
-        a = np.asarray(node.parents[0].value, dtype=np.float64)
-        if np.any(a <= 0):
-            raise ValueError("Natural parameters should be positive")
-        return np.ascontiguousarray(np.broadcast_to(a, shape))
-
     def _labels(self, lab):
         lab = np.asarray(lab)
         if lab.dtype.kind == 'f':
@@ -412,7 +393,7 @@ class HMMPlan:
                                     np.asarray(self.Y.parents[2].value, dtype=np.float64))
             self.C, self.Cn, self.ldc = up(C), up(Cn), C.shape[1]
             self.Tstat = rt.zeros(K, self.FS)
-        self.prior_a0, self.prior_A = up(self._prior(self.a0, (K,))), up(self._prior(self.A, (K, K)))
+        self.prior_a0, self.prior_A = up(prior_table(self.a0, (K,))), up(prior_table(self.A, (K, K)))
         self.alpha_a0, self.elog_a0 = rt.empty(K), rt.empty(K)
         self.alpha_A, self.elog_A = rt.empty(K, K), rt.empty(K, K)
         self.used_a0, self.used_A = rt.empty(K), rt.empty(K, K)
@@ -449,14 +430,9 @@ class HMMPlan:
             self.used_a0.copy_(self.elog_a0)
             self.used_A.copy_(self.elog_A)
         C = self.C if self._with_emissions else None
-        if self.maskd is None:
-            self.kernels.pass_(self.B, self.T, self.D, self.K, self.Yd, C, self.ldc, self.used_a0,
-                               self.used_A, self.labels, self.ws, self.z0sum, self.xisum,
-                               self.Tstat, self.scal, gamma, z0, zz)
-        else:
-            self.kernels.pass_masked(self.B, self.T, self.D, self.K, self.Yd, C, self.ldc,
-                                     self.used_a0, self.used_A, self.labels, self.maskd, self.ws,
-                                     self.z0sum, self.xisum, self.Tstat, self.scal, gamma, z0, zz)
+        self.kernels.pass_(self.B, self.T, self.D, self.K, self.Yd, C, self.ldc, self.used_a0,
+                           self.used_A, self.labels, self.ws, self.z0sum, self.xisum, self.Tstat,
+                           self.scal, gamma, z0, zz, mask=self.maskd)
         if refresh or gamma is None:
             self._version += 1              # writing gamma / z0 / zz out changes no sum
 

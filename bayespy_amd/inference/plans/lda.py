@@ -22,6 +22,7 @@ import ctypes
 import numpy as np
 
 from . import _delta
+from ._dirichlet import DirichletKernels, prior_table
 
 from ... import _lib
 from ...device import get_runtime, ptr
@@ -33,7 +34,7 @@ from ...nodes.take import Gate
 LDA_MAX_K = 64          # vmp_lda_limits
 
 
-class LDAKernels:
+class LDAKernels(DirichletKernels):
 
     def __init__(self, rt):
         self.rt, self.lib, self.ctx = rt, rt.lib, rt.ctx
@@ -57,11 +58,6 @@ class LDAKernels:
             p(elog_theta), p(elog_beta_t), phases, p(lse), p(ws), p(Ndk), p(Nvk), p(scal),
             p(orig), p(phi)))
 
-    def dirichlet(self, rows, cols, rs, cs, prior, counts, alpha, elog, ws, bound):
-        self.rt.check(self.lib.vmp_lda_dirichlet(
-            self.ctx, rows, cols, rs, cs, ptr(prior), ptr(counts) if counts is not None else None,
-            ptr(alpha), ptr(elog), ptr(ws), ptr(bound)))
-
     def dirichlet_step_ws(self, rows, cols, rs, cs):
         """Doubles of the workspace of ``dirichlet_step`` for this table."""
         w = ctypes.c_int64()
@@ -75,9 +71,6 @@ class LDAKernels:
         self.rt.check(self.lib.vmp_lda_dirichlet_step(
             self.ctx, rows, cols, rs, cs, ptr(prior), ptr(counts) if counts is not None else None,
             float(mult), float(scale), ptr(alpha), ptr(elog), ptr(ws), ptr(bound)))
-
-    def dot(self, m, a, b, ws, out):
-        self.rt.check(self.lib.vmp_lda_dot(self.ctx, m, ptr(a), ptr(b), ptr(ws), ptr(out)))
 
 
 def _structure(words):
@@ -330,12 +323,6 @@ class LDAPlan:
         self.orig = order.to(i32)
         self._layout_stale = False
 
-    def _prior(self, node, rows, cols):
-        a = np.asarray(node.parents[0].value, dtype=np.float64)
-        if np.any(a <= 0):
-            raise ValueError("Natural parameters should be positive")
-        return np.ascontiguousarray(np.broadcast_to(a, (rows, cols)))
-
     def _init_dirichlet(self, node, prior):
         """Initial <log> table of a Dirichlet: from the prior (device), or the log of a value /
         of a draw from the prior (host, set-up only)."""
@@ -365,8 +352,8 @@ class LDAPlan:
         rt.sync_stream()
         self.group, self.chunk, wsd = k.plan(n, K)
         self._build_layouts()
-        pt = self._prior(self.p_topic, D, K)
-        pw = self._prior(self.p_word, K, V)
+        pt = prior_table(self.p_topic, (D, K))
+        pw = prior_table(self.p_word, (K, V))
         up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(rt.device)  # noqa: E731
         self.prior_theta, self.prior_beta_t = up(pt), up(pw.T)
         self.alpha_theta, self.alpha_beta_t = rt.empty(D, K), rt.empty(V, K)

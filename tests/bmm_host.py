@@ -9,38 +9,19 @@
   products in NumPy / SciPy (tests/lda_host.py).
 It lives under tests/ and is never imported by the product."""
 import ctypes
-import hashlib
-import os
-import subprocess
-import tempfile
+import functools
 
 import numpy as np
 
-from lda_host import dirichlet_rows
+from host_build import build_host_library
+from lda_host import CPUDirichletKernels
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'bayespy_amd', 'csrc')
-_LIB = []
 DTYPES = {'float64': 0, 'int64': 1, 'bool': 2, 'uint8': 2}
 
 
+@functools.lru_cache(None)
 def bmm_host():
-    if _LIB:
-        return _LIB[0]
-    srcs = [os.path.join(ROOT, 'tests', 'host', 'bmm_host.cpp'), os.path.join(CSRC, 'vmp_bmm_dev.h')]
-    h = hashlib.sha256()
-    for p in srcs:
-        with open(p, 'rb') as f:
-            h.update(f.read())
-    d = os.path.join(tempfile.gettempdir(), 'bayespy_amd_bmm_%s' % h.hexdigest()[:16])
-    so = os.path.join(d, 'libbmm_host.so')
-    if not os.path.exists(so):
-        os.makedirs(d, exist_ok=True)
-        tmp = so + '.%d.tmp' % os.getpid()
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-ffp-contract=off',
-                               srcs[0], '-o', tmp])
-        os.replace(tmp, so)
-    lib = ctypes.CDLL(so)
+    lib = build_host_library('bmm', ['tests/host/bmm_host.cpp', 'bayespy_amd/csrc/vmp_bmm_dev.h'])
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
     lib.bmm_kpad.argtypes = [i32]
     lib.bmm_words.argtypes = [i32]
@@ -56,7 +37,6 @@ def bmm_host():
     lib.bmm_tables.restype = None
     lib.bmm_pass.argtypes = [i64, i32, i32] + [vp] * 9
     lib.bmm_pass.restype = None
-    _LIB.append(lib)
     return lib
 
 
@@ -112,7 +92,7 @@ def restate(x, w, c, dtype=np.longdouble):
                 S_w=np.sum(S * w))
 
 
-class CPUBMMKernels:
+class CPUBMMKernels(CPUDirichletKernels):
     """Double of BMMKernels on CPU tensors; ``calls`` lists the entry points in call order."""
 
     def __init__(self, rt):
@@ -154,18 +134,3 @@ class CPUBMMKernels:
         scal.numpy()[:3] = [sl, float(np.sum(n * c.numpy())), float(np.sum(s * w.numpy()))]
         if r_out is not None:
             r_out.numpy()[...] = r
-
-    def dirichlet(self, rows, cols, rs, cs, prior, counts, alpha, elog, ws, bound):
-        self.calls.append('dirichlet')
-
-        def view(t):
-            return np.lib.stride_tricks.as_strided(t.numpy().reshape(-1), shape=(rows, cols),
-                                                   strides=(8 * rs, 8 * cs))
-        al, el, b = dirichlet_rows(view(prior), None if counts is None else view(counts))
-        view(alpha)[...] = al
-        view(elog)[...] = el
-        bound.numpy()[...] = b
-
-    def dot(self, m, a, b, ws, out):
-        self.calls.append('dot')
-        out.numpy()[...] = float(np.sum(a.numpy().reshape(-1)[:m] * b.numpy().reshape(-1)[:m]))

@@ -9,35 +9,18 @@
   engine runs models with such chains on a CPU.
 It lives under tests/ and is never imported by the product."""
 import ctypes
-import hashlib
-import os
-import subprocess
-import tempfile
+import functools
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'bayespy_amd', 'csrc')
-_LIB = []
+from host_build import build_host_library
 
 
+
+@functools.lru_cache(None)
 def chain_tv_host():
-    if _LIB:
-        return _LIB[0]
-    srcs = [os.path.join(ROOT, 'tests', 'host', 'chain_tv_host.cpp'),
-            os.path.join(CSRC, 'vmp_chain_tv_dev.h')]
-    h = hashlib.sha256()
-    for p in srcs:
-        h.update(open(p, 'rb').read())
-    d = os.path.join(tempfile.gettempdir(), 'bayespy_amd_chain_tv_%s' % h.hexdigest()[:16])
-    so = os.path.join(d, 'libchain_tv_host.so')
-    if not os.path.exists(so):
-        os.makedirs(d, exist_ok=True)
-        tmp = so + '.%d.tmp' % os.getpid()
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-ffp-contract=off',
-                               srcs[0], '-o', tmp])
-        os.replace(tmp, so)
-    lib = ctypes.CDLL(so)
+    lib = build_host_library('chain_tv', ['tests/host/chain_tv_host.cpp',
+                                          'bayespy_amd/csrc/vmp_chain_tv_dev.h'])
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
     lib.chain_tv_max_d.restype = i32
     lib.chain_tv_work_doubles.argtypes = [i64, i32, i32]
@@ -46,7 +29,6 @@ def chain_tv_host():
     lib.chain_tv_nslice.restype = i64
     lib.chain_tv_pair_stats.argtypes = [i64, i32, i32, vp, vp, vp, vp, i64]
     lib.chain_tv_pair_stats.restype = i32
-    _LIB.append(lib)
     return lib
 
 

@@ -1,7 +1,10 @@
 // TEST DOUBLE: the chain pass of csrc/vmp_hmm_fused.hip on the host, built with g++ from the very
 // header the kernels include (csrc/vmp_hmm_fused_dev.h).  Workgroups are walked one after the
 // other, a workgroup's chains by lane group, the lanes of a chain as an array reduced by the
-// header's butterflies -- the order of every addition is the one the header states.
+// header's butterflies -- the order of every addition is the one the header states.  mask (B x T
+// bytes, 1 = observed) or null.  A masked step has e = 0, adds nothing to the feature sums or to
+// sum gamma . e, and its y is never read; a chain without an observed step has weight 0 in
+// sum gamma_0, sum xi and sum log Z -- the header's section MASKS.
 #include <math.h>
 #include <stdint.h>
 #include <vector>
@@ -57,9 +60,9 @@ int64_t hmmf_workspace_doubles(int64_t B, int T, int D, int K)
 // z0sum (K), xisum (K x K), Tstat (K x FS), scal[0] = sum log Z, scal[1] = sum gamma . e;
 // gamma (B T K), z0 (B K), zz (B (T-1) K K) or null
 void hmmf_pass(int64_t B, int T, int D, int K, const double *Y, const double *C, int ldc,
-               const double *la0, const double *lA, const int32_t *labels, double *z0sum,
-               double *xisum, double *Tstat, double *scal, double *gamma_out, double *z0_out,
-               double *zz_out)
+               const double *la0, const double *lA, const int32_t *labels, const uint8_t *mask,
+               double *z0sum, double *xisum, double *Tstat, double *scal, double *gamma_out,
+               double *z0_out, double *zz_out)
 {
     const int KP = vmp_hmmf_kpad(K), G = 64 / KP, NF = vmp_hmmf_nfeat(D), FS = 1 + D + D * D;
     const int64_t cpw = vmp_hmmf_chains_per_wg(B, D, K), nw = vmp_hmmf_wgs(B, D, K);
@@ -76,7 +79,7 @@ void hmmf_pass(int64_t B, int T, int D, int K, const double *Y, const double *C,
     std::vector<double> la((size_t)T * KP);
     double phi[VMP_HMMF_MAX_NF], yy[VMP_HMMF_MAX_D + 1], e[VMP_HMMF_MAX_K], q[VMP_HMMF_MAX_K];
     double lb[VMP_HMMF_MAX_K], gl[VMP_HMMF_MAX_K], gam[VMP_HMMF_MAX_K], u[VMP_HMMF_MAX_K];
-    double p[VMP_HMMF_MAX_K];
+    double p[VMP_HMMF_MAX_K], gw[VMP_HMMF_MAX_K];
 
     for (int64_t wg = 0; wg < nw; ++wg) {
         const int64_t cb = wg * cpw, ce = cb + cpw < B ? cb + cpw : B;
@@ -87,14 +90,21 @@ void hmmf_pass(int64_t B, int T, int D, int K, const double *Y, const double *C,
             double *xg = xi.data() + (size_t)g * KP * KP;          // [i * KP + j]
             double *fg = facc.data() + (size_t)g * KP * NF;         // [j * NF + f]
             const double *Yc = Y + c * (int64_t)T * D;
+            const uint8_t *mrow = mask ? mask + c * (int64_t)T : nullptr;
+            const double w = (!mask || vmp_hmmf_chain_observed(mrow, T)) ? 1.0 : 0.0;
+            bool o = true;                                  // of the step of the last features()
             auto features = [&](int t) {
-                for (int d = 0; d < D; ++d) yy[d] = Yc[(int64_t)t * D + d];
+                o = !mask || mrow[t] != 0;
+                for (int d = 0; d < D; ++d) yy[d] = o ? Yc[(int64_t)t * D + d] : 0.0;
                 yy[D] = 1.0;
                 for (int f = 0; f < NF; ++f) phi[f] = yy[fa[f]] * yy[fb[f]];
                 for (int j = 0; j < KP; ++j)
-                    e[j] = C ? vmp_hmmf_emit(Cs.data() + j, KP, phi, NF) : 0.0;
+                    e[j] = vmp_hmmf_observed_or_zero(
+                        o, C ? vmp_hmmf_emit(Cs.data() + j, KP, phi, NF) : 0.0);
             };
+            // gm holds gamma * w, as in the kernel
             auto accumulate = [&](const double *gm, bool with_e) {
+                if (!o) return;
                 for (int j = 0; j < KP; ++j) {
                     if (with_e && gm[j] != 0.0) ge[g * KP + j] += gm[j] * e[j];
                     for (int f = 0; f < NF; ++f) fg[j * NF + f] += gm[j] * phi[f];
@@ -106,15 +116,16 @@ void hmmf_pass(int64_t B, int T, int D, int K, const double *Y, const double *C,
                     const int cur = labels[c * T + t];
                     features(t);
                     for (int j = 0; j < KP; ++j) gam[j] = j == cur ? 1.0 : 0.0;
-                    accumulate(gam, false);
+                    for (int j = 0; j < KP; ++j) gw[j] = gam[j] * w;
+                    accumulate(gw, false);
                     for (int j = 0; j < K; ++j) {
                         if (t == 0) {
-                            z0a[g * KP + j] += gam[j];
+                            z0a[g * KP + j] += gam[j] * w;
                             if (z0_out) z0_out[c * K + j] = gam[j];
                         } else {
                             for (int i = 0; i < K; ++i) {
                                 const double x = i == prev ? gam[j] : 0.0;
-                                xg[i * KP + j] += x;
+                                xg[i * KP + j] += x * w;
                                 if (zz_out)
                                     zz_out[((c * (int64_t)(T - 1) + t - 1) * K + i) * K + j] = x;
                             }
@@ -139,7 +150,7 @@ void hmmf_pass(int64_t B, int T, int D, int K, const double *Y, const double *C,
                 double M;
                 const double S = group_lse_parts(q, KP, &M);
                 const double cn = M + log(S);
-                lz[g] += cn;
+                lz[g] += cn * w;
                 for (int j = 0; j < KP; ++j) la[(size_t)n * KP + j] = q[j] - cn;
             }
             // backward
@@ -163,13 +174,14 @@ void hmmf_pass(int64_t B, int T, int D, int K, const double *Y, const double *C,
                     const double r = vmp_hmmf_ratio(gam[j], s);
                     for (int i = 0; i < KP; ++i) {
                         const double x = p[i] * r;
-                        xg[i * KP + j] += x;
+                        xg[i * KP + j] += x * w;
                         if (zz_out && i < K && j < K)
                             zz_out[((c * (int64_t)(T - 1) + n) * K + i) * K + j] = x;
                     }
                     if (gamma_out && j < K) gamma_out[(c * (int64_t)T + n + 1) * K + j] = gam[j];
                 }
-                accumulate(gam, true);
+                for (int j = 0; j < KP; ++j) gw[j] = gam[j] * w;
+                accumulate(gw, true);
                 double lbn[VMP_HMMF_MAX_K], mx[VMP_HMMF_MAX_K];
                 for (int i = 0; i < KP; ++i) {
                     double mr, sr;
@@ -183,9 +195,10 @@ void hmmf_pass(int64_t B, int T, int D, int K, const double *Y, const double *C,
             features(0);
             for (int j = 0; j < KP; ++j) gl[j] = j < K ? la[j] + lb[j] : -INFINITY;
             softmax(gl, KP, gam);
-            accumulate(gam, true);
+            for (int j = 0; j < KP; ++j) gw[j] = gam[j] * w;
+            accumulate(gw, true);
             for (int j = 0; j < K; ++j) {
-                z0a[g * KP + j] += gam[j];
+                z0a[g * KP + j] += gam[j] * w;
                 if (gamma_out) gamma_out[c * (int64_t)T * K + j] = gam[j];
                 if (z0_out) z0_out[c * K + j] = gam[j];
             }

@@ -8,42 +8,22 @@
   SciPy.
 It lives under tests/ and is never imported by the product."""
 import ctypes
-import hashlib
-import os
-import subprocess
-import tempfile
+import functools
 
 import numpy as np
 from scipy import special
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'bayespy_amd', 'csrc')
-_LIB = []
+from host_build import build_host_library
 
 
+@functools.lru_cache(None)
 def lda_host():
-    if _LIB:
-        return _LIB[0]
-    srcs = [os.path.join(ROOT, 'tests', 'host', 'lda_host.cpp'), os.path.join(CSRC, 'vmp_lda_dev.h')]
-    h = hashlib.sha256()
-    for p in srcs:
-        with open(p, 'rb') as f:
-            h.update(f.read())
-    d = os.path.join(tempfile.gettempdir(), 'bayespy_amd_lda_%s' % h.hexdigest()[:16])
-    so = os.path.join(d, 'liblda_host.so')
-    if not os.path.exists(so):
-        os.makedirs(d, exist_ok=True)
-        tmp = so + '.%d.tmp' % os.getpid()
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-ffp-contract=off',
-                               srcs[0], '-o', tmp])
-        os.replace(tmp, so)
-    lib = ctypes.CDLL(so)
+    lib = build_host_library('lda', ['tests/host/lda_host.cpp', 'bayespy_amd/csrc/vmp_lda_dev.h'])
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
     lib.lda_group.argtypes = [i32]
     lib.lda_chunk_tokens.argtypes = [i64, i32]
     lib.lda_pass.argtypes = [i64, i64, i32] + [vp] * 14
     lib.lda_pass.restype = None
-    _LIB.append(lib)
     return lib
 
 
@@ -114,7 +94,29 @@ def dirichlet_rows(prior, counts):
     return alpha, elog, bound
 
 
-class CPULDAKernels:
+class CPUDirichletKernels:
+    """Mixin of the doubles with Dirichlet tables (LDA, Bernoulli mixture, HMM): ``dirichlet`` and
+    ``dot`` of a kernels double that has ``calls``."""
+
+    def dirichlet(self, rows, cols, rs, cs, prior, counts, alpha, elog, ws, bound):
+        self.calls.append('dirichlet')
+
+        def view(t):
+            # element (r, c) at r * rs + c * cs
+            return np.lib.stride_tricks.as_strided(t.numpy().reshape(-1), shape=(rows, cols),
+                                                   strides=(8 * rs, 8 * cs))
+        al, el, b = dirichlet_rows(view(prior), None if counts is None else view(counts))
+        view(alpha)[...] = al
+        view(elog)[...] = el
+        bound.numpy()[...] = b
+
+    def dot(self, m, a, b, ws, out):
+        self.calls.append('dot')
+        with np.errstate(invalid='ignore'):          # 0 * -inf, as on the device
+            out.numpy()[...] = float(np.sum(a.numpy().reshape(-1)[:m] * b.numpy().reshape(-1)[:m]))
+
+
+class CPULDAKernels(CPUDirichletKernels):
     """Double of LDAKernels on CPU tensors; ``calls`` lists the entry points in call order."""
 
     def __init__(self, rt):
@@ -146,20 +148,3 @@ class CPULDAKernels:
         lse.numpy()[:n] = l
         if phi is not None:
             phi.numpy()[...] = ph
-
-    def dirichlet(self, rows, cols, rs, cs, prior, counts, alpha, elog, ws, bound):
-        self.calls.append('dirichlet')
-
-        def view(t):
-            # element (r, c) at r * rs + c * cs
-            return np.lib.stride_tricks.as_strided(t.numpy().reshape(-1), shape=(rows, cols),
-                                                   strides=(8 * rs, 8 * cs))
-        al, el, b = dirichlet_rows(view(prior), None if counts is None else view(counts))
-        view(alpha)[...] = al
-        view(elog)[...] = el
-        bound.numpy()[...] = b
-
-    def dot(self, m, a, b, ws, out):
-        self.calls.append('dot')
-        with np.errstate(invalid='ignore'):
-            out.numpy()[...] = float(np.sum(a.numpy() * b.numpy()))

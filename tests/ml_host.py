@@ -8,45 +8,23 @@
   entry points of this library, so that the generic engine runs models with these nodes on a CPU.
 It lives under tests/ and is never imported by the product."""
 import ctypes
-import hashlib
-import os
-import subprocess
-import tempfile
+import functools
 
 import numpy as np
 from scipy import special
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'bayespy_amd', 'csrc')
-_LIB = []
+from host_build import build_host_library, special_functions_text
 
 
+
+@functools.lru_cache(None)
 def ml_host():
-    if _LIB:
-        return _LIB[0]
-    srcs = [os.path.join(ROOT, 'tests', 'host', 'ml_host.cpp'), os.path.join(CSRC, 'vmp_ml_dev.h')]
-    from host_build import _special_functions_text
-    sf = _special_functions_text()
-    h = hashlib.sha256(sf.encode())
-    for p in srcs:
-        h.update(open(p, 'rb').read())
-    d = os.path.join(tempfile.gettempdir(), 'bayespy_amd_ml_%s' % h.hexdigest()[:16])
-    so = os.path.join(d, 'libml_host.so')
-    if not os.path.exists(so):
-        os.makedirs(d, exist_ok=True)
-        sfh = os.path.join(d, 'sf.%d.h' % os.getpid())
-        with open(sfh, 'w') as f:
-            f.write(sf)
-        tmp = so + '.%d.tmp' % os.getpid()
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-ffp-contract=off',
-                               '-include', sfh, srcs[0], '-o', tmp])
-        os.replace(tmp, so)
-    lib = ctypes.CDLL(so)
+    lib = build_host_library('ml', ['tests/host/ml_host.cpp', 'bayespy_amd/csrc/vmp_ml_dev.h'],
+                             prelude=special_functions_text())
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
     lib.ml_invpsi.argtypes = [i64, vp, vp]
     lib.ml_gamma_shape.argtypes = [i64, vp, vp, vp, vp, vp, vp]
     lib.ml_concentration.argtypes = [i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    _LIB.append(lib)
     return lib
 
 

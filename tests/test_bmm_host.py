@@ -115,9 +115,10 @@ def test_default_engine_keeps_the_generic_plan():
     from bayespy_amd.inference.plans import compile_model
     from bayespy_amd.inference.plans.generic import GenericPlan
     from bayespy_amd.inference.plans.bmm import BernoulliMixturePlan
+    from bayespy_amd.inference.plans.hmm import HMMPlan
     assert [P.__name__ for P in plans.PLAN_TYPES] == [
         'PCAPlan', 'MaskedPCAPlan', 'GMMPlan', 'LSSMPlan', 'MaskedLSSMPlan', 'LDAPlan']
-    assert plans.OPT_IN_TYPES == [BernoulliMixturePlan]
+    assert plans.OPT_IN_TYPES == [BernoulliMixturePlan, HMMPlan]
     import host_generic
     m = _model()
     host_generic.install()          # the generic engine on the NumPy double of its entry points

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 SUMS = ('z0sum', 'xisum', 'T', 'logZ', 'ge')
 
 
-def gpu_pass(Y, C, la0, lA, labels=None, want=False):
+def gpu_pass(Y, C, la0, lA, labels=None, want=False, mask=None):
     import torch
     from bayespy_amd.device import get_runtime
     from bayespy_amd.inference.plans.hmm import HMMKernels
@@ -40,10 +40,12 @@ def gpu_pass(Y, C, la0, lA, labels=None, want=False):
     zz = rt.empty(B, T - 1, K, K) if want else None
     lab = None if labels is None else torch.from_numpy(
         np.ascontiguousarray(labels, dtype=np.int32)).to(rt.device)
+    md = None if mask is None else torch.from_numpy(
+        np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)).to(rt.device)
     Cd = None if C is None else up(C)
     la0d, lAd = up(la0), up(lA)
     k.pass_(B, T, D, K, up(Y), Cd, 0 if C is None else C.shape[1], la0d, lAd, lab, ws, z0sum,
-            xisum, Ts, scal, g, z0, zz)
+            xisum, Ts, scal, g, z0, zz, mask=md)
     rt.sync_stream()
     s = scal.cpu().numpy()
     out = dict(z0sum=z0sum.cpu().numpy(), xisum=xisum.cpu().numpy(), T=Ts.cpu().numpy(),

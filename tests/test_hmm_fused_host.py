@@ -156,7 +156,7 @@ def test_block_is_opt_in():
     from bayespy_amd.inference.plans import compile_model
     from bayespy_amd.inference.plans.generic import GenericPlan
     from bayespy_amd.inference.plans.hmm import HMMPlan
-    assert HMMPlan not in plans.PLAN_TYPES and HMMPlan in plans.OPT_IN_CHAIN_TYPES
+    assert HMMPlan not in plans.PLAN_TYPES and HMMPlan in plans.OPT_IN_TYPES
     import host_generic
     m = _model()
     host_generic.install()

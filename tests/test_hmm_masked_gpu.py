@@ -1,7 +1,7 @@
 """GPU: masks on the fused hidden-Markov-model block on the real library -- the fixtures of
 tests/golden/hmm_masked.npz and the model of examples/hmm_ragged.py through engine='fused', and
 ``vmp_hmm_fused_pass_masked`` alone against the long-double restatement of the reference arithmetic
-(tests/hmm_masked_host.py ``restate_masked``) at the shapes of tests/test_hmm_fused_gpu.py with three
+(tests/hmm_fused_host.py ``restate``) at the shapes of tests/test_hmm_fused_gpu.py with three
 workgroups, the last one ragged, under one mask that mixes fully observed chains, chains with
 nothing observed, masked first and last steps, ragged tails and holes; a mask of ones against the
 unmasked entry, the values at masked positions, a mask of zeros, fixed labels, the optional outputs,
@@ -25,57 +25,26 @@ SUMS = ('z0sum', 'xisum', 'T', 'logZ', 'ge')
 OUTS = ('gamma', 'z0', 'zz')
 
 
-def gpu_pass_masked(Y, C, la0, lA, mask, labels=None, want=False):
-    import torch
-    from bayespy_amd.device import get_runtime
-    from bayespy_amd.inference.plans.hmm import HMMKernels
-    rt = get_runtime()
-    k = HMMKernels(rt)
-    B, T, D = Y.shape
-    K = len(la0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(rt.device)  # noqa: E731
-    _, wsd = k.plan(B, T, D, K)
-    ws = rt.empty(int(wsd))
-    z0sum, xisum, Ts, scal = rt.zeros(K), rt.zeros(K, K), rt.zeros(K, 1 + D + D * D), rt.zeros(8)
-    g = rt.empty(B, T, K) if want else None
-    z0 = rt.empty(B, K) if want else None
-    zz = rt.empty(B, T - 1, K, K) if want else None
-    lab = None if labels is None else torch.from_numpy(
-        np.ascontiguousarray(labels, dtype=np.int32)).to(rt.device)
-    md = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)).to(rt.device)
-    Cd = None if C is None else up(C)
-    la0d, lAd = up(la0), up(lA)
-    k.pass_masked(B, T, D, K, up(Y), Cd, 0 if C is None else C.shape[1], la0d, lAd, lab, md, ws,
-                  z0sum, xisum, Ts, scal, g, z0, zz)
-    rt.sync_stream()
-    s = scal.cpu().numpy()
-    out = dict(z0sum=z0sum.cpu().numpy(), xisum=xisum.cpu().numpy(), T=Ts.cpu().numpy(),
-               logZ=float(s[0]), ge=float(s[1]), dots=s[2:4].copy())
-    if want:
-        out.update(gamma=g.cpu().numpy(), z0=z0.cpu().numpy(), zz=zz.cpu().numpy())
-    return out
-
-
 def _on_device(Q):
     assert type(Q.plans[0]).__name__ == 'HMMPlan'
 
 
 def test_fixtures_through_the_library():
-    from hmm_masked_models import run_masked_cases
+    from hmm_models import run_hmm_cases
     from test_hmm_masked_host import _mods, _golden, check_masked_fixtures
     g, gin = _golden()
     with warnings.catch_warnings():
         warnings.simplefilter('error')
-        res = run_masked_cases(_mods(_on_device, engine='fused'), gin)
+        res = run_hmm_cases(_mods(_on_device, engine='fused'), gin)
     check_masked_fixtures(res, g)
 
 
 def test_fixtures_with_masks_in_device_memory():
     import torch
-    from hmm_masked_models import run_masked_cases
+    from hmm_models import run_hmm_cases
     from test_hmm_masked_host import _mods, _golden, L_RTOL
     g, gin = _golden()
-    res = run_masked_cases(_mods(_on_device, engine='fused'), gin, only=('b', 'f'),
+    res = run_hmm_cases(_mods(_on_device, engine='fused'), gin, only=('b', 'f'),
                            device_mask=lambda m: torch.from_numpy(np.ascontiguousarray(m)).cuda())
     for tag in 'bf':
         np.testing.assert_allclose(res[tag + '_L'], g[tag + '_L'], rtol=L_RTOL)
@@ -114,8 +83,7 @@ def _shapes():
 
 @pytest.mark.parametrize('B,T,D,K', _shapes())
 def test_masked_pass_against_long_double(B, T, D, K):
-    from hmm_fused_host import hmmf_host
-    from hmm_masked_host import compare_masked, mixed_mask, nan_fill
+    from hmm_fused_host import hmmf_host, compare, mixed_mask, nan_fill
     from test_hmm_fused_gpu import gpu_pass
     from test_hmm_fused_host import pass_inputs
     Y, C, la0, lA = pass_inputs(B, T, D, K)
@@ -124,24 +92,24 @@ def test_masked_pass_against_long_double(B, T, D, K):
     ob = mask.any(axis=1)
     assert ob.sum() >= 2 and (~ob).sum() >= 1
     Yn = nan_fill(Y, mask)
-    got = gpu_pass_masked(Yn, C, la0, lA, mask, want=True)
-    assert compare_masked(got, Yn, C, la0, lA, mask, SUMS + OUTS, label=str((B, T, D, K))) == []
+    got = gpu_pass(Yn, C, la0, lA, want=True, mask=mask)
+    assert compare(got, Yn, C, la0, lA, SUMS + OUTS, label=str((B, T, D, K)), mask=mask) == []
     # the optional outputs off, a second call, 0 and 1e300 at the masked positions: the same bits
-    off, again = gpu_pass_masked(Yn, C, la0, lA, mask), gpu_pass_masked(Yn, C, la0, lA, mask)
+    off, again = gpu_pass(Yn, C, la0, lA, mask=mask), gpu_pass(Yn, C, la0, lA, mask=mask)
     for k in SUMS + ('dots',):
         np.testing.assert_array_equal(off[k], got[k], err_msg=k)
         np.testing.assert_array_equal(again[k], off[k], err_msg=k)
     for fill in (0.0, 1e300):
-        alt = gpu_pass_masked(nan_fill(Y, mask, fill), C, la0, lA, mask, want=True)
+        alt = gpu_pass(nan_fill(Y, mask, fill), C, la0, lA, want=True, mask=mask)
         for k in SUMS + ('dots',) + OUTS:
             np.testing.assert_array_equal(alt[k], got[k], err_msg='%s, fill %g' % (k, fill))
     # a mask of ones: the bits of vmp_hmm_fused_pass, sums and optional outputs
     ref = gpu_pass(Y, C, la0, lA, want=True)
-    one = gpu_pass_masked(Y, C, la0, lA, np.ones((B, T), dtype=bool), want=True)
+    one = gpu_pass(Y, C, la0, lA, want=True, mask=np.ones((B, T), dtype=bool))
     for k in SUMS + ('dots',) + OUTS:
         np.testing.assert_array_equal(one[k], ref[k], err_msg=k)
     # a mask of zeros: nothing
-    z = gpu_pass_masked(Yn, C, la0, lA, np.zeros((B, T), dtype=bool))
+    z = gpu_pass(Yn, C, la0, lA, mask=np.zeros((B, T), dtype=bool))
     for k in ('z0sum', 'xisum', 'T'):
         assert np.all(z[k] == 0), k
     assert z['logZ'] == 0 and z['ge'] == 0
@@ -149,15 +117,16 @@ def test_masked_pass_against_long_double(B, T, D, K):
 
 @pytest.mark.parametrize('B,T,D,K', [(13, 7, 2, 3), (7, 4, 8, 33)])
 def test_fixed_labels_with_a_mask(B, T, D, K):
-    from hmm_masked_host import mixed_mask, nan_fill
+    from hmm_fused_host import mixed_mask, nan_fill
+    from test_hmm_fused_gpu import gpu_pass
     from test_hmm_fused_host import pass_inputs
     from test_hmm_masked_host import check_labels
     Y, C, la0, lA = pass_inputs(B, T, D, K)
     mask = mixed_mask(B, T, np.random.RandomState(5))
     lab = np.random.RandomState(1).randint(K, size=(B, T))
-    r = gpu_pass_masked(nan_fill(Y, mask), C, la0, lA, mask, labels=lab, want=True)
+    r = gpu_pass(nan_fill(Y, mask), C, la0, lA, labels=lab, want=True, mask=mask)
     check_labels(r, lab, Y, mask, K)
-    off = gpu_pass_masked(nan_fill(Y, mask), C, la0, lA, mask, labels=lab)
+    off = gpu_pass(nan_fill(Y, mask), C, la0, lA, labels=lab, mask=mask)
     for k in SUMS:
         np.testing.assert_array_equal(off[k], r[k])
 
@@ -165,7 +134,8 @@ def test_fixed_labels_with_a_mask(B, T, D, K):
 def test_tables_below_the_underflow_of_exp_with_a_mask():
     """One used row of <log A> near 0, the others near -670 (Dirichlet(1e-3) rows)."""
     from scipy import special
-    from hmm_masked_host import compare_masked, mixed_mask, nan_fill
+    from hmm_fused_host import compare, mixed_mask, nan_fill
+    from test_hmm_fused_gpu import gpu_pass
     from test_hmm_fused_host import pass_inputs
     K = 3
     Y, C, _, _ = pass_inputs(7, 9, 2, K)
@@ -176,9 +146,9 @@ def test_tables_below_the_underflow_of_exp_with_a_mask():
     la0 = special.digamma(np.full(K, 1e-3)) - special.digamma(3e-3)
     mask = mixed_mask(7, 9, np.random.RandomState(2))
     Yn = nan_fill(Y, mask)
-    got = gpu_pass_masked(Yn, C, la0, lA, mask, want=True)
+    got = gpu_pass(Yn, C, la0, lA, want=True, mask=mask)
     assert np.all(np.isfinite(got['zz']))
-    assert compare_masked(got, Yn, C, la0, lA, mask, SUMS + ('gamma', 'zz'), label='one row') == []
+    assert compare(got, Yn, C, la0, lA, SUMS + ('gamma', 'zz'), label='one row', mask=mask) == []
 
 
 def test_cabi_masked_pass_checks_its_arguments_on_a_live_context():

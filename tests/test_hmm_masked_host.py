@@ -1,7 +1,7 @@
 """CPU: masks on the fused hidden-Markov-model block without a device -- the matcher (full-shape
 masks accepted, scalar and broadcasting masks declined), the plan's host logic on the kernel double
-tests/hmm_masked_host.py (CPUMaskedHMMKernels) against every fixture of tests/golden/hmm_masked.npz
-(live reference, tools/make_golden_hmm_masked.py), ``Z.mask`` / ``Y.mask``, re-observation, save /
+tests/hmm_fused_host.py (CPUHMMKernels) against every fixture of tests/golden/hmm_masked.npz
+(live reference, tools/make_golden_hmm.py masked), ``Z.mask`` / ``Y.mask``, re-observation, save /
 load, the g++ build of the device header's masked pass against a long-double restatement, and the
 C ABI of ``vmp_hmm_fused_pass_masked``."""
 import ctypes
@@ -31,11 +31,11 @@ def _mods(after=None, **kw):
 
 def _on_double(Q):
     from bayespy_amd.device import Runtime
-    from hmm_masked_host import CPUMaskedHMMKernels
+    from hmm_fused_host import CPUHMMKernels
     plan = Q.plans[0]
     assert type(plan).__name__ == 'HMMPlan'
     rt = Runtime(device='cpu')
-    plan._rt, plan._kernels = rt, CPUMaskedHMMKernels(rt)
+    plan._rt, plan._kernels = rt, CPUHMMKernels(rt)
 
 
 def _golden():
@@ -125,7 +125,7 @@ def test_engine_fused_builds_the_block_with_a_mask():
 
 # -- the plan on the kernel double ---------------------------------------------------------------------
 def check_masked_fixtures(res, g):
-    from hmm_masked_models import CASES, LEARNED
+    from hmm_models import CASES, LEARNED
     checked = 0
     for k, v in res.items():
         if k.endswith('_plan'):
@@ -152,11 +152,11 @@ def check_masked_fixtures(res, g):
 
 def test_plan_reproduces_every_fixture_on_the_kernel_double():
     """Fails without the feature: engine='fused' declines the masked models."""
-    from hmm_masked_models import run_masked_cases
+    from hmm_models import run_hmm_cases
     g, gin = _golden()
     with warnings.catch_warnings():
         warnings.simplefilter('error')
-        res = run_masked_cases(_mods(_on_double, engine='fused'), gin)
+        res = run_hmm_cases(_mods(_on_double, engine='fused'), gin)
     check_masked_fixtures(res, g)
     calls = res['a_plan'].plans[0].kernels.calls
     # set-up pass + one per sweep, all masked; gamma, z0 and zz only on request
@@ -168,9 +168,9 @@ def test_plan_reproduces_every_fixture_on_the_kernel_double():
 
 
 def test_fixtures_with_device_masks_on_the_kernel_double():
-    from hmm_masked_models import run_masked_cases
+    from hmm_models import run_hmm_cases
     g, gin = _golden()
-    res = run_masked_cases(_mods(_on_double, engine='fused'), gin, only=('b', 'd', 'f'),
+    res = run_hmm_cases(_mods(_on_double, engine='fused'), gin, only=('b', 'd', 'f'),
                            device_mask=_device_mask)
     for k, v in res.items():
         if k.endswith('_L') or k.endswith('_mask'):
@@ -202,14 +202,14 @@ def test_masks_of_the_nodes():
 
 
 def test_values_at_masked_positions_do_not_matter():
-    from hmm_masked_models import run_masked_cases
+    from hmm_models import run_hmm_cases
     g, gin = _golden()
-    base = run_masked_cases(_mods(_on_double, engine='fused'), gin, only=('b', 'e'))
+    base = run_hmm_cases(_mods(_on_double, engine='fused'), gin, only=('b', 'e'))
     for fill in (0.0, 1e3):
         alt = dict(gin)
         for tag in 'be':
             alt[tag + '_y'] = np.where(gin[tag + '_mask'][..., None], gin[tag + '_y'], fill)
-        res = run_masked_cases(_mods(_on_double, engine='fused'), alt, only=('b', 'e'))
+        res = run_hmm_cases(_mods(_on_double, engine='fused'), alt, only=('b', 'e'))
         for k, v in base.items():
             if not k.endswith('_plan'):
                 np.testing.assert_array_equal(res[k], v, err_msg=k)
@@ -217,9 +217,9 @@ def test_values_at_masked_positions_do_not_matter():
 
 def test_reobservation_keeps_the_posteriors():
     """After updates: new data and a new full-shape mask (or none) re-form the sums only."""
-    from hmm_masked_models import run_masked_cases
+    from hmm_models import run_hmm_cases
     g, gin = _golden()
-    res = run_masked_cases(_mods(_on_double, engine='fused'), gin, only=('e',))
+    res = run_hmm_cases(_mods(_on_double, engine='fused'), gin, only=('e',))
     Q = res['e_plan']
     plan = Q.plans[0]
     Y = plan.Y
@@ -236,10 +236,10 @@ def test_reobservation_keeps_the_posteriors():
         np.testing.assert_array_equal(plan.mu.get_moments()[0], mu_before)
         np.testing.assert_array_equal(Y.mask, m2)
         np.testing.assert_array_equal(plan.maskd.numpy(), m2.astype(np.uint8))
-        from hmm_masked_host import host_pass_masked
+        from hmm_fused_host import host_pass
         L = plan.layout
         C = plan.state[L.off_C:L.off_C + int(L.KP) * int(L.F2P)].numpy().reshape(-1, int(L.F2P))[:3]
-        want = host_pass_masked(y2, C, plan.used_a0.numpy(), plan.used_A.numpy(), m2)
+        want = host_pass(y2, C, plan.used_a0.numpy(), plan.used_A.numpy(), mask=m2)
         np.testing.assert_array_equal(plan.Tstat.numpy(), want['T'])
         np.testing.assert_array_equal(plan.xisum.numpy(), want['xisum'])
         # and without a mask: the unmasked pass again
@@ -258,9 +258,9 @@ def test_reobservation_keeps_the_posteriors():
 
 
 def _save_load(tmp_path, tag):
-    from hmm_masked_models import run_masked_cases
+    from hmm_models import run_hmm_cases
     g, gin = _golden()
-    Q = run_masked_cases(_mods(_on_double, engine='fused'), gin, only=(tag,))[tag + '_plan']
+    Q = run_hmm_cases(_mods(_on_double, engine='fused'), gin, only=(tag,))[tag + '_plan']
     fn = str(tmp_path / 'hmm.ckpt')
     Q.save(filename=fn)
     L4 = Q.L[:4].copy()
@@ -325,36 +325,34 @@ HOST_SHAPES = [(3, 2, 1, 1), (7, 3, 3, 2), (13, 7, 2, 3), (67, 5, 2, 2), (9, 65,
 def test_host_build_of_the_masked_pass_against_long_double(B, T, D, K):
     """The rule of DESIGN 4.15: 8 times the deviation of the float64 evaluation of the reference
     formulas from long double, floor 4 ulp of the quantity's magnitude."""
-    from hmm_fused_host import host_pass
-    from hmm_masked_host import host_pass_masked, compare_masked, mixed_mask, nan_fill
+    from hmm_fused_host import host_pass, compare, mixed_mask, nan_fill
     from test_hmm_fused_host import pass_inputs
     Y, C, la0, lA = pass_inputs(B, T, D, K)
     mask = mixed_mask(B, T, np.random.RandomState(B + T))
     Yn = nan_fill(Y, mask)
-    got = host_pass_masked(Yn, C, la0, lA, mask, want=True)
+    got = host_pass(Yn, C, la0, lA, want=True, mask=mask)
     keys = ('z0sum', 'xisum', 'T', 'logZ', 'ge', 'gamma', 'z0', 'zz')
-    assert compare_masked(got, Yn, C, la0, lA, mask, keys, label=str((B, T, D, K))) == []
+    assert compare(got, Yn, C, la0, lA, keys, label=str((B, T, D, K)), mask=mask) == []
     sums = ('z0sum', 'xisum', 'T', 'logZ', 'ge')
     # the values at masked positions, the optional outputs: the same bits
     for fill in (0.0, 1e300):
-        alt = host_pass_masked(nan_fill(Y, mask, fill), C, la0, lA, mask)
+        alt = host_pass(nan_fill(Y, mask, fill), C, la0, lA, mask=mask)
         for k in sums:
             np.testing.assert_array_equal(alt[k], got[k], err_msg=k)
-    # a mask of ones and no mask: the bits of the unmasked host build
+    # a mask of ones: the bits of mask=None
     ref = host_pass(Y, C, la0, lA, want=True)
-    for mk in (np.ones((B, T), dtype=bool), None):
-        one = host_pass_masked(Y, C, la0, lA, mk, want=True)
-        for k in keys:
-            np.testing.assert_array_equal(one[k], ref[k], err_msg=k)
+    one = host_pass(Y, C, la0, lA, want=True, mask=np.ones((B, T), dtype=bool))
+    for k in keys:
+        np.testing.assert_array_equal(one[k], ref[k], err_msg=k)
     # a mask of zeros: nothing
-    z = host_pass_masked(Yn, C, la0, lA, np.zeros((B, T), dtype=bool))
+    z = host_pass(Yn, C, la0, lA, mask=np.zeros((B, T), dtype=bool))
     assert not np.any(z['z0sum']) and not np.any(z['xisum']) and not np.any(z['T'])
     assert z['logZ'] == 0 and z['ge'] == 0
     # the prior pass
-    assert compare_masked(host_pass_masked(Yn, None, la0, lA, mask), Yn, None, la0, lA, mask) == []
+    assert compare(host_pass(Yn, None, la0, lA, mask=mask), Yn, None, la0, lA, mask=mask) == []
     # fixed labels: T over the observed steps, z0sum and xisum over the chains with one
     lab = np.random.RandomState(0).randint(K, size=(B, T))
-    r = host_pass_masked(Yn, C, la0, lA, mask, labels=lab, want=True)
+    r = host_pass(Yn, C, la0, lA, labels=lab, want=True, mask=mask)
     check_labels(r, lab, Y, mask, K)
 
 

@@ -6,6 +6,8 @@ EVERYTHING is compared bitwise (np.array_equal), never with a tolerance.
 The counters (vmp_pca_sweep_counts, vmp_pca_pass_counts) belong to the process-wide context:
 every check is on deltas.
 """
+import gc
+
 import numpy as np
 import pytest
 
@@ -67,6 +69,9 @@ def _assert_same(a, b):
 
 class sweep_counts:
     def __init__(self, plan):
+        # plans of earlier tests are finalised now, not inside the counted window: PCAPlan.__del__
+        # joins the plate stream of the shared context, which launches a pass that is held
+        gc.collect()
         self.k = plan.kernels
         self.start = self.k.sweep_counts()
         self.pstart = self.k.pass_counts()
