@@ -242,6 +242,11 @@ SIGNATURES = {
     'vmp_hmm_fused_pass_masked': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp,
                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                           c_vp, c_vp]),
+    'vmp_hmm_fused_cat_limits': (c_i32, [P(c_i32), P(c_i32)]),
+    'vmp_hmm_fused_cat_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
+    'vmp_hmm_fused_pass_categorical': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                               c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp, c_vp, c_vp]),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_hold_passes': (c_i32, [c_vp, c_i32]),

@@ -35,8 +35,16 @@
 //     chain c of its range belongs to lane group c % (64 / KP), which walks its chains in
 //     ascending order and adds each chain's steps in the order of the backward sweep
 //     (t = T-1 ... 1, then t = 0);  the groups are added in group order, then the workgroups'
-//     partials in workgroup order by a second kernel.
-// The bits of every output therefore depend on the inputs and (B, T, D, K) only.
+//     partials in workgroup order by a second kernel;
+//   * categorical emissions (csrc/vmp_hmm_cat.hip; y_t a word in [0, M), e_t[j] = <log P>[y_t][j]
+//     read from the word-major table, nothing to add up): everything above but the feature line,
+//     with vmp_hmmf_cat_chains_per_wg(B, M, K) chains per workgroup; the count S[m][j] of lane
+//     (group g, column j) takes gamma_t[j] times the chain weight at the observed steps with
+//     y_t = m, in the order in which that lane meets them (its chains ascending, each in the
+//     order of the backward sweep); a workgroup's partial adds the groups from zero in group
+//     order, the second kernel the workgroups in workgroup order and writes S word-major (M, K).
+// The bits of every output therefore depend on the inputs and (B, T, D, K) only ((B, T, M, K) with
+// categorical emissions).
 //
 // MASKS (vmp_hmm_fused_pass_masked; mask[b, t] = 1 where y_{b,t} is observed).  A masked step
 // sends a zero message: e_t = 0 for every state.  The step stays in the chain: the recursion above
@@ -59,6 +67,7 @@
 #define VMP_HMMF_MAX_D 8
 #define VMP_HMMF_MAX_WGS 4096
 #define VMP_HMMF_MAX_NF 45        // features of D = 8
+#define VMP_HMMF_MAX_M 128        // categorical emissions: 512 M bytes of count accumulators in LDS
 
 __host__ __device__ inline int vmp_hmmf_kpad(int K)
 {
@@ -136,6 +145,47 @@ __host__ __device__ inline double vmp_hmmf_emit(const double *C, int ldc, const 
 __host__ __device__ inline double vmp_hmmf_observed_or_zero(bool observed, double e)
 {
     return observed ? e : 0.0;
+}
+
+// categorical emissions: a step counts as observed when its mask says so AND its word lies in
+// [0, M) (one unsigned compare); any other word indexes nothing and the step sends a zero message.
+// The caller validates the words; this only keeps a bad one from becoming an address.
+__host__ __device__ inline bool vmp_hmmf_cat_observed(bool unmasked, int32_t word, int M)
+{
+    return unmasked && (uint32_t)word < (uint32_t)M;
+}
+
+// doubles one workgroup leaves behind: sum gamma_0 (K), sum xi (K x K), the counts (M x K,
+// word-major), sum log Z, sum gamma . e
+__host__ __device__ inline int64_t vmp_hmmf_cat_partial_doubles(int M, int K)
+{
+    return (int64_t)K + (int64_t)K * K + (int64_t)M * K + 2;
+}
+
+// as vmp_hmmf_chains_per_wg, with the partial of the categorical pass
+__host__ __device__ inline int64_t vmp_hmmf_cat_chains_per_wg(int64_t B, int M, int K)
+{
+    const int64_t groups = 64 / vmp_hmmf_kpad(K);
+    int64_t maxw = ((int64_t)1 << 24) / vmp_hmmf_cat_partial_doubles(M, K);
+    if (maxw > VMP_HMMF_MAX_WGS) maxw = VMP_HMMF_MAX_WGS;
+    if (maxw < 1) maxw = 1;
+    int64_t c = (B + maxw - 1) / maxw;
+    c = (c + groups - 1) / groups * groups;
+    if (c < groups) c = groups;
+    return c;
+}
+
+__host__ __device__ inline int64_t vmp_hmmf_cat_wgs(int64_t B, int M, int K)
+{
+    const int64_t c = vmp_hmmf_cat_chains_per_wg(B, M, K);
+    return B > 0 ? (B + c - 1) / c : 0;
+}
+
+// workspace of the categorical pass: la (B T K), the partials, 1024 doubles for the dot products
+__host__ __device__ inline int64_t vmp_hmmf_cat_workspace_doubles(int64_t B, int T, int M, int K)
+{
+    return B * (int64_t)T * K + vmp_hmmf_cat_wgs(B, M, K) * vmp_hmmf_cat_partial_doubles(M, K)
+           + 1024;
 }
 
 // the weight of a chain: 1 if any of its T steps is observed

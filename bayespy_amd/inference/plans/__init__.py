@@ -11,12 +11,22 @@ from .lssm_masked import MaskedLSSMPlan
 from .lda import LDAPlan, LDASVIPlan
 from .bmm import BernoulliMixturePlan
 from .hmm import HMMPlan
+from .hmm_cat import CategoricalHMMPlan
 
 PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
 # engine='fused': a block's opt-in form takes the place of its default form
 OPT_IN_FORMS = {LDAPlan: LDASVIPlan}
 # engine='fused': blocks that have no default form (their models run on the generic engine otherwise)
 OPT_IN_TYPES = [BernoulliMixturePlan, HMMPlan]
+# engine='fused': further emission families of an opt-in block, each a plan class of its own, tried
+# right after that block (the block itself declines them with a reason, so they join neither list
+# above: CategoricalHMMPlan is HMMPlan with a table lookup in place of the Gaussian quadratic form)
+OPT_IN_EMISSIONS = {HMMPlan: [CategoricalHMMPlan]}
+
+
+def opt_in_types():
+    """``OPT_IN_TYPES`` with the plan classes of ``OPT_IN_EMISSIONS`` inserted after their block."""
+    return [Q for P in OPT_IN_TYPES for Q in [P] + OPT_IN_EMISSIONS.get(P, [])]
 
 
 def _reusable_plans(nodes, engine, options=None):
@@ -40,7 +50,7 @@ def _reusable_plans(nodes, engine, options=None):
         return None
     if engine == 'fused' and any(isinstance(p, GenericPlan) for p in plans):
         return None
-    if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values() or type(p) in OPT_IN_TYPES
+    if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values() or type(p) in opt_in_types()
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -90,7 +100,7 @@ def compile_model(nodes, engine=None, **options):
         plan = GenericPlan(nodes)
         plan._engine_request = 'generic'
         return [plan]
-    types = [OPT_IN_FORMS.get(P, P) for P in PLAN_TYPES] + OPT_IN_TYPES if engine == 'fused' \
+    types = [OPT_IN_FORMS.get(P, P) for P in PLAN_TYPES] + opt_in_types() if engine == 'fused' \
         else PLAN_TYPES
     remaining = [n for n in nodes]
     plans = []

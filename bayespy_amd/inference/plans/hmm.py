@@ -59,6 +59,7 @@ from ...nodes.mixture import Mixture
 from .gmm import GMMKernels
 
 _LIMITS = []
+_KINDS = {'hmm': 'Gaussian', 'hmm_cat': 'categorical'}      # checkpoint kind -> emission family
 
 
 def hmm_limits():
@@ -276,8 +277,9 @@ class HMMPlan:
 
     def __init__(self, roles, runtime=None, kernels=None):
         self.roles = roles
-        self.Y, self.Z, self.A = roles['Y'], roles['Z'], roles['A']
-        self.a0, self.Zc = roles['a0'], roles['Zc']
+        self.Y, self.Z = roles['Y'], roles['Z']
+        self.Zc = roles['Zc']
+        self.a0, self.A = self.Z.parents                # the roles, or constants (hmm_cat.py)
         self.mu, self.Lam = roles.get('mu'), roles.get('Lambda')
         self.learned = self.mu is not None
         self.K, self.T = self.Z.categories, self.Z.states
@@ -321,7 +323,7 @@ class HMMPlan:
         _delta.warn_state_discarded(self, node)
         self._ready = False
         self._version += 1
-        if HMMPlan.match([n for n in self.nodes() if n is not self.Zc]) is None:
+        if type(self).match([n for n in self.nodes() if n is not self.Zc]) is None:
             from .generic import GenericPlan
             GenericPlan([n for n in self.nodes() if n is not self.Zc])
 
@@ -339,6 +341,11 @@ class HMMPlan:
             a = np.broadcast_to(np.asarray(y, dtype=np.float64), self.Y.plates + (self.D,))
             t = torch.from_numpy(np.array(a.reshape(shape), order='C')).to(rt.device)
         self.Yd = t
+        self._upload_mask()
+        self._y_stale = False
+
+    def _upload_mask(self):
+        rt, torch = self.rt, self.rt.torch
         m = self.Y._mask
         if m is True:
             self.maskd = None
@@ -347,7 +354,6 @@ class HMMPlan:
         else:
             self.maskd = torch.from_numpy(np.ascontiguousarray(
                 np.asarray(m, dtype=bool).reshape(self.B, self.T).astype(np.uint8))).to(rt.device)
-        self._y_stale = False
 
     def _labels(self, lab):
         lab = np.asarray(lab)
@@ -393,21 +399,39 @@ class HMMPlan:
                                     np.asarray(self.Y.parents[2].value, dtype=np.float64))
             self.C, self.Cn, self.ldc = up(C), up(Cn), C.shape[1]
             self.Tstat = rt.zeros(K, self.FS)
-        self.prior_a0, self.prior_A = up(prior_table(self.a0, (K,))), up(prior_table(self.A, (K, K)))
-        self.alpha_a0, self.elog_a0 = rt.empty(K), rt.empty(K)
-        self.alpha_A, self.elog_A = rt.empty(K, K), rt.empty(K, K)
+        self.ws = rt.empty(int(wsd))
+        self._init_chain_state()
+        self._with_emissions = False
+        self._ready = True
+        self._run_pass()
+
+    def _init_chain_state(self):
+        """The tables of ``a0`` and ``A``, the sums of the chain and the initial state of ``Z``
+        (fixed labels, or its moments under the prior).  A role that is a constant (hmm_cat.py)
+        has the logarithm of its value as its table, uploaded once, no update and no bound term."""
+        rt, k, K, T = self.rt, self.kernels, self.K, self.T
+        torch = rt.torch
+        up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(rt.device)  # noqa: E731
+        self.alpha_a0, self.alpha_A = rt.zeros(K), rt.zeros(K, K)
         self.used_a0, self.used_A = rt.empty(K), rt.empty(K, K)
         self.z0sum, self.xisum = rt.zeros(K), rt.zeros(K, K)
-        self.ws = rt.empty(int(wsd))
         self.ws_small = rt.empty(max(K * K, 1024))
         # [0] sum log Z, [1] sum gamma . e, [2] z0 . <log a0> used, [3] xi . <log A> used,
         # [4] T . C, [5] z0 . <log a0>, [6] xi . <log A>
         self.scal = rt.zeros(8)
         self.bnd = rt.zeros(2)                          # bound terms of a0 and A
-        k.dirichlet(1, K, K, 1, self.prior_a0, None, self.alpha_a0, self.elog_a0, self.ws_small,
-                    self.bnd[0:1])
-        k.dirichlet(K, K, K, 1, self.prior_A, None, self.alpha_A, self.elog_A, self.ws_small,
-                    self.bnd[1:2])
+        if isinstance(self.a0, Constant):
+            self.elog_a0 = up(np.log(np.broadcast_to(self.a0.value, (K,))))
+        else:
+            self.prior_a0, self.elog_a0 = up(prior_table(self.a0, (K,))), rt.empty(K)
+            k.dirichlet(1, K, K, 1, self.prior_a0, None, self.alpha_a0, self.elog_a0,
+                        self.ws_small, self.bnd[0:1])
+        if isinstance(self.A, Constant):
+            self.elog_A = up(np.log(np.broadcast_to(self.A.value, (K, K))))
+        else:
+            self.prior_A, self.elog_A = up(prior_table(self.A, (K, K))), rt.empty(K, K)
+            k.dirichlet(K, K, K, 1, self.prior_A, None, self.alpha_A, self.elog_A, self.ws_small,
+                        self.bnd[1:2])
         # Z: fixed labels, or its moments under the prior (no emission term)
         self.labels = None
         init = self.Z._init
@@ -419,22 +443,25 @@ class HMMPlan:
             else:
                 raise NotImplementedError('the fused hidden-Markov-model block initialises Z '
                                           'from its prior, a value or at random')
-        self._with_emissions = False
-        self._ready = True
-        self._run_pass()
 
     def _run_pass(self, gamma=None, z0=None, zz=None, refresh=True):
         """The sums of the present ``Z`` state (the tables of its last update, or labels).
         ``refresh``: take the current <log a0> and <log A> as the tables of the pass."""
         if refresh:
-            self.used_a0.copy_(self.elog_a0)
-            self.used_A.copy_(self.elog_A)
+            self._refresh_tables()
+        self._launch_pass(gamma, z0, zz)
+        if refresh or gamma is None:
+            self._version += 1              # writing gamma / z0 / zz out changes no sum
+
+    def _refresh_tables(self):
+        self.used_a0.copy_(self.elog_a0)
+        self.used_A.copy_(self.elog_A)
+
+    def _launch_pass(self, gamma, z0, zz):
         C = self.C if self._with_emissions else None
         self.kernels.pass_(self.B, self.T, self.D, self.K, self.Yd, C, self.ldc, self.used_a0,
                            self.used_A, self.labels, self.ws, self.z0sum, self.xisum, self.Tstat,
                            self.scal, gamma, z0, zz, mask=self.maskd)
-        if refresh or gamma is None:
-            self._version += 1              # writing gamma / z0 / zz out changes no sum
 
     # -- operations ----------------------------------------------------------------------------------
     def update(self, node):
@@ -453,10 +480,10 @@ class HMMPlan:
             k.gmm.update_mu(self.D, K, self.state)
         elif self.learned and node is self.Lam:
             k.gmm.update_lambda(self.D, K, self.state)
-        elif node is self.a0:
+        elif node is self.a0 and not isinstance(node, Constant):
             k.dirichlet(1, K, K, 1, self.prior_a0, self.z0sum, self.alpha_a0, self.elog_a0,
                         self.ws_small, self.bnd[0:1])
-        elif node is self.A:
+        elif node is self.A and not isinstance(node, Constant):
             k.dirichlet(K, K, K, 1, self.prior_A, self.xisum, self.alpha_A, self.elog_A,
                         self.ws_small, self.bnd[1:2])
         else:
@@ -479,21 +506,27 @@ class HMMPlan:
                 extra = dict(mu=float(host[8 + 3]), Lambda=float(host[8 + 4]))
             else:
                 k.dot(K * self.FS, self.Tstat, self.Cn, self.ws_small, self.scal[4:5])
-            k.dot(K, self.z0sum, self.elog_a0, self.ws_small, self.scal[5:6])
-            k.dot(K * K, self.xisum, self.elog_A, self.ws_small, self.scal[6:7])
-            s = self.scal.cpu().numpy()
-            b = self.bnd.cpu().numpy()
-            entropy = 0.0 if self.labels is not None else float(s[0] - s[1] - (s[2] + s[3]))
-            t = dict(Y=LY if self.learned else float(s[4]), Z=float(s[5] + s[6]) + entropy,
-                     a0=float(b[0]), A=float(b[1]), **extra)
+            s, chain = self._chain_terms()
+            t = dict(Y=LY if self.learned else float(s[4]), **chain, **extra)
             t['total'] = sum(t.values())
             self._L = t
             self._L_version = self._version
         return _delta.bound_terms(self._L, self._delta)
 
+    def _chain_terms(self):
+        """(scal on the host, the bound terms of Z, a0 and A) by the formula of the module's
+        docstring; whatever the caller wants in scal[4] is launched before."""
+        k, K = self.kernels, self.K
+        k.dot(K, self.z0sum, self.elog_a0, self.ws_small, self.scal[5:6])
+        k.dot(K * K, self.xisum, self.elog_A, self.ws_small, self.scal[6:7])
+        s = self.scal.cpu().numpy()
+        b = self.bnd.cpu().numpy()
+        entropy = 0.0 if self.labels is not None else float(s[0] - s[1] - (s[2] + s[3]))
+        return s, dict(Z=float(s[5] + s[6]) + entropy, a0=float(b[0]), A=float(b[1]))
+
     def lower_bound_contribution(self, node):
         terms = self._lower_bound_terms()
-        for key in ('Y', 'Z', 'a0', 'A', 'mu', 'Lambda'):
+        for key in ('Y', 'Z', 'a0', 'A', 'mu', 'Lambda', 'P'):
             if node is self.roles.get(key):
                 return terms[key]
         return 0.0
@@ -557,6 +590,12 @@ class HMMPlan:
         return np.array(True)
 
     # -- persistence -----------------------------------------------------------------------------------
+    _KIND, _EMISSIONS = 'hmm', 'Gaussian'
+    _DIMS = '(B, T, D, K, learned emissions)'
+
+    def _dims(self):
+        return (self.B, self.T, self.D, self.K, int(self.learned))
+
     _SAVED_BOTH = ('alpha_a0', 'elog_a0', 'alpha_A', 'elog_A', 'used_a0', 'used_A', 'z0sum',
                    'xisum', 'scal', 'bnd')
 
@@ -569,9 +608,8 @@ class HMMPlan:
         self._materialize()
         base = 'plans/%d/' % index
         _delta.save(put, base, self._delta)
-        put(base + 'kind', np.array([ord(ch) for ch in 'hmm'], dtype=np.uint8))
-        put(base + 'dims', np.array([self.B, self.T, self.D, self.K, int(self.learned)],
-                                    dtype=np.int64))
+        put(base + 'kind', np.array([ord(ch) for ch in self._KIND], dtype=np.uint8))
+        put(base + 'dims', np.array(self._dims(), dtype=np.int64))
         put(base + 'flags', np.array([1 if self.labels is not None else 0,
                                       1 if self._with_emissions else 0], dtype=np.int64))
         if self.labels is not None:
@@ -584,14 +622,17 @@ class HMMPlan:
     def load_state(self, reader, nodes, index):
         self._materialize()
         base = 'plans/%d/' % index
-        if not reader.has(base + 'kind') or bytes(np.asarray(reader.get(base + 'kind'),
-                                                             dtype=np.uint8)) != b'hmm':
+        kind = bytes(np.asarray(reader.get(base + 'kind'), dtype=np.uint8)).decode() \
+            if reader.has(base + 'kind') else None
+        if kind != self._KIND:
             raise Exception("File does not contain the state of the fused hidden-Markov-model "
-                            "block")
+                            "block with %s emissions%s"
+                            % (self._EMISSIONS, '' if kind not in _KINDS else
+                               ': it holds that of the block with %s emissions' % _KINDS[kind]))
         dims = tuple(int(v) for v in reader.get(base + 'dims'))
-        if dims != (self.B, self.T, self.D, self.K, int(self.learned)):
-            raise ValueError('checkpoint is for (B, T, D, K, learned emissions) = %s, the model '
-                             'has %s' % (dims, (self.B, self.T, self.D, self.K, int(self.learned))))
+        if dims != self._dims():
+            raise ValueError('checkpoint is for %s = %s, the model has %s'
+                             % (self._DIMS, dims, self._dims()))
         saved = np.asarray(reader.get(base + 'mask'), dtype=np.uint8).reshape(-1) \
             if reader.has(base + 'mask') else None
         mine = None if self.maskd is None else self.maskd.cpu().numpy().reshape(-1)

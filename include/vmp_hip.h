@@ -998,6 +998,42 @@ int32_t vmp_hmm_fused_pass_masked(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D,
                                   double *z0sum, double *xisum, double *Tstat, double *scal,
                                   double *gamma, double *z0, double *zz);
 
+/* Hidden Markov model with categorical emissions (the discrete HMM of hmm.rst's first half): the
+ * chain pass of the fused block (bayespy_amd/csrc/vmp_hmm_cat.hip, vmp_hmm_fused_dev.h).  B chains
+ * of T time instances, words y_t in [0, M), K states.  The recursion, the lane mapping, the mask
+ * rules and the order of the additions are those of vmp_hmm_fused_pass_masked; the emission term
+ * is a table lookup.
+ *   vmp_hmm_fused_cat_limits (host only): *max_K = 64, *max_M = 128 (a workgroup keeps 512 M
+ *     bytes of count accumulators in LDS).
+ *   vmp_hmm_fused_cat_plan (host only): for (B, T, M, K) the chains of a workgroup *chains_per_wg
+ *     (a function of the shape alone) and the scratch *workspace_doubles of the pass
+ *     (B T K + partials + 1024).
+ *   vmp_hmm_fused_pass_categorical: y (B, T) int32 words; elogPt (M, K) = <log P> WORD-MAJOR
+ *     (element (m, k) at m K + k), or NULL for no emission term; elog_a0 (K), elog_A (K x K);
+ *     labels (B x T int32) or NULL; mask (B x T bytes, 1 = observed) or NULL (everything
+ *     observed).  e_t[k] = elogPt[y_t][k] at an observed step, 0 at a masked one, whose y_t is
+ *     never read (any integer may stand there).  PRECONDITION: every observed word lies in
+ *     [0, M); the caller validates them.  A word outside that range never indexes anything: its
+ *     step is treated as masked (the chain weight is taken from the mask alone).
+ *     Out: z0sum (K), xisum (K x K) as in vmp_hmm_fused_pass; S (M, K) word-major =
+ *     sum over the observed (b, t) with y = m of gamma_{b,t,k}; scal[0] = sum_b log Z_b,
+ *     scal[1] = sum gamma . e, scal[2] = z0sum . elog_a0, scal[3] = xisum . elog_A; with gamma
+ *     (B, T, K), z0 (B, K), zz (B, T-1, K, K) non-NULL also these.  A chain without an observed
+ *     step adds nothing to any sum.  ws: vmp_hmm_fused_cat_plan's doubles.  No atomics: the bits
+ *     of every output depend on the inputs and (B, T, M, K) only; a mask of ones gives the bits of
+ *     a NULL mask.  B = 0 gives zeros.  The shape is judged before the pointers: T < 2 or a
+ *     size below 1 (B below 0): VMP_ERR_INVALID; K or M above the limits: VMP_ERR_UNSUPPORTED;
+ *     then a null required argument: VMP_ERR_INVALID.  Nothing is launched after a refusal. */
+int32_t vmp_hmm_fused_cat_limits(int32_t *max_K, int32_t *max_M);
+int32_t vmp_hmm_fused_cat_plan(int64_t B, int32_t T, int32_t M, int32_t K, int64_t *chains_per_wg,
+                               int64_t *workspace_doubles);
+int32_t vmp_hmm_fused_pass_categorical(vmp_ctx *ctx, int64_t B, int32_t T, int32_t M, int32_t K,
+                                       const int32_t *y, const double *elogPt,
+                                       const double *elog_a0, const double *elog_A,
+                                       const int32_t *labels, const uint8_t *mask, double *ws,
+                                       double *z0sum, double *xisum, double *S, double *scal,
+                                       double *gamma, double *z0, double *zz);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */

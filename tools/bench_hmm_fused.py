@@ -17,6 +17,12 @@ tests/hmm_models.py, Z from fixed random labels):
            NaN stands at the masked positions.  Without --out these lines (and the unmasked pass
            of the same build before them) go to profiles/hmm_fused/bench_hmm_masked.json.
 
+  cat      (--emissions categorical) the same three legs for the discrete block
+           (inference/plans/hmm_cat.py): M = 16 words, learned P, Z from fixed random labels; the
+           pass is ``vmp_hmm_fused_pass_categorical`` (8 + 16 K bytes per chain step: the int32 word read
+           twice, the forward state written and read once; the <log P> rows come from L2).
+           Without --out these lines go to profiles/hmm_fused/bench_hmm_cat.json.
+
     python tools/bench_hmm_fused.py [--legs fused,pass,generic] [--B 20000] [--T 1000] [--steps 5]
                                     [--warmup 2] [--out profiles/...json]
     python tools/bench_hmm_fused.py --legs pass --observed 1.0,0.7 --ragged
@@ -59,6 +65,74 @@ def build(y, mu, z0, engine):
     return Q
 
 
+def make_words(B, T, M, K, seed=0):
+    rs = np.random.RandomState(seed)
+    P = rs.dirichlet(0.3 * np.ones(M), size=K)
+    z = np.empty((B, T), dtype=np.int64)
+    z[:, 0] = rs.randint(K, size=B)
+    for t in range(1, T):                           # sticky chains
+        z[:, t] = np.where(rs.rand(B) < 0.9, z[:, t - 1], rs.randint(K, size=B))
+    u = rs.rand(B, T)
+    y = (u[..., None] > np.cumsum(P, axis=1)[z]).sum(-1).clip(0, M - 1)
+    return y, rs.randint(K, size=(B, T))
+
+
+def build_cat(y, z0, K, M, engine):
+    import bayespy_amd.nodes as N_
+    from bayespy_amd.inference import VB
+    B, T = y.shape
+    a0 = N_.Dirichlet(1e-3 * np.ones(K), name='a0')
+    A = N_.Dirichlet(1e-3 * np.ones((K, K)), name='A')
+    P = N_.Dirichlet(np.ones((K, M)), name='P')
+    Z = N_.CategoricalMarkovChain(a0, A, states=T, plates=(B,), name='Z')
+    Y = N_.Mixture(Z, N_.Categorical, P, name='Y')
+    Y.observe(y)
+    Z.initialize_from_value(z0)
+    Q = VB(Y, P, A, a0, Z, engine=engine)
+    Q.ignore_bound_checks = True
+    return Q
+
+
+def categorical_legs(a, emit):
+    import torch
+    B, T, K, M = a.B, a.T, a.K, a.M
+    y, z0 = make_words(B, T, M, K)
+    legs = a.legs.split(',')
+    if 'fused' in legs or 'pass' in legs:
+        torch.cuda.reset_peak_memory_stats()
+        Q = build_cat(y, z0, K, M, 'fused')
+        plan = Q.plans[0]
+        assert type(plan).__name__ == 'CategoricalHMMPlan'
+        if 'fused' in legs:
+            emit(dict(leg='fused', what='Q.update()',
+                      **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
+            emit(dict(leg='fused_bound', L=float(Q.L[Q.iter - 1]),
+                      peak_GB=torch.cuda.max_memory_allocated() / 1e9))
+        else:
+            Q.update(verbose=False)
+        if 'pass' in legs:
+            r = timed(lambda: plan._run_pass(refresh=False), a.steps, a.warmup)
+            steps_total = float(B) * T
+            s = 1e-3 * r['ms_median']
+            emit(dict(leg='pass', what='vmp_hmm_fused_pass_categorical',
+                      bytes_per_chain_step=8 + 16 * K,
+                      GB_per_s=steps_total * (8 + 16 * K) / s / 1e9,
+                      exp_per_chain_step=(3 * K + 2) * K,
+                      Gexp_per_s=steps_total * (3 * K + 2) * K / s / 1e9, **r))
+        del Q, plan
+        torch.cuda.empty_cache()
+    if 'generic' in legs:
+        try:
+            torch.cuda.reset_peak_memory_stats()
+            Q = build_cat(y, z0, K, M, 'generic')
+            emit(dict(leg='generic', what='Q.update()',
+                      **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
+            emit(dict(leg='generic_bound', L=float(Q.L[Q.iter - 1]),
+                      peak_GB=torch.cuda.max_memory_allocated() / 1e9))
+        except (RuntimeError, MemoryError) as exc:         # out of memory at this size
+            emit(dict(leg='generic', error=str(exc)[:200]))
+
+
 def timed(fn, steps, warmup):
     import torch
     for _ in range(warmup):
@@ -88,17 +162,28 @@ def main():
                     help='comma-separated fractions of observed steps for the masked pass')
     ap.add_argument('--ragged', action='store_true',
                     help='masked pass with sequence lengths uniform in 1 ... T')
+    ap.add_argument('--emissions', default='gaussian', choices=('gaussian', 'categorical'))
+    ap.add_argument('--M', type=int, default=16, help='words of the categorical legs')
     a = ap.parse_args()
     import torch
     B, T, D, K = a.B, a.T, a.D, a.K
-    y, mu, z0 = make_data(B, T, D, K)
-    shape = dict(B=B, T=T, D=D, K=K)
+    cat = a.emissions == 'categorical'
+    shape = dict(B=B, T=T, M=a.M, K=K, emissions='categorical') if cat else dict(B=B, T=T, D=D, K=K)
     lines = []
 
     def emit(rec):
         rec = dict(shape, **rec)
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
+
+    if cat:
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'hmm_fused', 'bench_hmm_cat.json')
+        categorical_legs(a, emit)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        return
+    y, mu, z0 = make_data(B, T, D, K)
 
     legs = a.legs.split(',')
     masks = [('observed %g' % float(f), float(f)) for f in (a.observed or '').split(',') if f]
