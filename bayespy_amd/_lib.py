@@ -235,6 +235,11 @@ SIGNATURES = {
     'vmp_bmm_tables': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'vmp_bmm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                              c_vp, c_vp, c_vp]),
+    'vmp_bmm_limits_masked': (c_i32, [P(c_i32), P(c_i32)]),
+    'vmp_bmm_plan_masked': (c_i32, [c_i64, c_i32, c_i32, P(c_i64), P(c_i64)]),
+    'vmp_bmm_pack_masked': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'vmp_bmm_tables_masked': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'vmp_bmm_pass_masked': (c_i32, [c_vp, c_i64, c_i32, c_i32] + [c_vp] * 12),
     'vmp_hmm_fused_limits': (c_i32, [P(c_i32), P(c_i32)]),
     'vmp_hmm_fused_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_hmm_fused_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,

@@ -35,12 +35,38 @@
 // Non-finite tables (a point mass at p0 = 0 or 1 gives w = +-inf and c = -inf) are OUTSIDE the
 // contract: the reference forms 0 * (-inf) = NaN for them as well.  A logit of -inf (padding) gives
 // r = 0 exactly.
+//
+// MISSING OBSERVATIONS (the *_masked entries).  A row carries two bit planes, 2 W words with
+// W = ceil(D / 64): plane 0 = x & m in words 0 .. W-1, plane 1 = the mask m (1 = observed) in words
+// W .. 2W-1, the unused high bits of both zero.  With xm = x & m
+//     l_k = c[k] + sum_d xm_nd w[d, k] + sum_d m_nd l0[d, k],    l0[d, k] = <log(1 - p_dk)>,
+//     c[k] = <log pi_k> - max_k <log pi_k>                       (sum_d l0 is no longer in c),
+//     S_dk = sum_n r_nk xm_nd,  M_dk = sum_n r_nk m_nd,  counts = (S, M - S),
+// the masked broadcast of mixture.py summed over D.  A hidden position is never interpreted: any
+// value, NaN included, may stand there (the reference checks hidden values as well and raises for
+// them).  A ROW WITH NO OBSERVED BIT has r = softmax(c), which is written to r_out when asked for
+// (with labels: the one-hot row), and adds exactly nothing to N_k, sum lse, S and M: the reference
+// masks the row out of the message of Z to R and out of the bound term of Z.
+// Order of the additions of the masked pass:
+//   * logit: starts at zero, adds w[d, k] for the set bits of plane 0 in ascending d, then l0[d, k]
+//     for the set bits of plane 1 in ascending d, and c[k] last;
+//   * the sum under the logarithm, the slots of N_k and sum lse (observed rows only) and the chunks
+//     as above;
+//   * S[k, d] adds r_k of the rows with bit d of plane 0 set, M[k, d] of those with bit d of plane
+//     1 set, in two levels: within a tile of 64 rows from zero in ascending row order, and the
+//     tiles' sums in tile order to the running sum of the chunk.  (The unmasked pass adds row by
+//     row through the chunk; with few distinct rows, as a small D gives, the equal terms of such
+//     a sum round the same way hundreds of times in a row.  At (N, D, K) = (300, 1, 5) that put
+//     S . w + M . l0 at 1.27 times its allowance; in two levels it is at 0.23 of it.);
+//   * the chunks' partial S, M, N_k and sum lse are added in chunk order by a second kernel.
 #pragma once
 
 #include <stdint.h>
 
 #define VMP_BMM_MAX_K 64
 #define VMP_BMM_MAX_D 1024
+#define VMP_BMM_MASKED_MAX_K 64   // the masked pass: the same limits
+#define VMP_BMM_MASKED_MAX_D 1024
 #define VMP_BMM_TILE 64           // rows per tile: 16 per wavefront of a four-wavefront workgroup
 #define VMP_BMM_MIN_CHUNK 256
 #define VMP_BMM_MAX_CHUNKS 1024
@@ -73,6 +99,37 @@ __host__ __device__ inline int64_t vmp_bmm_chunks(int64_t N, int D, int K)
 {
     const int64_t rows = vmp_bmm_chunk_rows(N, D, K);
     return N > 0 ? (N + rows - 1) / rows : 0;
+}
+
+// the masked pass: S (K x D), M (K x D), N_k (K), sum lse (1) per chunk, under the same caps
+__host__ __device__ inline int64_t vmp_bmm_partial_doubles_masked(int D, int K)
+{
+    return 2 * (int64_t)D * K + K + 1;
+}
+
+__host__ __device__ inline int64_t vmp_bmm_chunk_rows_masked(int64_t N, int D, int K)
+{
+    int64_t maxc = ((int64_t)1 << 25) / vmp_bmm_partial_doubles_masked(D, K);
+    if (maxc > VMP_BMM_MAX_CHUNKS) maxc = VMP_BMM_MAX_CHUNKS;
+    if (maxc < 1) maxc = 1;
+    int64_t rows = (N + maxc - 1) / maxc;
+    rows = (rows + VMP_BMM_TILE - 1) / VMP_BMM_TILE * VMP_BMM_TILE;
+    if (rows < VMP_BMM_MIN_CHUNK) rows = VMP_BMM_MIN_CHUNK;
+    return rows;
+}
+
+__host__ __device__ inline int64_t vmp_bmm_chunks_masked(int64_t N, int D, int K)
+{
+    const int64_t rows = vmp_bmm_chunk_rows_masked(N, D, K);
+    return N > 0 ? (N + rows - 1) / rows : 0;
+}
+
+// whether any bit of the mask plane (W words) of a row is set
+__host__ __device__ inline bool vmp_bmm_row_observed(const uint64_t *mask_words, int W)
+{
+    uint64_t any = 0;
+    for (int i = 0; i < W; ++i) any |= mask_words[i];
+    return any != 0;
 }
 
 // slot of row t (0 .. 63) of a tile

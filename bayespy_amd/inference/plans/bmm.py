@@ -4,7 +4,8 @@ Execution plan of the Bernoulli-mixture block (doc/source/examples/bmm.rst)
     R = Dirichlet(const);  Z = Categorical(R, plates=(N, 1))
     P = Beta(const [a, b], plates=(D, K));  X = Mixture(Z, Bernoulli, P);  X.observe(x)
 
-with constant priors, a fully observed ``X``, K <= 64 and D <= 1024.  Opt-in: ``VB(...,
+with constant priors, K <= 64 and D <= 1024; ``X`` fully observed or observed with a mask of the
+full shape (N, D) (below).  Opt-in: ``VB(...,
 engine='fused')``; the default engine runs this model on the generic engine as before.  The plan
 owns, in HBM: ``x`` as bits (ceil(D / 64) words per row), the Beta parameters and moments of ``P``
 as a (D K, 2) table, those of ``R`` (K), the tables w = <log p> - <log(1 - p)> and c = <log pi> +
@@ -17,9 +18,23 @@ All plate terms of the lower bound follow from the statistics, sum_n lse_n and t
     <log p(Z)> + entropy = sum_k N_k <log pi_k>
                            + sum_n lse_n - sum_k N_k c_used[k] - sum_dk S_dk w_used[d, k]
 
+Masks: ``X.observe(x, mask=m)`` with ``m`` a boolean host array or a ``DeviceMask`` of shape
+exactly (N, D).  The row then carries two bit planes, xm = x & m and m (N D / 4 bytes in all), and
+the plan keeps ``M`` and ``l0`` beside ``S`` and ``w``:
+    logit_nk = c[k] + sum_d xm_nd w[d, k] + sum_d m_nd l0[d, k],   l0 = <log(1 - p)>,
+    c = <log pi> (less its maximum),  S_dk = sum_n r_nk xm_nd,  M_dk = sum_n r_nk m_nd,
+    N_k = sum over the rows with an observed entry of r_nk,  message to P = (S, M - S).
+The two bound formulas above hold on these sums with ``counts`` = (S, M - S) for the first and
+S . w + M . l0 for the last product of the second.  A row with nothing observed has ``Z.mask``
+False: its moment is softmax(<log pi>) of the tables the last update used and it enters neither
+N_k nor the bound term of ``Z``.  A hidden position of ``x`` is never read by the kernels.  A
+scalar mask or one that broadcasts over a plate is declined (generic engine).
+
 Checkpoints: the block writes its own ``plans/<i>/`` group (kind 'bmm') like every fused plan.  A
 checkpoint of the generic engine holds the natural parameters of every node, the (N, 1, K) array
-of ``Z`` among them, which this block never keeps; the two are not interchangeable.
+of ``Z`` among them, which this block never keeps; the two are not interchangeable.  A masked plan
+adds ``mask``, ``M`` and ``l0`` and refuses a checkpoint whose mask differs; an unmasked plan
+writes what it always wrote.
 """
 import ctypes
 
@@ -30,7 +45,7 @@ from ._dirichlet import DirichletKernels, prior_table
 
 from ... import _lib
 from ...device import get_runtime, ptr
-from ...nodes.node import Constant
+from ...nodes.node import Constant, DeviceMask
 from ...nodes.dirichlet import Dirichlet
 from ...nodes.beta import Beta
 from ...nodes.categorical import Categorical
@@ -39,8 +54,20 @@ from ...nodes.mixture import Mixture
 
 BMM_MAX_K = 64          # vmp_bmm_limits
 BMM_MAX_D = 1024
+BMM_MASKED_MAX_K = 64   # vmp_bmm_limits_masked as documented; the matcher reads the built values
+BMM_MASKED_MAX_D = 1024
 
 _DTYPES = {'float64': 0, 'int64': 1, 'bool': 2, 'uint8': 2}
+_MASKED_LIMITS = []
+
+
+def bmm_masked_limits():
+    """(max K, max D) of the built masked pass: host-only ``vmp_bmm_limits_masked``."""
+    if not _MASKED_LIMITS:
+        k, d = ctypes.c_int32(), ctypes.c_int32()
+        _lib.raise_for_status(_lib.load().vmp_bmm_limits_masked(ctypes.byref(k), ctypes.byref(d)))
+        _MASKED_LIMITS.append((k.value, d.value))
+    return _MASKED_LIMITS[0]
 
 
 class BMMKernels(DirichletKernels):
@@ -71,6 +98,40 @@ class BMMKernels(DirichletKernels):
         self.rt.check(self.lib.vmp_bmm_pass(self.ctx, N, D, K, p(xw), p(labels), p(w), p(c), p(ws),
                                             p(S), p(Nk), p(counts), p(scal), p(r_out)))
 
+    # -- missing observations: two bit planes per row, tables (w, l0, c), statistics (S, M) --------
+    def plan_masked(self, N, D, K):
+        c, w = ctypes.c_int64(), ctypes.c_int64()
+        rc = self.lib.vmp_bmm_plan_masked(N, D, K, ctypes.byref(c), ctypes.byref(w))
+        if rc != _lib.VMP_OK:
+            _lib.raise_for_status(rc, 'the fused Bernoulli-mixture block with a mask supports '
+                                      'K <= %d and D <= %d' % bmm_masked_limits())
+        return c.value, w.value
+
+    def pack_masked(self, N, D, dtype, x, mask, xw, flag):
+        self.rt.check(self.lib.vmp_bmm_pack_masked(self.ctx, N, D, dtype, ptr(x), ptr(mask),
+                                                   ptr(xw), ptr(flag)))
+
+    def tables_masked(self, D, K, elog_p, elog_pi, w, l0, c):
+        self.rt.check(self.lib.vmp_bmm_tables_masked(self.ctx, D, K,
+                                                     ptr(elog_p) if elog_p is not None else None,
+                                                     ptr(elog_pi), ptr(w), ptr(l0), ptr(c)))
+
+    def pass_masked(self, N, D, K, xw, labels, w, l0, c, ws, S, M, Nk, counts, scal, r_out=None):
+        def p(t):
+            return ptr(t) if t is not None else None
+        self.rt.check(self.lib.vmp_bmm_pass_masked(self.ctx, N, D, K, p(xw), p(labels), p(w),
+                                                   p(l0), p(c), p(ws), p(S), p(M), p(Nk),
+                                                   p(counts), p(scal), p(r_out)))
+
+
+def _mask_shape(mask):
+    return tuple(mask.shape) if isinstance(mask, DeviceMask) else np.shape(mask)
+
+
+def _takes_mask(X):
+    """No mask, or one of the full shape of the plates of ``X``."""
+    return X._mask is True or _mask_shape(X._mask) == tuple(X.plates)
+
 
 def _match(nodes, why):
     for X in nodes:
@@ -100,8 +161,10 @@ def _match(nodes, why):
         if any(getattr(n, '_shard_axis', None) is not None for n in four):
             no('a plate is sharded over ranks')
             continue
-        if X._mask is not True:
-            no('it has a mask')
+        if not _takes_mask(X):
+            no('it has a mask of shape %s: the block takes no mask or a mask of the full shape of '
+               'the plates of X, here %s; a scalar mask or one that broadcasts over a plate goes '
+               'through the generic engine' % (_mask_shape(X._mask), tuple(X.plates)))
             continue
         bad = [n for n in (P, R) if not isinstance(n.parents[0], Constant)]
         if bad:
@@ -120,6 +183,10 @@ def _match(nodes, why):
         if K > BMM_MAX_K or D > BMM_MAX_D:
             no('D = %d, K = %d exceed the limits of the block (D <= %d, K <= %d)'
                % (D, K, BMM_MAX_D, BMM_MAX_K))
+            continue
+        if X._mask is not True and (K > bmm_masked_limits()[0] or D > bmm_masked_limits()[1]):
+            no('D = %d, K = %d exceed the limits of the block with a mask (D <= %d, K <= %d)'
+               % ((D, K) + bmm_masked_limits()[::-1]))
             continue
         kids = ((R, [Z]), (Z, [X]), (P, [X]), (X, []))
         if any([c for c, _ in n.children] != want for n, want in kids):
@@ -143,7 +210,10 @@ class BernoulliMixturePlan:
     @staticmethod
     def describe():
         return ("Mixture(Categorical(Dirichlet(const), plates=(N, 1)), Bernoulli, Beta(const, "
-                "plates=(D, K))), fully observed, D <= %d, K <= %d" % (BMM_MAX_D, BMM_MAX_K))
+                "plates=(D, K))), fully observed (D <= %d, K <= %d) or observed with a mask of "
+                "the full shape (N, D) (D <= %d, K <= %d); a scalar mask or one that broadcasts "
+                "over a plate is declined"
+                % (BMM_MAX_D, BMM_MAX_K, BMM_MASKED_MAX_D, BMM_MASKED_MAX_K))
 
     @staticmethod
     def match(nodes, why=None):
@@ -157,6 +227,7 @@ class BernoulliMixturePlan:
         self._rt, self._kernels = runtime, kernels
         self._ready = False
         self._x_stale = False
+        self.maskd = None           # (N, D) uint8 in HBM when X has a mask
         self._version = 0
         self._L_version = -1
         self._L = None
@@ -182,8 +253,10 @@ class BernoulliMixturePlan:
         return bool(self._ready)
 
     def invalidate(self, node):
-        if node is self.X and node.observed and node._mask is True:
-            # new observations of the same shape: the bits are packed again, the posteriors stay
+        if node is self.X and node.observed and _takes_mask(node) \
+                and (not self._ready or (node._mask is True) == (self.maskd is None)):
+            # new observations of the same shape, with a mask of the full shape or none: the bits
+            # are packed again, the posteriors stay
             self._x_stale = True
             self._version += 1
             return
@@ -196,7 +269,7 @@ class BernoulliMixturePlan:
 
     # -- set-up ------------------------------------------------------------------------------------
     def _pack(self):
-        """``X._data`` as bits; a value that is neither 0 nor 1 is the reference's ValueError
+        """``X._data`` as bits (with ``maskd``, uploaded before: two planes); a value that is neither 0 nor 1 is the reference's ValueError
         (binomial.py, through Bernoulli's observe)."""
         rt, torch = self.rt, self.rt.torch
         N, D = self.N, self.D
@@ -216,16 +289,32 @@ class BernoulliMixturePlan:
             t = t.expand(N, D).contiguous()
         dtype = _DTYPES[str(t.dtype).replace('torch.', '')]
         W = (D + 63) // 64
-        self.xw = torch.zeros(max(N, 1) * W, dtype=torch.int64, device=rt.device)
+        planes = 1 if self.maskd is None else 2
+        self.xw = torch.zeros(max(N, 1) * W * planes, dtype=torch.int64, device=rt.device)
         flag = torch.zeros(1, dtype=torch.int32, device=rt.device)
-        self.kernels.pack(N, D, dtype, t, self.xw, flag)
+        if self.maskd is None:
+            self.kernels.pack(N, D, dtype, t, self.xw, flag)
+        else:
+            self.kernels.pack_masked(N, D, dtype, t, self.maskd, self.xw, flag)
         if int(flag.cpu().numpy()[0]) != 0:
             raise ValueError("Invalid count")
         self._x_stale = False
 
+    def _upload_mask(self):
+        rt, torch = self.rt, self.rt.torch
+        m = self.X._mask
+        if m is True:
+            self.maskd = None
+        elif isinstance(m, DeviceMask):
+            self.maskd = m.tensor.to(rt.device).reshape(self.N, self.D).to(torch.uint8).contiguous()
+        else:
+            self.maskd = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(m, dtype=bool).reshape(self.N, self.D).astype(np.uint8))).to(rt.device)
+
     def _materialize(self):
         if self._ready:
             if self._x_stale:
+                self._upload_mask()
                 self._pack()
                 self._run_pass()
             return
@@ -234,7 +323,9 @@ class BernoulliMixturePlan:
         torch = rt.torch
         N, D, K = self.N, self.D, self.K
         rt.sync_stream()
-        self.chunk, wsd = k.plan(N, D, K)
+        self._upload_mask()
+        masked = self.maskd is not None
+        self.chunk, wsd = k.plan_masked(N, D, K) if masked else k.plan(N, D, K)
         self._pack()
         up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(rt.device)  # noqa: E731
         pp = prior_table(self.P, (D, K, 2)).reshape(D * K, 2)
@@ -244,9 +335,11 @@ class BernoulliMixturePlan:
         self.alpha_r, self.elog_r = rt.empty(K), rt.empty(K)
         self.w, self.c = rt.zeros(D, K), rt.zeros(K)
         self.S, self.Nk, self.counts = rt.zeros(D, K), rt.zeros(K), rt.zeros(D * K, 2)
+        if masked:
+            self.l0, self.M = rt.zeros(D, K), rt.zeros(D, K)
         self.ws = rt.empty(int(wsd))
         self.ws_small = rt.empty(max(D * K, 1024))
-        # [0] sum lse, [1] N_k . c used, [2] S . w used, [3] bound of P, [4] bound of R,
+        # [0] sum lse, [1] N_k . c used, [2] S . w (+ M . l0) used, [3] bound of P, [4] bound of R,
         # [5] counts . <log p>, [6] N_k . <log pi>
         self.scal = rt.zeros(8)
         self._init_table(self.P, pp, D * K, 2, self.prior_p, self.alpha_p, self.elog_p,
@@ -267,7 +360,7 @@ class BernoulliMixturePlan:
             if lab.size and (lab.min() < 0 or lab.max() >= K):
                 raise ValueError("Invalid category index")
             self.labels = torch.from_numpy(lab.astype(np.int32)).to(rt.device)
-        k.tables(D, K, None, self.elog_r, self.w, self.c)
+        self._tables(None)
         self._ready = True
         self._run_pass()
 
@@ -296,10 +389,23 @@ class BernoulliMixturePlan:
         elog.copy_(torch.from_numpy(np.array(e.reshape(rows, cols), order='C')).to(rt.device))
         alpha.fill_(float('nan'))                    # a point mass has no parameters
 
+    def _tables(self, elog_p):
+        """The tables of the pass from ``elog_p`` (None: no observation term) and ``elog_r``."""
+        if self.maskd is None:
+            self.kernels.tables(self.D, self.K, elog_p, self.elog_r, self.w, self.c)
+        else:
+            self.kernels.tables_masked(self.D, self.K, elog_p, self.elog_r, self.w, self.l0,
+                                       self.c)
+
     def _run_pass(self, r_out=None):
         """The statistics of the present ``Z`` state (tables ``w`` / ``c`` or labels)."""
-        self.kernels.pass_(self.N, self.D, self.K, self.xw, self.labels, self.w, self.c, self.ws,
-                           self.S, self.Nk, self.counts, self.scal, r_out)
+        if self.maskd is None:
+            self.kernels.pass_(self.N, self.D, self.K, self.xw, self.labels, self.w, self.c,
+                               self.ws, self.S, self.Nk, self.counts, self.scal, r_out)
+        else:
+            self.kernels.pass_masked(self.N, self.D, self.K, self.xw, self.labels, self.w, self.l0,
+                                     self.c, self.ws, self.S, self.M, self.Nk, self.counts,
+                                     self.scal, r_out)
         self._version += 1
 
     # -- operations ----------------------------------------------------------------------------------
@@ -311,7 +417,7 @@ class BernoulliMixturePlan:
         D, K = self.D, self.K
         if node is self.Z:
             self.labels = None
-            k.tables(D, K, self.elog_p, self.elog_r, self.w, self.c)
+            self._tables(self.elog_p)
             self._run_pass()
         elif node is self.P:
             k.dirichlet(D * K, 2, 2, 1, self.prior_p, self.counts, self.alpha_p, self.elog_p,
@@ -370,8 +476,32 @@ class BernoulliMixturePlan:
             return [np.array(np.broadcast_to(x, (self.N, self.D)), dtype=np.float64)]
         raise NotImplementedError
 
+    def _host_mask(self):
+        """The mask as a boolean host array of shape (N, D), or None without one."""
+        m = self.X._mask
+        return None if m is True else np.asarray(m, dtype=bool).reshape(self.N, self.D)
+
+    def get_mask(self, node):
+        """``X``: its mask; ``Z``: any entry of the row observed, (N, 1); ``P``: any entry of the
+        column observed, (D, 1); ``R``: any entry observed -- the masks the reference propagates
+        from ``X`` to its parents."""
+        m = self._host_mask()
+        if m is None:
+            return np.array(True)
+        if node is self.X:
+            return m.copy()
+        if node is self.Z:
+            return m.any(axis=1)[:, None]
+        if node is self.P:
+            return m.any(axis=0)[:, None]
+        return np.array(bool(m.any()))
+
     # -- persistence -----------------------------------------------------------------------------------
     _SAVED = ('alpha_p', 'elog_p', 'alpha_r', 'elog_r', 'w', 'c', 'S', 'Nk', 'counts', 'scal')
+    _SAVED_MASKED = ('M', 'l0')
+
+    def _saved(self):
+        return self._SAVED + (self._SAVED_MASKED if self.maskd is not None else ())
 
     def save_state(self, put, nodes, index):
         self._materialize()
@@ -382,7 +512,9 @@ class BernoulliMixturePlan:
         put(base + 'flags', np.array([1 if self.labels is not None else 0], dtype=np.int64))
         if self.labels is not None:
             put(base + 'labels', self.labels.cpu().numpy())
-        for name in self._SAVED:
+        if self.maskd is not None:
+            put(base + 'mask', self.maskd.cpu().numpy())
+        for name in self._saved():
             put(base + name, getattr(self, name).cpu().numpy())
 
     def load_state(self, reader, nodes, index):
@@ -395,6 +527,16 @@ class BernoulliMixturePlan:
         if dims != (self.N, self.D, self.K):
             raise ValueError('checkpoint is for (N, D, K) = %s, the model has %s'
                              % (dims, (self.N, self.D, self.K)))
+        saved = np.asarray(reader.get(base + 'mask'), dtype=np.uint8).reshape(-1) \
+            if reader.has(base + 'mask') else None
+        mine = None if self.maskd is None else self.maskd.cpu().numpy().reshape(-1)
+        if (saved is None) != (mine is None) or (saved is not None
+                                                 and not np.array_equal(saved != 0, mine != 0)):
+            raise ValueError('checkpoint was saved with %s, the model has %s: observe X with the '
+                             'mask of the checkpoint before loading it'
+                             % tuple('no mask on X' if m is None else
+                                     'a mask on X with %d of %d entries observed'
+                                     % (int(np.count_nonzero(m)), m.size) for m in (saved, mine)))
         torch = self.rt.torch
         self._delta = _delta.load(reader, base)
         if int(np.asarray(reader.get(base + 'flags')).ravel()[0]):
@@ -402,7 +544,7 @@ class BernoulliMixturePlan:
                 np.array(reader.get(base + 'labels'), dtype=np.int32)).to(self.rt.device)
         else:
             self.labels = None
-        for name in self._SAVED:
+        for name in self._saved():
             getattr(self, name).copy_(torch.from_numpy(
                 np.array(reader.get(base + name), dtype=np.float64)).reshape(
                     getattr(self, name).shape).to(self.rt.device))

@@ -945,6 +945,42 @@ int32_t vmp_bmm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, const uint64
                      const int32_t *labels, const double *w, const double *c, double *ws,
                      double *S, double *Nk, double *counts, double *scal, double *r_out);
 
+/* Bernoulli mixture with missing observations: X.observe(x, mask=m), m of the full shape (N, D),
+ * 1 = observed (details: vmp_bmm_dev.h).  A row is two bit planes, 2 ceil(D / 64) words: x & m,
+ * then m; with xm = x & m
+ *     logit_nk = c[k] + sum_d xm_nd w[d, k] + sum_d m_nd l0[d, k]
+ *     S_dk = sum_n r_nk xm_nd,  M_dk = sum_n r_nk m_nd,  N_k = sum over the observed rows of r_nk.
+ *   vmp_bmm_limits_masked (host only): *max_K = 64, *max_D = 1024.
+ *   vmp_bmm_plan_masked (host only): as vmp_bmm_plan for partials of 2 D K + K + 1 doubles per
+ *     chunk, under the same caps.
+ *   vmp_bmm_pack_masked: x as for vmp_bmm_pack and mask (N x D uint8, non-zero = observed) to
+ *     2 W words per row, W = ceil(D / 64): words 0 .. W-1 hold x & m, words W .. 2W-1 hold m,
+ *     unused high bits zero.  *flag is set only for an OBSERVED value that is neither 0 nor 1.  A
+ *     hidden position is never interpreted: NaN, -1 or 7 may stand there.  (The reference checks
+ *     hidden values as well and raises "Invalid count" for them.)
+ *   vmp_bmm_tables_masked: w[d, k] = <log p> - <log(1 - p)>, l0[d, k] = <log(1 - p)> (both D x K)
+ *     and c[k] = <log pi_k> - max_k <log pi_k>; sum_d l0 is not in c.  elog_p == NULL gives
+ *     w = l0 = 0, the moments of Z under its prior.
+ *   vmp_bmm_pass_masked: the pass of vmp_bmm_pass on the two planes: plane 0 against w in
+ *     ascending d, then plane 1 against l0 in ascending d, then c.  Out: S, M (D x K), Nk (K),
+ *     counts ((D K, 2)) = (S, M - S), scal[0] = sum lse over the observed rows, scal[1] = Nk . c,
+ *     scal[2] = S . w + M . l0; r_out (N x K) if not NULL.  A row with no observed bit has
+ *     r = softmax(c) (with labels: its one-hot row), written to r_out, and adds exactly nothing
+ *     to Nk, sum lse, S and M.  ws: vmp_bmm_plan_masked's doubles.  No atomics: the bits of every
+ *     output depend on the inputs and (N, D, K) only, with or without r_out and whatever stands
+ *     at hidden positions.  Limits and argument errors as for vmp_bmm_pass. */
+int32_t vmp_bmm_limits_masked(int32_t *max_K, int32_t *max_D);
+int32_t vmp_bmm_plan_masked(int64_t N, int32_t D, int32_t K, int64_t *chunk_rows,
+                            int64_t *workspace_doubles);
+int32_t vmp_bmm_pack_masked(vmp_ctx *ctx, int64_t N, int32_t D, int32_t dtype, const void *x,
+                            const uint8_t *mask, uint64_t *xw, int32_t *flag);
+int32_t vmp_bmm_tables_masked(vmp_ctx *ctx, int32_t D, int32_t K, const double *elog_p,
+                              const double *elog_pi, double *w, double *l0, double *c);
+int32_t vmp_bmm_pass_masked(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, const uint64_t *xw,
+                            const int32_t *labels, const double *w, const double *l0,
+                            const double *c, double *ws, double *S, double *M, double *Nk,
+                            double *counts, double *scal, double *r_out);
+
 /* Hidden Markov model with Gaussian emissions: the chain pass of the fused block
  * (doc/source/examples/hmm.rst; details: bayespy_amd/csrc/vmp_hmm_fused.hip, vmp_hmm_fused_dev.h).
  * B chains of T time instances, D-dimensional observations, K states.  No (B, T-1, K, K) array is

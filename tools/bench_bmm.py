@@ -6,9 +6,11 @@ Timed legs of the fused Bernoulli-mixture block (inference/plans/bmm.py); one JS
        D = 1024, K = 64, with the pass kernel's share (``vmp_bmm_pass`` timed alone on the same
        state) and its fraction of the fp64 matrix peak (4 N D K flops);
   (ii) at N = 1e5, D = 64, K = 32 the fused block against the generic engine (the largest size at
-       which the generic engine's (N, D, K) arrays, 1.6 GB each, fit comfortably).
+       which the generic engine's (N, D, K) arrays, 1.6 GB each, fit comfortably);
+  (m)  the same three legs with 30 % of the entries hidden by a mask of the full shape (m1, m2,
+       mii): the masked pass does twice the matrix work (8 N D K flops).
 
-    python tools/bench_bmm.py [--legs i1,i2,ii] [--steps 10] [--warmup 3] [--out profiles/...json]
+    python tools/bench_bmm.py [--legs i1,i2,ii,m1,m2,mii] [--steps 10] [--warmup 3] [--out profiles/...json]
 
 Every leg warms up, then times ``steps`` updates one by one between device synchronisations and
 reports the median and the spread.
@@ -40,7 +42,18 @@ def make_data(N, D, K, seed=0):
     return x.cpu().numpy()          # observe() checks host arrays; the plan uploads the bits
 
 
-def build(x, K, engine):
+def make_mask(N, D, hidden, seed=1):
+    import torch
+    g = torch.Generator(device='cuda').manual_seed(seed)
+    m = torch.empty(N, D, dtype=torch.bool, device='cuda')
+    step = max(1, (1 << 24) // D)
+    for lo in range(0, N, step):
+        hi = min(N, lo + step)
+        m[lo:hi] = torch.rand(hi - lo, D, device='cuda', generator=g) >= hidden
+    return m.cpu().numpy()
+
+
+def build(x, K, engine, mask=None):
     from bayespy_amd import nodes
     from bayespy_amd.inference import VB
     N, D = x.shape
@@ -48,7 +61,10 @@ def build(x, K, engine):
     Z = nodes.Categorical(R, plates=(N, 1), name='Z')
     P = nodes.Beta([0.5, 0.5], plates=(D, K), name='P')
     X = nodes.Mixture(Z, nodes.Bernoulli, P, name='X')
-    X.observe(x)
+    if mask is None:
+        X.observe(x)
+    else:
+        X.observe(x * mask, mask=mask)
     P.initialize_from_random()
     return VB(Z, R, X, P, engine=engine)
 
@@ -69,15 +85,16 @@ def timed(fn, steps, warmup):
                 steps=steps, warmup=warmup)
 
 
-def leg_fused(tag, N, D, K, steps, warmup):
+def leg_fused(tag, N, D, K, steps, warmup, hidden=0.0):
     import torch
     x = make_data(N, D, K)
-    Q = build(x, K, 'fused')
+    mask = make_mask(N, D, hidden) if hidden else None
+    Q = build(x, K, 'fused', mask)
     plan = Q.plans[0]
     upd = timed(lambda: Q.update(verbose=False), steps, warmup)
     pas = timed(lambda: plan._run_pass(), steps, warmup)
-    flops = 4.0 * N * D * K
-    out = dict(leg=tag, engine='fused', N=N, D=D, K=K, update=upd, pass_alone=pas,
+    flops = (8.0 if hidden else 4.0) * N * D * K
+    out = dict(leg=tag, engine='fused', N=N, D=D, K=K, hidden=hidden, update=upd, pass_alone=pas,
                pass_share=pas['median_ms'] / upd['median_ms'],
                pass_tflops=flops / (pas['median_ms'] * 1e-3) / 1e12,
                chunk_rows=int(plan.chunk), x_bytes=int(plan.xw.numel() * 8),
@@ -86,11 +103,12 @@ def leg_fused(tag, N, D, K, steps, warmup):
     return out
 
 
-def leg_compare(N, D, K, steps, warmup):
+def leg_compare(N, D, K, steps, warmup, hidden=0.0):
     x = make_data(N, D, K)
-    out = dict(leg='ii', N=N, D=D, K=K)
+    mask = make_mask(N, D, hidden) if hidden else None
+    out = dict(leg='mii' if hidden else 'ii', N=N, D=D, K=K, hidden=hidden)
     for engine in ('fused', 'generic'):
-        Q = build(x if engine == 'fused' else x.astype(np.int64), K, engine)
+        Q = build(x if engine == 'fused' else x.astype(np.int64), K, engine, mask)
         out[engine] = timed(lambda: Q.update(verbose=False), steps, warmup)
         out[engine]['plan'] = type(Q.plans[0]).__name__
     out['generic_over_fused'] = out['generic']['median_ms'] / out['fused']['median_ms']
@@ -113,6 +131,12 @@ def main():
             r = leg_fused('i2', 10 ** 6, 1024, 64, a.steps, a.warmup)
         elif leg == 'ii':
             r = leg_compare(10 ** 5, 64, 32, a.steps, a.warmup)
+        elif leg == 'm1':
+            r = leg_fused('m1', 10 ** 7, 64, 32, a.steps, a.warmup, hidden=0.3)
+        elif leg == 'm2':
+            r = leg_fused('m2', 10 ** 6, 1024, 64, a.steps, a.warmup, hidden=0.3)
+        elif leg == 'mii':
+            r = leg_compare(10 ** 5, 64, 32, a.steps, a.warmup, hidden=0.3)
         else:
             raise SystemExit('unknown leg %r' % leg)
         lines.append(json.dumps(r))
