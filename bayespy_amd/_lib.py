@@ -189,6 +189,8 @@ SIGNATURES = {
     'vmp_gmm_prepare_z': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp]),
     'vmp_gmm_pass': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'vmp_gmm_update_alpha': (c_i32, [c_vp, c_i32, c_i32, c_vp]),
+    'vmp_gmm_natural_init': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    'vmp_gmm_natural_step': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_vp, c_vp]),
     'vmp_gmm_lower_bound': (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     'vmp_sum_multiply': (c_i32, [c_vp, c_i32, P(c_i64), c_i32, P(c_vp), P(c_i64), P(c_i64),
                                  ctypes.c_uint32, c_f64, c_vp, c_vp, c_sz]),

@@ -655,6 +655,151 @@ gmm_update_lambda_kernel(vmp_gmm_layout L, int D, int K, double *st)
     }
 }
 
+// Stochastic variational inference (vmp.py:432-440): one step of length `scale` along the natural
+// gradients of the global nodes in `nodes` (1 = mu, 2 = Lambda, 4 = alpha), the statistics T of a
+// mini-batch standing for `mult` times as many rows:  phi <- phi + scale (phi* - phi)  with
+//   mu      Lambda_mu* = beta0 I + m R <Lambda_k>,  h* = m <Lambda_k> S1            (phi: h, Lambda_mu)
+//   Lambda  n* = n0 + m R,  V* = V0 + m (S2 - S1 <mu>^T - <mu> S1^T + R <mu mu^T>)   (off_nk, off_Vk)
+//   alpha   alpha* = alpha0 + m R_k                                                 (off_alpha)
+// and the moments of every stepped node formed again from its new parameters.  The state keeps
+// only moments of mu, so its natural parameters live in `phi` ([K][D + D*D]: h_k, then Lambda_mu,k).
+// EVERY optimum is taken from the moments present at entry: a cluster reads all it needs -- what
+// another lane will overwrite goes through LDS or stays in the lane that overwrites it -- before
+// the group's fence, and writes only after it.  scale == 1 takes phi* itself; with mult == 1 the
+// step of one node is then gmm_update_mu / _lambda / _alpha_kernel operation for operation
+// (1 * x and fma(1, x, y) are exact), so the results agree bit for bit.
+constexpr int STEP_MU = 1, STEP_LAMBDA = 2, STEP_ALPHA = 4;
+
+template <int WPC>
+__global__ void __launch_bounds__(grp_threads(WPC))
+gmm_natural_step_kernel(vmp_gmm_layout L, int D, int K, int nodes, double mult, double scale,
+                        double *st, double *phi)
+{
+    constexpr int TPC = 64 * WPC, CPB = grp_threads(WPC) / TPC;
+    __shared__ double Ms[CPB][TPC];
+    __shared__ double Cs[CPB][TPC];
+    __shared__ double hs[CPB][MAXD];      // new h_k
+    __shared__ double mus[CPB][MAXD];     // <mu_k> at entry
+    __shared__ double s1s[CPB][MAXD];     // m S1_k
+    __shared__ double nks[CPB];           // n_k at entry
+    const int w = threadIdx.x / TPC, l = threadIdx.x % TPC;
+    const int k = blockIdx.x * CPB + w;
+    const bool act = (k < K) && (l < D * D);
+    const int i = act ? l / D : 0, j = act ? l - i * D : 0;
+    const int kk = k < K ? k : 0;
+    const bool full = scale == 1.0;
+
+    // alpha: all clusters at once in the first wavefront of the first workgroup (nothing else
+    // reads or writes the Dirichlet slots); the sum is the wavefront sum of gmm_update_alpha_kernel
+    if ((nodes & STEP_ALPHA) && blockIdx.x == 0 && threadIdx.x < 64) {
+        const int c = threadIdx.x;
+        double a = 0.0;
+        if (c < K) {
+            a = st[L.off_prior + c] + mult * st[L.off_T + (int64_t)c * L.FS];    // alpha0 + m R_k
+            if (!full) {
+                const double old = st[L.off_alpha + c];
+                a = old + scale * (a - old);
+            }
+            st[L.off_alpha + c] = a;
+        }
+        const double ps = vmp_digamma(__shfl(wave_sum(a), 0, 64));
+        if (c < K) st[L.off_alpha + L.KP + c] = vmp_digamma(a) - ps;             // dirichlet.py:150-152
+    }
+    if (!(nodes & (STEP_MU | STEP_LAMBDA))) return;
+
+    const double beta0 = st[L.off_prior + L.KP + 0], n0 = st[L.off_prior + L.KP + 1];
+    const double *V0 = st + L.off_prior + L.KP + 8;
+    const double *T = st + L.off_T + (int64_t)kk * L.FS;
+    double *Lam = st + L.off_Lam + (int64_t)kk * D * D;
+    double *mu = st + L.off_mu + (int64_t)kk * D;
+    double *Cmu = st + L.off_Cmu + (int64_t)kk * D * D;
+    double *Vk = st + L.off_Vk + (int64_t)kk * D * D;
+    double *ph = phi + (int64_t)kk * (D + D * D);
+    const double R = mult * T[0];
+
+    // ---- read: the moments, parameters and statistics at entry ---------------------------------
+    double lam_old = 0.0, cmu_old = 0.0, v_old = 0.0, pl_old = 0.0, t2 = 0.0, v0 = 0.0;
+    if (act) {
+        lam_old = Lam[l];
+        cmu_old = Cmu[l];
+        v_old = Vk[l];
+        pl_old = ph[D + l];
+        t2 = mult * T[1 + D + l];
+        v0 = V0[l];
+    }
+    if (k < K && l < D) {
+        mus[w][l] = mu[l];
+        s1s[w][l] = mult * T[1 + l];
+        double s = 0.0;
+        for (int c = 0; c < D; ++c) s += Lam[l * D + c] * (mult * T[1 + c]);     // m <Lambda> S1
+        if (!full) {
+            const double old = ph[l];
+            s = old + scale * (s - old);
+        }
+        hs[w][l] = s;
+    }
+    if (l == 0) nks[w] = st[L.off_nk + kk];
+    grp_sync<WPC>();
+
+    int bad = 0;
+    if (nodes & STEP_MU) {
+        double v = act ? R * lam_old + ((i == j) ? beta0 : 0.0) : 0.0;
+        if (act && !full) v = pl_old + scale * (v - pl_old);
+        if (act) ph[D + l] = v;
+        double ld;
+        v = grp_spd_inverse<WPC>(v, D, i, j, act, l, Ms[w], &ld, &bad);
+        Cs[w][l] = v;
+        grp_sync<WPC>();
+        if (act) Cmu[l] = v;
+        if (k < K && l < D) {
+            double s = 0.0;
+            for (int c = 0; c < D; ++c) s += Cs[w][l * D + c] * hs[w][c];
+            mu[l] = s;
+            ph[l] = hs[w][l];
+        }
+        if (k < K && l == 0) st[L.off_logdetLmu + k] = ld;
+    }
+    if (nodes & STEP_LAMBDA) {
+        double nk = n0 + R;
+        if (!full) nk = nks[w] + scale * (nk - nks[w]);
+        double v = 0.0;
+        if (act) {
+            const double mm = cmu_old + mus[w][i] * mus[w][j];
+            v = v0 + t2 - s1s[w][i] * mus[w][j] - mus[w][i] * s1s[w][j] + R * mm;
+            if (!full) v = v_old + scale * (v - v_old);
+            Vk[l] = v;
+        }
+        // symmetrise before factorising
+        Ms[w][l] = v;
+        grp_sync<WPC>();
+        if (act) v = 0.5 * (Ms[w][i * D + j] + Ms[w][j * D + i]);
+        grp_sync<WPC>();
+        double ld;
+        v = grp_spd_inverse<WPC>(v, D, i, j, act, l, Ms[w], &ld, &bad);
+        if (act) Lam[l] = nk * v;                                               // wishart.py:184
+        if (k < K && l == 0) {
+            double md = 0.0;
+            for (int c = 0; c < D; ++c) md += vmp_digamma(0.5 * nk - 0.5 * c);  // utils/misc.py:1146
+            st[L.off_nk + k] = nk;
+            st[L.off_logdetV + k] = ld;
+            st[L.off_logdetLam + k] = md + (double)D * log(2.0) - ld;           // wishart.py:185
+        }
+    }
+    if (k < K && l == 0 && bad) st[L.off_scal + 3] = (double)VMP_ERR_NOT_POSDEF;
+}
+
+// q(mu_k) at its prior in natural parameters: h = 0, Lambda_mu = beta0 I
+__global__ void __launch_bounds__(NT)
+gmm_natural_init_kernel(vmp_gmm_layout L, int D, int K, const double *st, double *phi)
+{
+    const double beta0 = st[L.off_prior + L.KP + 0];
+    const int per = D + D * D;
+    for (int e = blockIdx.x * NT + threadIdx.x; e < K * per; e += gridDim.x * NT) {
+        const int c = e % per - D;
+        phi[e] = (c >= 0 && c / D == c % D) ? beta0 : 0.0;
+    }
+}
+
 // c_k of E[log N(y | mu_k, Lambda_k)] without the data terms
 __device__ inline double gmm_ck(const double *st, const vmp_gmm_layout &L, int D, int k)
 {
@@ -1086,6 +1231,40 @@ int32_t vmp_gmm_update_alpha(vmp_ctx *ctx, int32_t D, int32_t K, double *state)
 {
     VMP_GMM_PROLOGUE();
     hipLaunchKernelGGL(gmm_update_alpha_kernel, dim3(1), dim3(NT), 0, ctx->stream, L, D, K, state);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+int32_t vmp_gmm_natural_init(vmp_ctx *ctx, int32_t D, int32_t K, const double *state,
+                             double *phi_mu)
+{
+    VMP_GMM_PROLOGUE();
+    VMP_REQUIRE(ctx, phi_mu, VMP_ERR_INVALID, "null argument");
+    const int n = K * (D + D * D);
+    hipLaunchKernelGGL(gmm_natural_init_kernel, dim3((n + NT - 1) / NT), dim3(NT), 0, ctx->stream,
+                       L, D, K, state, phi_mu);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+int32_t vmp_gmm_natural_step(vmp_ctx *ctx, int32_t D, int32_t K, int32_t nodes, double mult,
+                             double scale, double *state, double *phi_mu)
+{
+    VMP_GMM_PROLOGUE();
+    VMP_REQUIRE(ctx, phi_mu, VMP_ERR_INVALID, "null argument");
+    VMP_REQUIRE(ctx, nodes >= 1 && nodes <= (STEP_MU | STEP_LAMBDA | STEP_ALPHA), VMP_ERR_INVALID,
+                "nodes is a bit set of 1 (mu), 2 (Lambda), 4 (alpha), got %d", nodes);
+    VMP_REQUIRE(ctx, mult > 0 && mult < INFINITY && scale == scale && fabs(scale) < INFINITY,
+                VMP_ERR_INVALID, "bad multiplier %g or step length %g", mult, scale);
+    if (D * D <= 64)
+        hipLaunchKernelGGL(gmm_natural_step_kernel<1>, dim3((K + 3) / 4), dim3(NT), 0, ctx->stream,
+                           L, D, K, nodes, mult, scale, state, phi_mu);
+    else if (D * D <= 256)
+        hipLaunchKernelGGL(gmm_natural_step_kernel<4>, dim3(K), dim3(NT), 0, ctx->stream, L, D, K,
+                           nodes, mult, scale, state, phi_mu);
+    else
+        hipLaunchKernelGGL(gmm_natural_step_kernel<16>, dim3(K), dim3(1024), 0, ctx->stream, L, D,
+                           K, nodes, mult, scale, state, phi_mu);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }

@@ -5,7 +5,7 @@ block and maps the reference's per-node operations (``update``,
 """
 from .pca import PCAPlan
 from .masked_pca import MaskedPCAPlan
-from .gmm import GMMPlan
+from .gmm import GMMPlan, GMMSVIPlan
 from .lssm import LSSMPlan
 from .lssm_masked import MaskedLSSMPlan
 from .lda import LDAPlan, LDASVIPlan
@@ -22,6 +22,9 @@ OPT_IN_TYPES = [BernoulliMixturePlan, HMMPlan]
 # right after that block (the block itself declines them with a reason, so they join neither list
 # above: CategoricalHMMPlan is HMMPlan with a table lookup in place of the Gaussian quadratic form)
 OPT_IN_EMISSIONS = {HMMPlan: [CategoricalHMMPlan]}
+# engine='fused': further forms of a default block, tried right after it -- the block keeps
+# whatever it matches (GMMSVIPlan takes the mixture under mini-batches, which GMMPlan declines)
+OPT_IN_AFTER = {GMMPlan: [GMMSVIPlan]}
 
 
 def opt_in_types():
@@ -51,6 +54,7 @@ def _reusable_plans(nodes, engine, options=None):
     if engine == 'fused' and any(isinstance(p, GenericPlan) for p in plans):
         return None
     if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values() or type(p) in opt_in_types()
+                                 or any(type(p) in v for v in OPT_IN_AFTER.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -100,8 +104,8 @@ def compile_model(nodes, engine=None, **options):
         plan = GenericPlan(nodes)
         plan._engine_request = 'generic'
         return [plan]
-    types = [OPT_IN_FORMS.get(P, P) for P in PLAN_TYPES] + opt_in_types() if engine == 'fused' \
-        else PLAN_TYPES
+    types = [Q for P in PLAN_TYPES for Q in [OPT_IN_FORMS.get(P, P)] + OPT_IN_AFTER.get(P, [])] \
+        + opt_in_types() if engine == 'fused' else PLAN_TYPES
     remaining = [n for n in nodes]
     plans = []
     progress = True

@@ -75,6 +75,13 @@ class GMMKernels:
     def lower_bound(self, D, K, state):
         self.rt.check(self.lib.vmp_gmm_lower_bound(self.ctx, D, K, ptr(state)))
 
+    def natural_init(self, D, K, state, phi_mu):
+        self.rt.check(self.lib.vmp_gmm_natural_init(self.ctx, D, K, ptr(state), ptr(phi_mu)))
+
+    def natural_step(self, D, K, nodes, mult, scale, state, phi_mu):
+        self.rt.check(self.lib.vmp_gmm_natural_step(self.ctx, D, K, int(nodes), float(mult),
+                                                    float(scale), ptr(state), ptr(phi_mu)))
+
     def set_timing(self, on):
         self.rt.check(self.lib.vmp_ctx_set_timing(self.ctx, 1 if on else 0))
 
@@ -93,6 +100,8 @@ class GMMKernels:
 
 
 class GMMPlan:
+
+    KIND = 'gmm'            # of its checkpoints
 
     @staticmethod
     def describe():
@@ -157,13 +166,11 @@ class GMMPlan:
     def __init__(self, roles, runtime=None, kernels=None):
         self.roles = roles
         self.Y, self.z, self.mu = roles['Y'], roles['z'], roles['mu']
-        self.Lam, self.alpha = roles['Lambda'], roles['alpha']
+        self.Lam, self.alpha = roles.get('Lambda'), roles['alpha']
         self.N = self.Y.plates[0]
         self.K, self.D = self.Y.clusters, self.Y.dims[0][0]
         self.alpha0 = np.broadcast_to(self.alpha.parents[0].value, (self.K,)).astype(np.float64)
-        self.beta0 = self.mu.parents[1].scalar()
-        self.n0 = self.Lam.parents[0].scalar()
-        self.V0 = np.array(self.Lam.parents[1].value, dtype=np.float64)
+        self._read_priors()
         self._rt, self._kernels = runtime, kernels
         self._ready = False
         self._version = 0
@@ -171,6 +178,11 @@ class GMMPlan:
         self._L = None
         for n in roles.values():
             n._plan = self
+
+    def _read_priors(self):
+        self.beta0 = self.mu.parents[1].scalar()
+        self.n0 = self.Lam.parents[0].scalar()
+        self.V0 = np.array(self.Lam.parents[1].value, dtype=np.float64)
 
     @property
     def rt(self):
@@ -208,6 +220,15 @@ class GMMPlan:
         self.rt.all_reduce_sum_(self.state[L.off_T:L.off_T + L.len_T])
         self.rt.all_reduce_sum_(self.state[L.off_zs:L.off_zs + 2])
 
+    def _check_initialisations(self):
+        for n in (self.mu, self.Lam, self.alpha):
+            if n._init is not None or n.observed:
+                raise NotImplementedError('the fused GMM block initialises mu, Lambda and alpha '
+                                          'from their priors')
+
+    def _initialise_globals(self):
+        """After ``init_state``: what a form of the block sets besides the priors."""
+
     def _materialize(self):
         if self._ready:
             return
@@ -217,10 +238,7 @@ class GMMPlan:
         N, D, K = self.N, self.D, self.K
         if self.Y._data is None:
             raise ValueError('Node %s has not been observed' % self.Y.name)
-        for n in (self.mu, self.Lam, self.alpha):
-            if n._init is not None or n.observed:
-                raise NotImplementedError('the fused GMM block initialises mu, Lambda and alpha '
-                                          'from their priors')
+        self._check_initialisations()
         rt.sync_stream()
         self.layout = L = k.layout(D, K)
         y = self.Y._data
@@ -234,6 +252,7 @@ class GMMPlan:
         self.state = rt.zeros(int(L.total))
         self.ws = rt.empty(int(k.workspace_doubles(D, K)))
         k.init_state(D, K, self.alpha0, self.beta0, self.n0, self.V0, self.state)
+        self._initialise_globals()
         init = self.z._init
         if init is None:
             k.prepare_z(D, K, True, self.state)
@@ -294,7 +313,7 @@ class GMMPlan:
     def lower_bound_contribution(self, node):
         terms = self._lower_bound_terms()
         for key in ('Y', 'z', 'alpha', 'mu', 'Lambda'):
-            if node is self.roles[key]:
+            if node is self.roles.get(key):
                 return terms[key]
         return 0.0
 
@@ -307,7 +326,7 @@ class GMMPlan:
         self._materialize()
         base = 'plans/%d/' % index
         _delta.save(put, base, self._delta)
-        put(base + 'kind', np.array([ord(c) for c in 'gmm'], dtype=np.uint8))
+        put(base + 'kind', np.array([ord(c) for c in self.KIND], dtype=np.uint8))
         put(base + 'dims', np.array([self.N, self.D, self.K], dtype=np.int64))
         put(base + 'state', self.state.cpu().numpy())
         put(base + 'R', self.Rd.cpu().numpy())
@@ -318,6 +337,12 @@ class GMMPlan:
         self._delta = _delta.load(reader, base)
         if not reader.has(base + 'state'):
             raise Exception("File does not contain the state of the fused mixture block")
+        if reader.has(base + 'kind'):
+            kind = ''.join(chr(int(c)) for c in np.asarray(reader.get(base + 'kind')).ravel())
+            if kind != self.KIND:
+                raise ValueError("the checkpoint holds the state of a fused block of kind '%s'; this "
+                                 "model runs on %s (kind '%s') -- load it into a model built the "
+                                 "same way" % (kind, type(self).__name__, self.KIND))
         dims = tuple(int(v) for v in reader.get(base + 'dims'))
         if dims != (self.N, self.D, self.K):
             raise ValueError('checkpoint is for (N, D, K) = %s, the model has %s'
@@ -361,3 +386,334 @@ class GMMPlan:
 
     def pass_times_ms(self, cap=64):
         return self.kernels.pass_times_ms(cap)
+
+
+# ---- stochastic variational inference -----------------------------------------------------------
+
+STEP_MU, STEP_LAMBDA, STEP_ALPHA = 1, 2, 4          # the bit set of vmp_gmm_natural_step
+
+
+def _scalar_multiplier(node):
+    """The one factor of a node with at most one plate axis, or None."""
+    m = tuple(np.ravel(node.plates_multiplier))
+    if len(m) > 1:
+        return None
+    return float(m[0]) if m else 1.0
+
+
+def _batch_multiplier(Y, z, globals_):
+    """What is wrong with the plate multipliers of the block's nodes (a reason), or None."""
+    if any(any(m != 1 for m in n.plates_multiplier) for n in globals_):
+        return ('a global node (mu, Lambda or alpha) carries a plates_multiplier; only the '
+                'mini-batch plate of z and Y may')
+    mz, my = _scalar_multiplier(z), _scalar_multiplier(Y)
+    if mz is None or my is None or not (mz > 0 and my > 0) or mz != my:
+        return ('the plates_multiplier of z / Y is not one positive factor: %s, %s'
+                % (tuple(z.plates_multiplier), tuple(Y.plates_multiplier)))
+    return None
+
+
+def _mean_prior(mu, D):
+    """beta0 of a prior N(0, beta0 I) with constants on the means, or a reason (str)."""
+    m0, b0 = mu.parents
+    if not (isinstance(m0, Constant) and isinstance(b0, Constant)):
+        return 'the prior of the means has parents that are nodes, not constants'
+    if np.any(m0.value):
+        return 'the prior mean of the means is not zero'
+    if isinstance(mu, GaussianARD):
+        b = np.asarray(b0.value, dtype=np.float64)
+        if b.size == 0 or np.any(b != b.reshape(-1)[0]):
+            return 'the prior precision of the means is not a scalar multiple of the identity'
+        return float(b.reshape(-1)[0])
+    P = np.asarray(b0.value, dtype=np.float64)
+    if P.ndim < 2 or P.shape[-2:] != (D, D):
+        return 'the prior precision of the means is not (D, D)'
+    c = float(P.reshape(-1)[0])
+    if not np.array_equal(P, np.broadcast_to(c * np.identity(D), P.shape)):
+        return 'the prior precision of the means is not a scalar multiple of the identity'
+    return c
+
+
+class GMMSVIPlan(GMMPlan):
+    """The block under stochastic variational inference (bayespy/demos/stochastic_inference.py):
+    ``z`` and ``Y`` hold a mini-batch of N rows that stands for ``m`` times as many
+    (``plates_multiplier``), every step re-observes ``Y`` -- the device state stays -- and updates
+    ``z`` (one pass over the batch), and ``gradient_step`` moves mu, Lambda and alpha along their
+    natural gradients in one launch (``vmp_gmm_natural_step``).  The means may be written
+    ``Gaussian(zeros(D), c I)`` and start from a value or a random draw, the precision may be a
+    constant.  Opt-in: ``VB(..., engine='fused')``, tried after ``GMMPlan``."""
+
+    KIND = 'gmm_svi'
+
+    @staticmethod
+    def describe():
+        return ("Mixture(Categorical(Dirichlet(const), plates_multiplier=(m,)), Gaussian, "
+                "GaussianARD(0, c, shape=(D,), plates=(K,)) or Gaussian(zeros(D), c I, plates=(K,)), "
+                "Wishart(const, const, plates=(K,)) or a constant SPD (D, D) / (K, D, D) array), "
+                "fully observed mini-batches, D <= 32, K <= 64")
+
+    @staticmethod
+    def match(nodes, why=None):
+        def no(Y, msg):
+            if why is not None:
+                why.append('fused Gaussian-mixture block (stochastic VI), observed node %s: %s'
+                           % (Y.name or '<unnamed>', msg))
+        for Y in nodes:
+            if not isinstance(Y, Mixture) or Y.node_class is not Gaussian:
+                continue
+            if len(Y.parents) != 3 or len(Y.plates) != 1:
+                no(Y, 'it needs plates (N,) and parents (z, mu, Lambda)')
+                continue
+            if Y._mask is not True:
+                no(Y, 'it has missing values (a mask)')
+                continue
+            z, mu, Lam = Y.parents
+            const_lam = isinstance(Lam, Constant)
+            if not (isinstance(z, Categorical) and type(mu) in (GaussianARD, Gaussian)
+                    and (const_lam or isinstance(Lam, Wishart))):
+                no(Y, 'its parents are not (Categorical, GaussianARD or Gaussian, Wishart or a '
+                      'constant array)')
+                continue
+            alpha = z.parents[0]
+            if not (isinstance(alpha, Dirichlet) and all(p == 1 for p in alpha.plates)):
+                no(Y, 'the assignment prior is not one Dirichlet node')
+                continue
+            if not isinstance(alpha.parents[0], Constant):
+                no(Y, 'the concentration of the assignment prior is a node (%s), not a constant'
+                      % type(alpha.parents[0]).__name__)
+                continue
+            latent = [z, mu, alpha] + ([] if const_lam else [Lam])
+            if not all(any(n is m for m in nodes) for n in latent):
+                continue
+            if any(getattr(n, '_shard_axis', None) is not None for n in latent + [Y]):
+                no(Y, 'its plates are sharded over ranks (Node.shard)')
+                continue
+            N = Y.plates[0]
+            K, D = Y.clusters, Y.dims[0][0]
+            if D > 32 or K > 64:
+                no(Y, 'D = %d, K = %d exceed the limits of the block (D <= 32, K <= 64)' % (D, K))
+                continue
+            if z.plates != (N,) or mu.plates != (K,) or tuple(mu.dims[0]) != (D,) \
+                    or (not const_lam and Lam.plates != (K,)):
+                no(Y, 'plates of z / mu / Lambda are not (N,), (K,), (K,)')
+                continue
+            bad = _batch_multiplier(Y, z, latent[1:])
+            if bad:
+                no(Y, bad)
+                continue
+            beta0 = _mean_prior(mu, D)
+            if isinstance(beta0, str):
+                no(Y, beta0)
+                continue
+            if const_lam:
+                P = np.asarray(Lam.value, dtype=np.float64)
+                if P.shape not in ((D, D), (K, D, D)):
+                    no(Y, 'the constant precision is not a (D, D) or (K, D, D) array')
+                    continue
+                spd = np.array_equal(P, np.swapaxes(P, -1, -2))
+                if spd:
+                    try:
+                        np.linalg.cholesky(P)
+                    except np.linalg.LinAlgError:
+                        spd = False
+                if not spd:
+                    no(Y, 'the constant precision is not symmetric positive definite')
+                    continue
+            else:
+                n0, V0 = Lam.parents
+                if not (isinstance(n0, Constant) and isinstance(V0, Constant) and n0.is_scalar()
+                        and V0.value.shape == (D, D)):
+                    no(Y, 'the Wishart prior is not (scalar degrees, one D x D scale)')
+                    continue
+            if any(len(n.children) != 1 for n in latent) or Y.children:
+                no(Y, 'one of its roles has other children as well')
+                continue
+            roles = dict(Y=Y, z=z, mu=mu, alpha=alpha)
+            if not const_lam:
+                roles['Lambda'] = Lam
+            return roles
+        return None
+
+    def __init__(self, roles, runtime=None, kernels=None):
+        super().__init__(roles, runtime=runtime, kernels=kernels)
+        self._m_seen = _scalar_multiplier(self.z)
+        self._z_init_seen = None
+        self._Ybuf = None
+
+    def _read_priors(self):
+        D = self.D
+        self.beta0 = _mean_prior(self.mu, D)
+        if self.Lam is not None:
+            self.n0 = self.Lam.parents[0].scalar()
+            self.V0 = np.array(self.Lam.parents[1].value, dtype=np.float64)
+            self.Lam_const = None
+        else:
+            # a constant precision sits in the slots of <Lambda>, <log|Lambda|>; the Wishart slots
+            # hold a placeholder that nothing steps and whose bound term is not read
+            self.n0, self.V0 = float(D), np.identity(D)
+            P = np.asarray(self.Y.parents[2].value, dtype=np.float64)
+            self.Lam_const = np.array(np.broadcast_to(P, (self.K, D, D)), order='C')
+
+    # -- state -----------------------------------------------------------------------------------
+    def _multiplier(self):
+        """The multiplier of the mini-batch plate as the nodes carry it now (it has a setter)."""
+        bad = _batch_multiplier(self.Y, self.z, [n for n in (self.mu, self.Lam, self.alpha)
+                                                 if n is not None])
+        if bad:
+            raise ValueError('fused Gaussian-mixture block: ' + bad)
+        return _scalar_multiplier(self.z)
+
+    def _is_device_batch(self, y):
+        torch = self.rt.torch
+        return isinstance(y, torch.Tensor) and y.device == self.rt.device \
+            and y.dtype == torch.float64 and tuple(y.shape) == (self.N, self.D) \
+            and y.is_contiguous()
+
+    def invalidate(self, node):
+        Y, z = self.Y, self.z
+        live = self._ready and Y.observed and Y._mask is True \
+            and tuple(np.shape(Y._data)) == (self.N, self.D)
+        if live and (node is z or node is Y) and _scalar_multiplier(z) != self._m_seen \
+                and GMMSVIPlan.match(self.nodes()) is not None:
+            # the setter of plates_multiplier: the state stays, the next operation reads the factor
+            self._m_seen = _scalar_multiplier(z)
+            self._version += 1
+            if node is z:
+                return
+        if live and node is Y:
+            # the next mini-batch -- a new array, or the same one filled again: the data changes,
+            # the state stays
+            y, torch = Y._data, self.rt.torch
+            if self._is_device_batch(y):
+                self.Yd = y
+            else:
+                if self._Ybuf is None:
+                    self._Ybuf = self.rt.empty(self.N, self.D)
+                src = y if isinstance(y, torch.Tensor) else \
+                    torch.from_numpy(np.array(y, dtype=np.float64, order='C'))
+                self._Ybuf.copy_(src)
+                self.Yd = self._Ybuf
+            self._version += 1
+            return
+        if live and node is z and z._init is self._z_init_seen:
+            return                  # the setter wrote the factor that was there: nothing changed
+        _delta.warn_state_discarded(self, node)
+        self._ready = False
+        self._version += 1
+        if GMMSVIPlan.match(self.nodes()) is None:
+            from .generic import GenericPlan
+            GenericPlan(self.nodes())
+
+    def _check_initialisations(self):
+        for n in (self.Lam, self.alpha):
+            if n is not None and (n._init is not None or n.observed):
+                raise NotImplementedError('the fused GMM block initialises Lambda and alpha from '
+                                          'their priors')
+        init = self.mu._init
+        if self.mu.observed or (init is not None and init[0] not in ('value', 'random')):
+            raise NotImplementedError('the fused GMM block initialises mu from its prior, from a '
+                                      'value or from a random draw')
+
+    def _initialise_globals(self):
+        rt, k, L = self.rt, self.kernels, self.layout
+        torch = rt.torch
+        D, K = self.D, self.K
+        self._m_seen = _scalar_multiplier(self.z)
+        self._z_init_seen = self.z._init
+        if self._Ybuf is None and not self._is_device_batch(self.Y._data):
+            self._Ybuf = self.Yd                    # the plan's own copy of a host array
+        # q(mu) in natural parameters: the prior's until the first update or step, also under a
+        # point mass (initialize_from_value leaves phi alone, expfamily.py:193-212)
+        self.phi_mu = rt.empty(K * (D + D * D))
+        k.natural_init(D, K, self.state, self.phi_mu)
+        if self.Lam_const is not None:
+            self.state[L.off_Lam:L.off_Lam + K * D * D].copy_(
+                torch.from_numpy(self.Lam_const.reshape(-1)))
+            self.state[L.off_logdetLam:L.off_logdetLam + K].copy_(
+                torch.from_numpy(np.ascontiguousarray(np.linalg.slogdet(self.Lam_const)[1])))
+        init = self.mu._init
+        if init is not None:
+            if init[0] == 'value':
+                x = np.array(np.broadcast_to(np.asarray(init[1], dtype=np.float64), (K, D)))
+            else:
+                # a draw from the prior N(0, I / beta0), as the generic engine draws it
+                Lc = np.linalg.cholesky(np.identity(D) / self.beta0 + 1e-12 * np.eye(D))
+                x = np.random.randn(K, D) @ Lc.T
+            self.state[L.off_mu:L.off_mu + K * D].copy_(
+                torch.from_numpy(np.ascontiguousarray(x).reshape(-1)))
+            self.state[L.off_Cmu:L.off_Cmu + K * D * D].zero_()
+
+    # -- operations ------------------------------------------------------------------------------
+    def _bit(self, node):
+        if node is self.mu:
+            return STEP_MU
+        if self.Lam is not None and node is self.Lam:
+            return STEP_LAMBDA
+        if node is self.alpha:
+            return STEP_ALPHA
+        return 0
+
+    def update(self, node):
+        if node is self.z:
+            return super().update(node)
+        bit = self._bit(node)
+        if not bit:
+            return
+        self._materialize()
+        m = self._multiplier()
+        _delta.updated(self._delta, self.roles, node)
+        self.rt.sync_stream()
+        self.kernels.natural_step(self.D, self.K, bit, m, 1.0, self.state, self.phi_mu)
+        self._version += 1
+
+    def gradient_step(self, nodes, scale=1.0):
+        """phi <- phi + scale * (phi* - phi) for mu, Lambda and alpha among ``nodes``, in one
+        launch: every optimum phi* is taken from the moments and statistics present before any
+        node moves (vmp.py:432-440).  A mean that is still a point mass steps from its prior's
+        parameters, as on the generic engine."""
+        from ...nodes.node import Stochastic
+        bits, todo = 0, []
+        for node in nodes:
+            if not isinstance(node, Stochastic) or node.observed:
+                continue
+            if node is self.z:
+                raise NotImplementedError(
+                    'gradient step of %s: the fused Gaussian-mixture block keeps no natural '
+                    'parameters of the responsibilities to step from; update it (Q.update(%r)), or '
+                    'use VB(..., engine="generic")' % (node.name, node.name))
+            if self._bit(node):
+                bits |= self._bit(node)
+                todo.append(node)
+        if not bits:
+            return
+        self._materialize()
+        m = self._multiplier()
+        for node in todo:
+            _delta.updated(self._delta, self.roles, node)
+        self.rt.sync_stream()
+        self.kernels.natural_step(self.D, self.K, bits, m, scale, self.state, self.phi_mu)
+        self._version += 1
+
+    def _lower_bound_terms(self):
+        self._materialize()
+        if self._L_version != self._version:
+            super()._lower_bound_terms()
+            # the mini-batch stands for m times as many rows (expfamily.py:470-480); a constant
+            # precision has no term; the total is formed again from the terms
+            m = self._multiplier()
+            t = self._L
+            t['Y'], t['z'] = m * t['Y'], m * t['z']
+            if self.Lam is None:
+                t['Lambda'] = 0.0
+            t['total'] = t['Y'] + t['z'] + t['alpha'] + t['mu'] + t['Lambda']
+        return _delta.bound_terms(self._L, self._delta)
+
+    # -- persistence: + the natural parameters of the means --------------------------------------
+    def save_state(self, put, nodes, index):
+        super().save_state(put, nodes, index)
+        put('plans/%d/phi_mu' % index, self.phi_mu.cpu().numpy())
+
+    def load_state(self, reader, nodes, index):
+        super().load_state(reader, nodes, index)
+        self.phi_mu.copy_(self.rt.torch.from_numpy(
+            np.array(reader.get('plans/%d/phi_mu' % index), dtype=np.float64)))

@@ -594,6 +594,23 @@ int32_t vmp_gmm_pass(vmp_ctx *ctx, const double *Y, int64_t N, int32_t D, int32_
                      double *state, void *workspace);
 /* alpha.update(): dirichlet.py:113-160 with the message categorical -> [r]. */
 int32_t vmp_gmm_update_alpha(vmp_ctx *ctx, int32_t D, int32_t K, double *state);
+/* Stochastic variational inference (vmp.py:432-440): ONE launch moves the global nodes in the bit
+ * set `nodes` (1 = mu, 2 = Lambda, 4 = alpha) by a step of length `scale` along their natural
+ * gradients, phi <- phi + scale (phi* - phi).  The optimum phi* is that of the update entry points
+ * above with the statistics T weighted by `mult` (the plates_multiplier of a mini-batch), and every
+ * optimum is taken from the moments present at entry -- the simultaneous step of the reference, not
+ * a sequence of updates.  The moments of the stepped nodes are formed again from the new
+ * parameters.  `phi_mu` (device, K * (D + D*D) doubles, cluster-major: h_k = Lambda_mu,k m_k, then
+ * Lambda_mu,k) holds the natural parameters of q(mu); those of Lambda and alpha are the state's own
+ * (off_nk, off_Vk), (off_alpha).  scale == 1 takes phi* itself, and with mult == 1 the step of one
+ * node then equals vmp_gmm_update_mu / _lambda / _alpha bit for bit.  A matrix that is not positive
+ * definite sets the status word of the state (VMP_ERR_NOT_POSDEF), as in the update entry points.
+ * vmp_gmm_natural_init sets phi_mu to the prior of the means (h = 0, Lambda_mu = beta0 I) from an
+ * initialised state. */
+int32_t vmp_gmm_natural_init(vmp_ctx *ctx, int32_t D, int32_t K, const double *state,
+                             double *phi_mu);
+int32_t vmp_gmm_natural_step(vmp_ctx *ctx, int32_t D, int32_t K, int32_t nodes, double mult,
+                             double scale, double *state, double *phi_mu);
 /* Lower bound of Y, z, alpha, mu, Lambda (expfamily.py:400-480). */
 int32_t vmp_gmm_lower_bound(vmp_ctx *ctx, int32_t D, int32_t K, double *state);
 

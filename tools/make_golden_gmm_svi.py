@@ -1,0 +1,45 @@
+#!/usr/bin/env python
+"""
+Fixture of the Gaussian mixture under stochastic variational inference from the LIVE reference:
+tests/golden/gmm_svi.npz.  Runs the model scripts of tests/gmm_svi_models.py on the reference,
+imported the way oracle/make_golden.py imports it, and stores the inputs (data, the mini-batch
+index sequences, the initial means, a constant precision) and, after every step, the bound, the
+per-node bound terms and the moments of the global nodes; Z.u[0] of the last mini-batch.
+
+    python tools/make_golden_gmm_svi.py
+"""
+import os
+import sys
+import warnings
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+
+def main():
+    from oracle.make_golden import _import_reference, OUT
+    _import_reference()
+    import bayespy.nodes
+    from bayespy.inference import VB
+    import gmm_svi_models as M
+    g = M.make_inputs(np.random.RandomState(5207))
+    mods = dict(nodes=bayespy.nodes, VB=VB)
+    out = dict(g)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        for tag in M.CASES:
+            for k, v in M.run_case(mods, g, tag).items():
+                if not k.endswith('_plan'):
+                    out[k] = np.array(v)
+    fn = os.path.join(OUT, 'gmm_svi.npz')
+    np.savez_compressed(fn, **out)
+    print(fn, os.path.getsize(fn), 'bytes')
+    for tag in M.CASES:
+        print(tag, out[tag + '_L'])
+
+
+if __name__ == '__main__':
+    main()
