@@ -10,7 +10,12 @@
 //             (column sums stay inside a lane; the row vector logalpha is exchanged through LDS)
 //   backward  zz_n[i,j] = softmax_ij(logalpha_n[i] + logbeta_n[j] + logP_n[i,j])   (lane-local
 //             columns again), then logbeta_{n-1}[i] = lse_j(logbeta_n[j] + logP_n[i,j] - c):
-//             a row reduction, done by transposing the exponentials through a padded LDS tile.
+//             a row reduction, done by transposing the slice through a padded LDS tile.
+// Every log-sum-exp over ONE axis is shifted by the maximum of that column / row, as the
+// reference's logsumexp(axis=) does, and c is assembled from the K pairs (maximum, sum): a state
+// more than 745 below the best one of its instance stays finite -- it may be the only cheap
+// route to what follows.  Only the softmax of zz is shifted by the joint maximum of its slice
+// (the reference's exp(v - c) underflows in the same places).
 // 64 / KP chains share a wavefront, chains are independent (grid over chains), time is
 // sequential.  Per chain and step: 3 K^2 exponentials and 3 K^2 fp64 words of HBM traffic
 // (logP read twice, zz written once; logalpha goes through a K-vector workspace) -- the two
@@ -86,7 +91,7 @@ __global__ __launch_bounds__(64) void alpha_beta_kernel(
             lds_fence();
             const double *Pn = P + (int64_t)n * P_ts;
             double col[REG ? KP : 1];
-            double m = -INFINITY;
+            double mj = -INFINITY;                // maximum of this lane's column
             if constexpr (REG) {
                 double cur[KP];
 #pragma unroll
@@ -100,25 +105,26 @@ __global__ __launch_bounds__(64) void alpha_beta_kernel(
 #pragma unroll
                 for (int i = 0; i < KP; ++i) {
                     col[i] = (act && i < K) ? vec[i] + cur[i] : -INFINITY;
-                    m = fmax(m, col[i]);
+                    mj = fmax(mj, col[i]);
                 }
             } else {
                 // many states: the column does not fit the register file, evaluate it twice
                 if (act)
-                    for (int i = 0; i < K; ++i) m = fmax(m, vec[i] + Pn[i * K + j]);
+                    for (int i = 0; i < K; ++i) mj = fmax(mj, vec[i] + Pn[i * K + j]);
             }
-            m = group_max<KP>(m);
+            const double m = group_max<KP>(mj);
             double s = 0.0;
             if constexpr (REG) {
 #pragma unroll
-                for (int i = 0; i < KP; ++i) s += exp_shift(col[i], m);
+                for (int i = 0; i < KP; ++i) s += exp_shift(col[i], mj);
             } else {
                 if (act)
-                    for (int i = 0; i < K; ++i) s += exp_shift(vec[i] + Pn[i * K + j], m);
+                    for (int i = 0; i < K; ++i) s += exp_shift(vec[i] + Pn[i * K + j], mj);
             }
-            const double tot = group_sum<KP>(s);
+            // c = m + log(tot) from the columns' (maximum, sum); an impossible column has s = 0
+            const double tot = group_sum<KP>(exp_shift(mj, m) * s);
             gsum -= m + log(tot);
-            la = log(s) - log(tot);              // lse_i(v_ij - c)
+            la = (mj == -INFINITY) ? -INFINITY : (mj - m) + (log(s) - log(tot));   // lse_i(v_ij - c)
             lds_fence();
         }
         if (live && j == 0) g[c] = gsum;
@@ -140,7 +146,7 @@ __global__ __launch_bounds__(64) void alpha_beta_kernel(
             const double *Pn = P + (int64_t)n * P_ts;
             const double *an = aw + (int64_t)n * K;
             double col[REG ? KP : 1], w[REG ? KP : 1];
-            double mz = -INFINITY, mb = -INFINITY;
+            double mz = -INFINITY;
             if constexpr (REG) {
                 double cur[KP], cura[KP];
 #pragma unroll
@@ -163,25 +169,19 @@ __global__ __launch_bounds__(64) void alpha_beta_kernel(
                     col[i] = ok ? lb + cur[i] : -INFINITY;
                     w[i] = ok ? cura[i] + col[i] : -INFINITY;
                     mz = fmax(mz, w[i]);
-                    mb = fmax(mb, col[i]);
                 }
             } else if (act) {
-                for (int i = 0; i < K; ++i) {
-                    const double cv = lb + Pn[i * K + j];
-                    mz = fmax(mz, an[i] + cv);
-                    mb = fmax(mb, cv);
-                }
+                for (int i = 0; i < K; ++i) mz = fmax(mz, an[i] + (lb + Pn[i * K + j]));
             }
             mz = group_max<KP>(mz);
-            mb = group_max<KP>(mb);
-            double sz = 0.0, sb = 0.0;
+            // the tile takes v_ij = logbeta_n[j] + logP_n[i,j] itself (-inf in the padding): the
+            // rows are shifted by their own maxima once a lane holds a whole row
+            double sz = 0.0;
             if constexpr (REG) {
 #pragma unroll
                 for (int i = 0; i < KP; ++i) {
                     w[i] = exp_shift(w[i], mz);
                     sz += w[i];
-                    col[i] = exp_shift(col[i], mb);
-                    sb += col[i];
                     tile[i * LD + j] = col[i];
                 }
             } else {
@@ -189,15 +189,12 @@ __global__ __launch_bounds__(64) void alpha_beta_kernel(
                     const bool ok = act && i < K;
                     const double cv = ok ? lb + Pn[i * K + j] : -INFINITY;
                     const double ez = ok ? exp_shift(an[i] + cv, mz) : 0.0;
-                    const double eb = exp_shift(cv, mb);
                     sz += ez;
-                    sb += eb;
-                    tile[i * LD + j] = eb;
+                    tile[i * LD + j] = cv;
                     tile2[i * LD + j] = ez;
                 }
             }
             const double rz = 1.0 / group_sum<KP>(sz);
-            const double totb = group_sum<KP>(sb);
             if (act && live) {
                 if constexpr (REG) {
 #pragma unroll
@@ -224,9 +221,25 @@ __global__ __launch_bounds__(64) void alpha_beta_kernel(
                 if (act && live) z0[c * K + j] = r / rt;
             } else {
                 lds_fence();
-                double r = 0.0;                   // row j of the exponentials
-                for (int t = 0; t < KP; ++t) r += tile[j * LD + t];
-                lb = log(r) - log(totb);          // lse_j(v_ij - c), now indexed by this lane
+                const double *row = tile + j * LD;    // row j of v, now indexed by this lane
+                double mr = -INFINITY, r = 0.0;
+                if constexpr (REG) {
+                    double rv[KP];
+#pragma unroll
+                    for (int t = 0; t < KP; ++t) {
+                        rv[t] = row[t];
+                        mr = fmax(mr, rv[t]);
+                    }
+#pragma unroll
+                    for (int t = 0; t < KP; ++t) r += exp_shift(rv[t], mr);
+                } else {
+                    for (int t = 0; t < KP; ++t) mr = fmax(mr, row[t]);
+                    for (int t = 0; t < KP; ++t) r += exp_shift(row[t], mr);
+                }
+                const double mb = group_max<KP>(mr);
+                const double totb = group_sum<KP>(exp_shift(mr, mb) * r);
+                // lse_j(v_ij - c) with c = mb + log(totb); a row with no way out has r = 0
+                lb = (mr == -INFINITY) ? -INFINITY : (mr - mb) + (log(r) - log(totb));
                 lds_fence();
             }
         }

@@ -1,7 +1,8 @@
 """
 TEST DOUBLE of the GENERIC part of the C ABI (include/vmp_hip.h: vmp_ewise, vmp_sum_multiply,
 vmp_gemm_strided, vmp_spd_batched, vmp_gaussian_moments, vmp_softmax_moments, vmp_onehot_i64,
-vmp_take_axis, vmp_segment_sum_axis, vmp_block_banded_solve, vmp_gaussian_shared_update, the queue
+vmp_take_axis, vmp_segment_sum_axis, vmp_alpha_beta_recursion, vmp_block_banded_solve,
+vmp_gaussian_shared_update, the queue
 entry points as no-ops) on host memory with NumPy.
 
 It lets the host logic of the generic engine (bayespy_amd/inference/plans/generic.py: message
@@ -314,6 +315,53 @@ class HostGenericLib:
         flag[0] = int(bad.any())
         ok = ~bad
         o[np.nonzero(ok)[0], lab[ok]] = 1.0
+        return 0
+
+    # -- categorical Markov chains ----------------------------------------------------------------
+    def vmp_alpha_beta_recursion(self, ctx, N, K, nchains, logp0, p0_bstride, logP, P_bstride,
+                                 P_tstride, z0, zz, g, workspace, workspace_bytes):
+        """utils/random.py:357-422 with the strides and the status codes of the entry point;
+        logalpha and logbeta with the log-sum-exp of ONE axis (a shift per column / per row)."""
+        self._count('vmp_alpha_beta_recursion')
+        N, K, B = int(N), int(K), int(nchains)
+        if not all(_ptr(p) for p in (logp0, logP, z0, zz, g)) or N < 1 or K < 1 or B < 0:
+            return -1
+        if K > 64:
+            return -4
+        if B == 0:
+            return 0
+        if not _ptr(workspace) or int(_v(workspace_bytes)) < B * N * K * 8:
+            return -1
+        p0 = _view(logp0, (B, K), (int(p0_bstride), 1))
+        P = _view(logP, (B, N, K, K), (int(P_bstride), int(P_tstride), K, 1))
+
+        def lse(x, axis):
+            m = np.max(x, axis=axis, keepdims=True)
+            m = np.where(np.isfinite(m), m, 0.0)
+            return np.log(np.sum(np.exp(x - m), axis=axis)) + np.squeeze(m, axis=axis)
+        la = np.empty((B, N, K))
+        la[:, 0] = p0
+        gg = np.zeros(B)
+        with np.errstate(all='ignore'):
+            for n in range(N):
+                v = la[:, n, :, None] + P[:, n]
+                c = lse(v.reshape(B, K * K), -1)
+                gg -= c
+                if n + 1 < N:
+                    la[:, n + 1] = lse(v - c[:, None, None], -2)
+            q = _dense(zz, (B, N, K, K))
+            lb = np.zeros((B, K))
+            for n in range(N - 1, -1, -1):
+                w = la[:, n, :, None] + lb[:, None, :] + P[:, n]
+                e = np.exp(w - np.max(w, axis=(-1, -2), keepdims=True))
+                q[:, n] = e / np.sum(e, axis=(-1, -2), keepdims=True)
+                if n > 0:
+                    v = lb[:, None, :] + P[:, n]
+                    c = lse(v.reshape(B, K * K), -1)
+                    lb = lse(v - c[:, None, None], -1)
+            r = np.sum(q[:, 0], axis=-1)
+            _dense(z0, (B, K))[...] = r / np.sum(r, axis=-1, keepdims=True)
+        _dense(g, (B,))[...] = gg
         return 0
 
     # -- plate re-indexing ------------------------------------------------------------------------
