@@ -12,6 +12,7 @@ from .lda import LDAPlan, LDASVIPlan
 from .bmm import BernoulliMixturePlan
 from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
+from .dgmm import DiagGaussianMixturePlan
 
 PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
 # engine='fused': a block's opt-in form takes the place of its default form
@@ -25,6 +26,8 @@ OPT_IN_EMISSIONS = {HMMPlan: [CategoricalHMMPlan]}
 # engine='fused': further forms of a default block, tried right after it -- the block keeps
 # whatever it matches (GMMSVIPlan takes the mixture under mini-batches, which GMMPlan declines)
 OPT_IN_AFTER = {GMMPlan: [GMMSVIPlan]}
+# engine='fused': further opt-in blocks, tried after ``opt_in_types()``
+OPT_IN_MORE = [DiagGaussianMixturePlan]
 
 
 def opt_in_types():
@@ -54,6 +57,7 @@ def _reusable_plans(nodes, engine, options=None):
     if engine == 'fused' and any(isinstance(p, GenericPlan) for p in plans):
         return None
     if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values() or type(p) in opt_in_types()
+                                 or type(p) in OPT_IN_MORE
                                  or any(type(p) in v for v in OPT_IN_AFTER.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
@@ -105,7 +109,7 @@ def compile_model(nodes, engine=None, **options):
         plan._engine_request = 'generic'
         return [plan]
     types = [Q for P in PLAN_TYPES for Q in [OPT_IN_FORMS.get(P, P)] + OPT_IN_AFTER.get(P, [])] \
-        + opt_in_types() if engine == 'fused' else PLAN_TYPES
+        + opt_in_types() + OPT_IN_MORE if engine == 'fused' else PLAN_TYPES
     remaining = [n for n in nodes]
     plans = []
     progress = True

@@ -998,6 +998,56 @@ int32_t vmp_bmm_pass_masked(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, const
                             const double *c, double *ws, double *S, double *M, double *Nk,
                             double *counts, double *scal, double *r_out);
 
+/* Diagonal-Gaussian mixture: the fused block of
+ *     alpha = Dirichlet(a);  Z = Categorical(alpha, plates=(N, 1))
+ *     mu = GaussianARD(m0, beta0, plates=(D, K));  tau = Gamma(a0, b0, plates=(D, K))
+ *     Y = Mixture(Z, GaussianARD, mu, tau);  Y.observe(y)
+ * (details: bayespy_amd/csrc/vmp_dgmm.hip, vmp_dgmm_dev.h).  N rows of D real observations, K
+ * clusters; no (N, D, K) or (N, K) array exists.  With h = <tau><mu>, q = -1/2 <tau> and
+ * g = 1/2 <log tau> - 1/2 <tau><mu^2> (D x K) the logit of row n is c[k] + sum_d y_nd h[d, k] +
+ * y_nd^2 q[d, k]; the constant -1/2 log 2 pi per element is the same for every k and is left to
+ * the caller (-1/2 N D log 2 pi in the bound term of Y).
+ *   vmp_dgmm_limits (host only): *max_K = 64, *max_D = 1024.
+ *   vmp_dgmm_plan (host only): for (N, D, K) the rows of a chunk *chunk_rows (one workgroup, a
+ *     function of (N, D, K) alone; at most 1024 chunks and 2^25 doubles of partials of 2 D K + K +
+ *     1 doubles each) and the scratch *workspace_doubles of the pass.
+ *   vmp_dgmm_tables: from the moments of mu ((D K, 2): <mu>, <mu^2>), of tau ((D K, 2): <tau>,
+ *     <log tau>) and elog_pi (K) the tables h, q (D x K) and c[k] = <log pi_k> + sum_d g[d, k] less
+ *     its largest element (r, the statistics and the entropy do not depend on a constant in c; lse
+ *     is relative to it); gsum (K), if not NULL, receives sum_d g[d, k].  A NULL moment table gives
+ *     h = q = 0, gsum = 0 and c from <log pi> alone: Z under its prior.
+ *   vmp_dgmm_pass: per tile of 64 rows logit = Y h + (Y o Y) q, then + c; lse = max + log sum
+ *     exp(logit - max), r = exp(logit - lse); S1 += r^T Y, S2 += r^T (Y o Y), all four products on
+ *     the fp64 matrix cores.  Out: S1, S2 (D x K), Nk (K), scal[0] = sum lse, scal[1] = Nk . c,
+ *     scal[2] = S1 . h + S2 . q; with r_out (N x K) also r itself.  `labels` (N int32) non-NULL: r
+ *     is the one-hot array of these classes and lse = 0.  ws: vmp_dgmm_plan's doubles.  No atomics:
+ *     the bits of every output depend on the inputs and (N, D, K) only, with or without r_out.
+ *     N = 0 gives zeros.  y or tables that are not finite are outside the contract.
+ *   vmp_dgmm_update: one launch for one node, from the statistics and the present moments
+ *     `other_mom` ((D K, 2)) of the other node; priors as dense (D, K) tables.
+ *       which = 0, q(mu): prior_a = m0, prior_b = beta0, other_mom = moments of tau;
+ *         lambda = beta0 + <tau> Nk, m = (beta0 m0 + <tau> S1) / lambda; par = (m, lambda),
+ *         mom = (m, m^2 + 1 / lambda).
+ *       which = 1, q(tau): prior_a = a0, prior_b = b0, other_mom = moments of mu;
+ *         a = a0 + Nk / 2, b = b0 + (S2 - 2 <mu> S1 + <mu^2> Nk) / 2; par = (a, b),
+ *         mom = (a / b, psi(a) - log b).
+ *     *bound = <log p(node)> - <log q(node)> (expfamily.py:400-480) summed over (D, K) in a fixed
+ *     order.  NULL statistics (any of S1, S2, Nk, other_mom) give the prior.
+ *   K or D above the limits: VMP_ERR_UNSUPPORTED; null / negative arguments: VMP_ERR_INVALID. */
+int32_t vmp_dgmm_limits(int32_t *max_K, int32_t *max_D);
+int32_t vmp_dgmm_plan(int64_t N, int32_t D, int32_t K, int64_t *chunk_rows,
+                      int64_t *workspace_doubles);
+int32_t vmp_dgmm_tables(vmp_ctx *ctx, int32_t D, int32_t K, const double *mu_mom,
+                        const double *tau_mom, const double *elog_pi, double *h, double *q,
+                        double *c, double *gsum);
+int32_t vmp_dgmm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, const double *y,
+                      const int32_t *labels, const double *h, const double *q, const double *c,
+                      double *ws, double *S1, double *S2, double *Nk, double *scal, double *r_out);
+int32_t vmp_dgmm_update(vmp_ctx *ctx, int32_t D, int32_t K, int32_t which, const double *prior_a,
+                        const double *prior_b, const double *S1, const double *S2,
+                        const double *Nk, const double *other_mom, double *par, double *mom,
+                        double *bound);
+
 /* Hidden Markov model with Gaussian emissions: the chain pass of the fused block
  * (doc/source/examples/hmm.rst; details: bayespy_amd/csrc/vmp_hmm_fused.hip, vmp_hmm_fused_dev.h).
  * B chains of T time instances, D-dimensional observations, K states.  No (B, T-1, K, K) array is
