@@ -214,6 +214,55 @@ __host__ __device__ inline double vmp_lgamma(double x)
     return (x - 0.5) * log(x) - x + 0.91893853320467274178 + ser - shift;
 }
 
+#if defined(__clang__)
+#define VMP_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define VMP_NO_CONTRACT
+#endif
+
+// s = fl(a + b) and the rounding error of that sum in *e (Knuth): a + b == s + *e exactly.
+__host__ __device__ inline double vmp_two_sum(double a, double b, double *e)
+{
+    VMP_NO_CONTRACT
+    const double s = a + b, bb = s - a;
+    *e = (a - (s - bb)) + (b - bb);
+    return s;
+}
+
+// ln Gamma(x + dx) as an unevaluated sum: the return value plus *lo, |dx| a rounding error of x.
+// For the ln Gamma(sum alpha) of a Dirichlet bound term: at x of a few hundred vmp_lgamma is 2 ulp
+// of 2 000 off ((x - 1/2) log x is rounded at its full size and inherits x times the error of the
+// logarithm), which the difference of two such values in the term does not forgive.  Here
+// log x = e ln 2 + log m with m in [sqrt 1/2, sqrt 2): e ln2_hi is exact and the error of the
+// logarithm is that of a number below 0.35; the products with x - 1/2 and the sums keep their
+// rounding errors.  About 0.1 ulp of the value at x >= 10; below 10 it is vmp_lgamma (*lo = the
+// dx term only).
+__host__ __device__ inline double vmp_lgamma_dd(double x, double dx, double *lo)
+{
+    VMP_NO_CONTRACT
+    if (!(x >= 10.0) || !(x < 4e15)) {
+        *lo = dx == 0.0 ? 0.0 : dx * vmp_digamma(x);
+        return vmp_lgamma(x);
+    }
+    int e;
+    double m = frexp(x, &e);
+    if (m < 0.70710678118654752440) { m *= 2.0; e -= 1; }
+    const double A = (double)e * 6.93147180369123816490e-01;                 // ln2_hi: exact
+    const double B = (double)e * 1.90821492927058770002e-10 + log(m);        // ln2_lo
+    const double w = x - 0.5;
+    const double p = w * A, pe = fma(w, A, -p);
+    const double q = w * B, qe = fma(w, B, -q);
+    double e1, e2;
+    const double s1 = vmp_two_sum(p, -x, &e1);
+    const double s2 = vmp_two_sum(s1, q, &e2);
+    const double inv = 1.0 / x, inv2 = inv * inv;
+    const double ser = inv * (1.0 / 12 - inv2 * (1.0 / 360 - inv2 * (1.0 / 1260 - inv2 * (1.0 / 1680 - inv2 * (1.0 / 1188 - inv2 * (691.0 / 360360 - inv2 * (1.0 / 156)))))));
+    // d/dx ln Gamma = psi(x) = log x - 1/(2x) - ...
+    const double small = ((pe + qe) + (e1 + e2)) + (0.91893853320467274178 + ser)
+                         + dx * ((A + B) - 0.5 * inv);
+    return vmp_two_sum(s2, small, lo);
+}
+
 // psi'(x) (trigamma; scipy.special.polygamma(1, .) call sites gamma.py:210,
 // dirichlet.py:230) for x > 0: upward recurrence to x >= 10, then the asymptotic series
 // 1/x + 1/(2x^2) + sum_n B_2n / x^(2n+1).

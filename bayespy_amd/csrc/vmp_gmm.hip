@@ -869,12 +869,31 @@ gmm_update_alpha_kernel(vmp_gmm_layout L, int D, int K, double *st)
 
 // out-of-line copies keep the register footprint of the bookkeeping kernels small
 __device__ __noinline__ double lgamma_ni(double x) { return vmp_lgamma(x); }
+__device__ __noinline__ v2f64 lgamma_dd_ni(double x, double dx)      // (value, rounding error)
+{
+    v2f64 g;
+    double lo;
+    g.x = vmp_lgamma_dd(x, dx, &lo);
+    g.y = lo;
+    return g;
+}
 
 __device__ __noinline__ double multigammaln_dev(double a, int d)
 {
     double s = (double)d * (d - 1) / 4.0 * log(M_PI);
     for (int i = 0; i < d; ++i) s += lgamma_ni(a - 0.5 * i);
     return s;
+}
+
+// sum over the wavefront of the unevaluated sums h + lo, every lane gets the total
+__device__ inline void wave_sum_dd(double &h, double &lo)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const double h2 = __shfl_xor(h, off, 64), l2 = __shfl_xor(lo, off, 64);
+        double e;
+        h = vmp_two_sum(h, h2, &e);
+        lo += l2 + e;
+    }
 }
 
 // expfamily.py:400-480 for Y, z, alpha, mu, Lambda.  One workgroup of 16
@@ -884,25 +903,23 @@ __global__ void __launch_bounds__(NTLB)
 gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st)
 {
     __shared__ double red[NTLB / 64];
-    __shared__ double lgs[MAXK][2 + 2 * MAXD];     // all log-Gamma values, ONE call site
+    __shared__ double lgs[MAXK][2 * MAXD];         // the log-Gamma values of Lambda, ONE call site
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
     const int KP = (int)L.KP;
     const double beta0 = st[L.off_prior + KP + 0], n0 = st[L.off_prior + KP + 1];
     const double ldV0 = st[L.off_prior + KP + 2];
     const double *V0 = st + L.off_prior + KP + 8;
-    const int per = 2 + 2 * D;
+    const int per = 2 * D;
     for (int e = tid; e < K * per; e += NTLB) {
         const int k = e / per, c = e - k * per;
         double x;
-        if (c == 0) x = st[L.off_prior + k];                          // alpha0_k
-        else if (c == 1) x = st[L.off_alpha + k];                     // alpha_k
-        else if (c < 2 + D) x = 0.5 * n0 - 0.5 * (c - 2);             // Gamma_D(n0/2) terms
-        else x = 0.5 * st[L.off_nk + k] - 0.5 * (c - 2 - D);          // Gamma_D(n_k/2) terms
+        if (c < D) x = 0.5 * n0 - 0.5 * c;                            // Gamma_D(n0/2) terms
+        else x = 0.5 * st[L.off_nk + k] - 0.5 * (c - D);              // Gamma_D(n_k/2) terms
         lgs[k][c] = vmp_lgamma(x);
     }
     __syncthreads();
     const double mgc = (double)D * (D - 1) / 4.0 * log(M_PI);
-    double LY = 0.0, Lz = 0.0, La = 0.0, Lmu = 0.0, LL = 0.0, sa0 = 0.0, sa = 0.0;
+    double LY = 0.0, Lz = 0.0, Lmu = 0.0, LL = 0.0;
     for (int k = w; k < K; k += NTLB / 64) {
         const double *T = st + L.off_T + (int64_t)k * L.FS;
         const double *Lam = st + L.off_Lam + (int64_t)k * D * D;
@@ -928,17 +945,12 @@ gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st)
             const double ldL = st[L.off_logdetLam + k];
             const double ck = 0.5 * ldL - 0.5 * (double)D * log(2.0 * M_PI) - 0.5 * trLmm;
             LY += R * ck + bs - 0.5 * ls2;
-            const double a0 = st[L.off_prior + k], a = st[L.off_alpha + k];
-            const double lp = st[L.off_alpha + KP + k];
-            Lz += R * lp;
-            La += -lgs[k][0] + lgs[k][1] + (a0 - a) * lp;
-            sa0 += a0;
-            sa += a;
+            Lz += R * st[L.off_alpha + KP + k];
             Lmu += -0.5 * beta0 * trmm + 0.5 * (double)D * log(beta0)
                    - 0.5 * st[L.off_logdetLmu + k] + 0.5 * (double)D;
             const double nk = st[L.off_nk + k];
             double mg0 = mgc, mgk = mgc;
-            for (int c = 0; c < D; ++c) { mg0 += lgs[k][2 + c]; mgk += lgs[k][2 + D + c]; }
+            for (int c = 0; c < D; ++c) { mg0 += lgs[k][c]; mgk += lgs[k][D + c]; }
             const double gp = 0.5 * n0 * ldV0 - 0.5 * D * n0 * log(2.0) - mg0;
             const double gq = 0.5 * nk * st[L.off_logdetV + k] - 0.5 * D * nk * log(2.0) - mgk;
             LL += gp - gq - 0.5 * trV0 + 0.5 * n0 * ldL + 0.5 * trVk - 0.5 * nk * ldL;
@@ -946,16 +958,37 @@ gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st)
     }
     LY = block_sum<NTLB>(LY, red);
     Lz = block_sum<NTLB>(Lz, red);
-    La = block_sum<NTLB>(La, red);
     Lmu = block_sum<NTLB>(Lmu, red);
     LL = block_sum<NTLB>(LL, red);
-    sa0 = block_sum<NTLB>(sa0, red);
-    sa = block_sum<NTLB>(sa, red);
-    if (tid < 2) lgs[0][tid] = vmp_lgamma(tid == 0 ? sa0 : sa);
-    __syncthreads();
+    // The alpha term is ln Gamma(sum alpha0) - ln Gamma(sum alpha) + sum_k (ln Gamma(alpha_k) -
+    // ln Gamma(alpha0_k) + (alpha0_k - alpha_k) <log pi_k>): two values of up to a few thousand
+    // and a sum of the same size that leave a difference of a hundred, and exactly 0 at K = 1.
+    // Wavefront 0, lane k holding cluster k, adds the K <= 64 terms and both sums of alpha as
+    // (value, rounding error) pairs, with every ln Gamma such a pair too (vmp_lgamma_dd).
+    double La = 0.0;
+    if (w == 0) {
+        const bool on = l < K;
+        double s0h = on ? st[L.off_prior + l] : 0.0, s0l = 0.0;
+        double s1h = on ? st[L.off_alpha + l] : 0.0, s1l = 0.0;
+        double th = 0.0, tl = 0.0;
+        if (on) {
+            const v2f64 g0 = lgamma_dd_ni(s0h, 0.0), g1 = lgamma_dd_ni(s1h, 0.0);
+            double e;
+            th = vmp_two_sum(g1.x, -g0.x, &e);
+            tl = (e + (g1.y - g0.y)) + (s0h - s1h) * st[L.off_alpha + KP + l];
+        }
+        wave_sum_dd(th, tl);
+        wave_sum_dd(s0h, s0l);
+        wave_sum_dd(s1h, s1l);
+        const v2f64 g = lgamma_dd_ni(l == 0 ? s0h : s1h, l == 0 ? s0l : s1l);
+        const double g0h = __shfl(g.x, 0, 64), g0l = __shfl(g.y, 0, 64);
+        const double g1h = __shfl(g.x, 1, 64), g1l = __shfl(g.y, 1, 64);
+        double de;
+        const double d = vmp_two_sum(g0h, -g1h, &de);
+        La = (th + d) + (((g0l - g1l) + de) + tl);
+    }
     if (tid == 0) {
         Lz += st[L.off_zs + 0] - st[L.off_zs + 1];
-        La += lgs[0][0] - lgs[0][1];
         st[L.off_L + 0] = LY;
         st[L.off_L + 1] = Lz;
         st[L.off_L + 2] = La;
@@ -1006,6 +1039,10 @@ int32_t launch_gmm_pass_as(vmp_ctx *ctx, const double *Y, int64_t N, int D, int 
     const size_t lds = ldsd * sizeof(double);
     int64_t g = (ntiles + NW / KS - 1) / (NW / KS);
     if (g > gmm_max_grid(ctx)) g = gmm_max_grid(ctx);
+    // tests only: fewer workgroups, so that a wavefront walks many tiles at a small N (the
+    // workspace and the offset of Tc keep the sizes of gmm_max_grid)
+    const int cap = vmp_tune_get("gmm_grid_cap", 0);
+    if (cap > 0 && g > cap) g = cap;
     if (g < 1) g = 1;
     auto kern = gmm_pass_kernel<DPT, KT, FT2, FROM_LABELS, NW, REGEN, KS>;
     if constexpr (!REGEN) {

@@ -304,6 +304,9 @@ int32_t vmp_gmm_wide_pass(vmp_ctx *ctx, const double *Y, int64_t N, int D, int K
     // F2P <= 256: 136 accumulator registers + ~104 others, two wavefronts per SIMD fit
     const int64_t gmax = (int64_t)ctx->num_cu * (FT2 <= 16 ? 2 : 1);
     if (g > gmax) g = gmax;
+    // tests only (as in vmp_gmm.hip): fewer workgroups; the workspace keeps its size
+    const int cap = vmp_tune_get("gmm_grid_cap", 0);
+    if (cap > 0 && g > cap) g = cap;
     if (g < 1) g = 1;
     if (!labels) {
         hipLaunchKernelGGL(gmm_cfrag_kernel, dim3((unsigned)((KT * KS1 * 64 + 255) / 256)),
