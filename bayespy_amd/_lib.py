@@ -247,6 +247,12 @@ SIGNATURES = {
     'vmp_dgmm_tables': (c_i32, [c_vp, c_i32, c_i32] + [c_vp] * 7),
     'vmp_dgmm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32] + [c_vp] * 11),
     'vmp_dgmm_update': (c_i32, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 9),
+    'vmp_dgmm_limits_masked': (c_i32, [P(c_i32), P(c_i32)]),
+    'vmp_dgmm_plan_masked': (c_i32, [c_i64, c_i32, c_i32, P(c_i64), P(c_i64)]),
+    'vmp_dgmm_pack_masked': (c_i32, [c_vp, c_i64, c_i32] + [c_vp] * 4),
+    'vmp_dgmm_tables_masked': (c_i32, [c_vp, c_i32, c_i32] + [c_vp] * 7),
+    'vmp_dgmm_pass_masked': (c_i32, [c_vp, c_i64, c_i32, c_i32] + [c_vp] * 13),
+    'vmp_dgmm_update_masked': (c_i32, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 9),
     'vmp_hmm_fused_limits': (c_i32, [P(c_i32), P(c_i32)]),
     'vmp_hmm_fused_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_hmm_fused_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,

@@ -13,6 +13,7 @@ from .bmm import BernoulliMixturePlan
 from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
 from .dgmm import DiagGaussianMixturePlan
+from .dgmm_masked import MaskedDiagGaussianMixturePlan
 
 PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
 # engine='fused': a block's opt-in form takes the place of its default form
@@ -28,6 +29,14 @@ OPT_IN_EMISSIONS = {HMMPlan: [CategoricalHMMPlan]}
 OPT_IN_AFTER = {GMMPlan: [GMMSVIPlan]}
 # engine='fused': further opt-in blocks, tried after ``opt_in_types()``
 OPT_IN_MORE = [DiagGaussianMixturePlan]
+# engine='fused': the form of an opt-in block for missing observations, a plan class of its own,
+# tried right after that block (which declines every mask with a reason)
+OPT_IN_MASKED = {DiagGaussianMixturePlan: [MaskedDiagGaussianMixturePlan]}
+
+
+def _with_masked(types):
+    """``types`` with the plan classes of ``OPT_IN_MASKED`` inserted after their block."""
+    return [Q for P in types for Q in [P] + OPT_IN_MASKED.get(P, [])]
 
 
 def opt_in_types():
@@ -59,6 +68,7 @@ def _reusable_plans(nodes, engine, options=None):
     if engine != 'fused' and any(type(p) in OPT_IN_FORMS.values() or type(p) in opt_in_types()
                                  or type(p) in OPT_IN_MORE
                                  or any(type(p) in v for v in OPT_IN_AFTER.values())
+                                 or any(type(p) in v for v in OPT_IN_MASKED.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -109,7 +119,7 @@ def compile_model(nodes, engine=None, **options):
         plan._engine_request = 'generic'
         return [plan]
     types = [Q for P in PLAN_TYPES for Q in [OPT_IN_FORMS.get(P, P)] + OPT_IN_AFTER.get(P, [])] \
-        + opt_in_types() + OPT_IN_MORE if engine == 'fused' else PLAN_TYPES
+        + _with_masked(opt_in_types() + OPT_IN_MORE) if engine == 'fused' else PLAN_TYPES
     remaining = [n for n in nodes]
     plans = []
     progress = True

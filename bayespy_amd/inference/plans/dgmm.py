@@ -21,7 +21,9 @@ g = sum_d (1/2 <log tau> - 1/2 <tau><mu^2>) of the PRESENT moments:
     <log p(Z)> + entropy = N_k . <log pi>
                            + sum_n lse_n - N_k . c_used - (S1 . h_used + S2 . q_used)
 The bound terms of ``mu`` and ``tau`` come from ``vmp_dgmm_update``, that of ``alpha`` from the
-Dirichlet kernel.  Masks, mini-batches and sharded plates are declined (generic engine).
+Dirichlet kernel.  Masks, mini-batches and sharded plates are declined (generic engine); a mask of
+the full shape (N, D) is taken by the subclass of dgmm_masked.py, to which an unobserved model
+goes over when ``Y`` is observed with such a mask.
 
 Checkpoints: the block writes its own ``plans/<i>/`` group (kind 'dgmm') like every fused plan.
 """
@@ -31,6 +33,7 @@ import numpy as np
 
 from . import _delta
 from ._dirichlet import DirichletKernels, prior_table
+from .bmm import _mask_shape
 
 from ... import _lib
 from ...device import get_runtime, ptr
@@ -86,7 +89,9 @@ class DGMMKernels(DirichletKernels):
                                                _p(bound)))
 
 
-def _match(nodes, why):
+def _match(nodes, why, masked=False):
+    """``masked``: the matcher of the block with missing observations (dgmm_masked.py), which takes
+    a mask of the full shape of the plates of Y where this block takes none."""
     for Y in nodes:
         if not isinstance(Y, Mixture) or Y.node_class is not GaussianARD:
             continue
@@ -113,9 +118,17 @@ def _match(nodes, why):
         if any(getattr(n, '_shard_axis', None) is not None for n in five):
             no('a plate is sharded over ranks')
             continue
-        if Y._mask is not True:
+        if not masked and Y._mask is not True:
             no('it has a mask: the block takes fully observed data only; a mask goes through the '
                'generic engine')
+            continue
+        if masked and Y._mask is True:
+            continue                    # no mask: the model of the block without one, no reason
+        if masked and _mask_shape(Y._mask) != tuple(Y.plates):
+            no('it has a mask of shape %s: the block with missing observations takes a mask of '
+               'the full shape of the plates of Y, here %s; a scalar mask or one that broadcasts '
+               'over a plate goes through the generic engine'
+               % (_mask_shape(Y._mask), tuple(Y.plates)))
             continue
         bad = [(n, p) for n in (mu, tau, alpha) for p in n.parents if not isinstance(p, Constant)]
         if bad:
@@ -137,10 +150,14 @@ def _match(nodes, why):
             no('plates of Z / mu / tau / alpha are %s / %s / %s / %s, not (N, 1) / (D, K) / (D, K) '
                '/ ()' % (Z.plates, mu.plates, tau.plates, alpha.plates))
             continue
-        max_k, max_d = dgmm_limits()
+        if masked:
+            from .dgmm_masked import dgmm_masked_limits
+            max_k, max_d = dgmm_masked_limits()
+        else:
+            max_k, max_d = dgmm_limits()
         if K > max_k or D > max_d:
-            no('D = %d, K = %d exceed the limits of the block (D <= %d, K <= %d)'
-               % (D, K, max_d, max_k))
+            no('D = %d, K = %d exceed the limits of the block%s (D <= %d, K <= %d)'
+               % (D, K, ' with a mask' if masked else '', max_d, max_k))
             continue
         kids = ((alpha, [Z]), (Z, [Y]), (mu, [Y]), (tau, [Y]), (Y, []))
         if any([c for c, _ in n.children] != want for n, want in kids):
@@ -214,6 +231,11 @@ class DiagGaussianMixturePlan:
         self._ready = False
         self._version += 1
         if DiagGaussianMixturePlan.match(self.nodes()) is None:
+            from .dgmm_masked import MaskedDiagGaussianMixturePlan
+            if MaskedDiagGaussianMixturePlan.match(self.nodes()) is not None:
+                # Y was observed with a mask of its full shape: the block for missing observations
+                MaskedDiagGaussianMixturePlan(self.roles, runtime=self._rt)
+                return
             from .generic import GenericPlan
             GenericPlan(self.nodes())
 
@@ -255,7 +277,7 @@ class DiagGaussianMixturePlan:
         torch = rt.torch
         N, D, K = self.N, self.D, self.K
         rt.sync_stream()
-        self.chunk, wsd = k.plan(N, D, K)
+        self.chunk, wsd = self._plan_pass()
         self._upload_y()
         m0, beta0 = self._const(self.mu, 0, False, 'm0'), self._const(self.mu, 1, True, 'beta0')
         a0, b0 = self._const(self.tau, 0, True, 'a0'), self._const(self.tau, 1, True, 'b0')
@@ -269,6 +291,7 @@ class DiagGaussianMixturePlan:
         self.h_now, self.q_now, self.c_now = rt.zeros(D, K), rt.zeros(D, K), rt.zeros(K)
         self.gsum = rt.zeros(K)
         self.S1, self.S2, self.Nk = rt.zeros(D, K), rt.zeros(D, K), rt.zeros(K)
+        self._alloc_more()
         self.ws = rt.empty(int(wsd))
         self.ws_small = rt.empty(max(D * K, 1024))
         # [0] sum lse, [1] N_k . c used, [2] S1 . h + S2 . q used, [3] bound of mu, [4] of tau,
@@ -304,7 +327,7 @@ class DiagGaussianMixturePlan:
             if lab.size and (lab.min() < 0 or lab.max() >= K):
                 raise ValueError("Invalid category index")
             self.labels = torch.from_numpy(lab.astype(np.int32)).to(rt.device)
-        k.tables(D, K, None, None, self.elog_r, self.h, self.q, self.c)
+        self._tables(None, None)
         self._ready = True
         self._run_pass()
 
@@ -344,6 +367,21 @@ class DiagGaussianMixturePlan:
             + a - b0 * a / b
         self.scal[4:5].copy_(self._up([bound.sum()]))
 
+    # where the block with missing observations (dgmm_masked.py) goes another way
+    def _plan_pass(self):
+        return self.kernels.plan(self.N, self.D, self.K)
+
+    def _alloc_more(self):
+        pass
+
+    def _tables(self, mu_mom, tau_mom):
+        """The tables of the pass from the given moments (None: no observation term)."""
+        self.kernels.tables(self.D, self.K, mu_mom, tau_mom, self.elog_r, self.h, self.q, self.c)
+
+    def _update_from_statistics(self, which, prior_a, prior_b, other, par, mom, bound):
+        self.kernels.update(self.D, self.K, which, prior_a, prior_b, self.S1, self.S2, self.Nk,
+                            other, par, mom, bound)
+
     def _run_pass(self, r_out=None):
         """The statistics of the present ``Z`` state (tables ``h`` / ``q`` / ``c`` or labels)."""
         self.kernels.pass_(self.N, self.D, self.K, self.y, self.labels, self.h, self.q, self.c,
@@ -356,17 +394,17 @@ class DiagGaussianMixturePlan:
         _delta.updated(self._delta, self.roles, node)
         rt, k = self.rt, self.kernels
         rt.sync_stream()
-        D, K = self.D, self.K
+        K = self.K
         if node is self.Z:
             self.labels = None
-            k.tables(D, K, self.mu_mom, self.tau_mom, self.elog_r, self.h, self.q, self.c)
+            self._tables(self.mu_mom, self.tau_mom)
             self._run_pass()
         elif node is self.mu:
-            k.update(D, K, 0, self.m0, self.beta0, self.S1, self.S2, self.Nk, self.tau_mom,
-                     self.mu_par, self.mu_mom, self.scal[3:4])
+            self._update_from_statistics(0, self.m0, self.beta0, self.tau_mom, self.mu_par,
+                                         self.mu_mom, self.scal[3:4])
         elif node is self.tau:
-            k.update(D, K, 1, self.a0, self.b0, self.S1, self.S2, self.Nk, self.mu_mom,
-                     self.tau_par, self.tau_mom, self.scal[4:5])
+            self._update_from_statistics(1, self.a0, self.b0, self.mu_mom, self.tau_par,
+                                         self.tau_mom, self.scal[4:5])
         elif node is self.alpha:
             k.dirichlet(1, K, K, 1, self.prior_r, self.Nk, self.alpha_r, self.elog_r,
                         self.ws_small, self.scal[5:6])
@@ -444,8 +482,24 @@ class DiagGaussianMixturePlan:
         put(base + 'flags', np.array([1 if self.labels is not None else 0], dtype=np.int64))
         if self.labels is not None:
             put(base + 'labels', self.labels.cpu().numpy())
-        for name in self._SAVED:
+        self._save_more(put, base)
+        for name in self._saved():
             put(base + name, getattr(self, name).cpu().numpy())
+
+    def _saved(self):
+        return self._SAVED
+
+    def _save_more(self, put, base):
+        pass
+
+    def _check_more(self, reader, base):
+        """A checkpoint of the block with missing observations is not this block's."""
+        if reader.has(base + 'mask'):
+            saved = np.asarray(reader.get(base + 'mask'), dtype=np.uint8).reshape(-1)
+            raise ValueError('checkpoint was saved with a mask on Y with %d of %d entries '
+                             'observed, the model has no mask on Y: observe Y with the mask of '
+                             'the checkpoint before loading it'
+                             % (int(np.count_nonzero(saved)), saved.size))
 
     def load_state(self, reader, nodes, index):
         self._materialize()
@@ -458,6 +512,7 @@ class DiagGaussianMixturePlan:
         if dims != (self.N, self.D, self.K):
             raise ValueError('checkpoint is for (N, D, K) = %s, the model has %s'
                              % (dims, (self.N, self.D, self.K)))
+        self._check_more(reader, base)
         torch = self.rt.torch
         self._delta = _delta.load(reader, base)
         if int(np.asarray(reader.get(base + 'flags')).ravel()[0]):
@@ -465,7 +520,7 @@ class DiagGaussianMixturePlan:
                 np.array(reader.get(base + 'labels'), dtype=np.int32)).to(self.rt.device)
         else:
             self.labels = None
-        for name in self._SAVED:
+        for name in self._saved():
             getattr(self, name).copy_(torch.from_numpy(
                 np.array(reader.get(base + name), dtype=np.float64)).reshape(
                     getattr(self, name).shape).to(self.rt.device))

@@ -1048,6 +1048,44 @@ int32_t vmp_dgmm_update(vmp_ctx *ctx, int32_t D, int32_t K, int32_t which, const
                         const double *Nk, const double *other_mom, double *par, double *mom,
                         double *bound);
 
+/* The same block with missing observations, Y.observe(y, mask=m) with m of the full shape (N, D)
+ * (details: bayespy_amd/csrc/vmp_dgmm_masked.hip, vmp_dgmm_masked_dev.h).  With yt = m o y the logit
+ * of row n is c[k] + sum_d m_nd g[d, k] + yt_nd h[d, k] + yt_nd^2 q[d, k]: sum_d g leaves c and
+ * becomes a third product, and the count of an element M[d, k] = sum_n r_nk m_nd takes the place of
+ * N_k in both updates.  A row with nothing observed has r = softmax(c) (one-hot under labels) and
+ * enters neither Nk nor sum lse; a column with nothing observed has M = S1 = S2 = 0 exactly.
+ *   vmp_dgmm_limits_masked (host only): *max_K = 64, *max_D = 1024.
+ *   vmp_dgmm_plan_masked (host only): as vmp_dgmm_plan, for partials of 3 D K + K + 1 doubles.
+ *   vmp_dgmm_pack_masked: y_packed (N x D) = y where mask (N x D bytes) is non-zero and one fixed
+ *     quiet-NaN bit pattern elsewhere, chosen by a select: what y holds at a hidden position (NaN,
+ *     inf, 1e300) reaches nothing.  *n_observed (device) receives the number of observed entries.
+ *     The pass finds the mask again as y_packed == y_packed and reads no other array of size N D.
+ *   vmp_dgmm_tables_masked: h, q, g (D x K) and c = elog_pi less its largest element.  A NULL moment
+ *     table gives h = q = g = 0: Z under its prior.
+ *   vmp_dgmm_pass_masked: the pass of vmp_dgmm_pass on y_packed with the three products.  Out: S1,
+ *     S2, M (D x K), Nk (K, over the rows with an observed entry), scal[0] = sum lse over the same
+ *     rows, scal[1] = Nk . c, scal[2] = S1 . h + S2 . q + M . g; r_out and labels as in
+ *     vmp_dgmm_pass.  ws: vmp_dgmm_plan_masked's doubles.  No atomics: the bits of every output
+ *     depend on y_packed, the tables and (N, D, K) only.
+ *   vmp_dgmm_update_masked: vmp_dgmm_update with M (D x K) in the place of Nk (K).
+ *   K or D above the limits: VMP_ERR_UNSUPPORTED; null / negative arguments: VMP_ERR_INVALID. */
+int32_t vmp_dgmm_limits_masked(int32_t *max_K, int32_t *max_D);
+int32_t vmp_dgmm_plan_masked(int64_t N, int32_t D, int32_t K, int64_t *chunk_rows,
+                             int64_t *workspace_doubles);
+int32_t vmp_dgmm_pack_masked(vmp_ctx *ctx, int64_t N, int32_t D, const double *y,
+                             const uint8_t *mask, double *y_packed, int64_t *n_observed);
+int32_t vmp_dgmm_tables_masked(vmp_ctx *ctx, int32_t D, int32_t K, const double *mu_mom,
+                               const double *tau_mom, const double *elog_pi, double *h, double *q,
+                               double *g, double *c);
+int32_t vmp_dgmm_pass_masked(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, const double *y_packed,
+                             const int32_t *labels, const double *h, const double *q,
+                             const double *g, const double *c, double *ws, double *S1, double *S2,
+                             double *M, double *Nk, double *scal, double *r_out);
+int32_t vmp_dgmm_update_masked(vmp_ctx *ctx, int32_t D, int32_t K, int32_t which,
+                               const double *prior_a, const double *prior_b, const double *S1,
+                               const double *S2, const double *M, const double *other_mom,
+                               double *par, double *mom, double *bound);
+
 /* Hidden Markov model with Gaussian emissions: the chain pass of the fused block
  * (doc/source/examples/hmm.rst; details: bayespy_amd/csrc/vmp_hmm_fused.hip, vmp_hmm_fused_dev.h).
  * B chains of T time instances, D-dimensional observations, K states.  No (B, T-1, K, K) array is
