@@ -265,6 +265,11 @@ SIGNATURES = {
     'vmp_hmm_fused_pass_categorical': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                c_vp, c_vp, c_vp]),
+    'vmp_cmm_limits': (c_i32, [P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
+    'vmp_cmm_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
+    'vmp_cmm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'vmp_cmm_tables': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    'vmp_cmm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 9),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_hold_passes': (c_i32, [c_vp, c_i32]),

@@ -14,6 +14,7 @@ from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
+from .cmm import CategoricalMixturePlan
 
 PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
 # engine='fused': a block's opt-in form takes the place of its default form
@@ -32,6 +33,9 @@ OPT_IN_MORE = [DiagGaussianMixturePlan]
 # engine='fused': the form of an opt-in block for missing observations, a plan class of its own,
 # tried right after that block (which declines every mask with a reason)
 OPT_IN_MASKED = {DiagGaussianMixturePlan: [MaskedDiagGaussianMixturePlan]}
+# engine='fused': opt-in blocks tried after everything above (CategoricalMixturePlan takes the
+# mixtures of Categorical, with or without a mask, that every block above passes over in silence)
+OPT_IN_LAST = [CategoricalMixturePlan]
 
 
 def _with_masked(types):
@@ -69,6 +73,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or type(p) in OPT_IN_MORE
                                  or any(type(p) in v for v in OPT_IN_AFTER.values())
                                  or any(type(p) in v for v in OPT_IN_MASKED.values())
+                                 or type(p) in OPT_IN_LAST
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -119,7 +124,8 @@ def compile_model(nodes, engine=None, **options):
         plan._engine_request = 'generic'
         return [plan]
     types = [Q for P in PLAN_TYPES for Q in [OPT_IN_FORMS.get(P, P)] + OPT_IN_AFTER.get(P, [])] \
-        + _with_masked(opt_in_types() + OPT_IN_MORE) if engine == 'fused' else PLAN_TYPES
+        + _with_masked(opt_in_types() + OPT_IN_MORE) + OPT_IN_LAST if engine == 'fused' \
+        else PLAN_TYPES
     remaining = [n for n in nodes]
     plans = []
     progress = True

@@ -1175,6 +1175,48 @@ int32_t vmp_hmm_fused_pass_categorical(vmp_ctx *ctx, int64_t B, int32_t T, int32
                                        double *z0sum, double *xisum, double *S, double *scal,
                                        double *gamma, double *z0, double *zz);
 
+/* Categorical mixture (latent class model): the plate pass of the fused block
+ *     R = Dirichlet(a);  Z = Categorical(R, plates=(N, 1))
+ *     P = Dirichlet(conc, plates=(D, K));  X = Mixture(Z, Categorical, P);  X.observe(x[, mask])
+ * (details: bayespy_amd/csrc/vmp_cmm.hip, vmp_cmm_dev.h).  N rows of D observations in [0, M), K
+ * clusters; x is kept as one byte per entry, 255 = hidden; <log P> and the counts S are
+ * CATEGORY-MAJOR, element (m, d, k) at (m D + d) K + k.  No (N, K), (N, D, K) or (N, D, M) array
+ * exists.
+ *   vmp_cmm_limits (host only): *max_K = 64, *min_M = 2, *max_M = 32 and *max_cells, the doubles of
+ *     the count table a workgroup keeps in LDS: roundup(D, 64 / KP) M KP <= *max_cells with
+ *     KP = 16, 32 or 64 the lanes that hold the K clusters.
+ *   vmp_cmm_plan (host only): for (N, D, K, M) the rows of a chunk *chunk_rows (one workgroup, a
+ *     function of the shape alone) and the scratch *workspace_doubles of the pass.  A shape above
+ *     the limits: VMP_ERR_UNSUPPORTED.
+ *   vmp_cmm_pack: x (N x D, row-major; dtype 0 = float64, 1 = int64, 2 = uint8, 3 = int32) and
+ *     mask (N x D bytes, non-zero = observed, or NULL: everything observed) to N D bytes.  A hidden
+ *     position gets 255 by a select whatever stands there (NaN, -1, 1e300).  An OBSERVED value that
+ *     is no integer in [0, M) gets 255 as well and sets *flag (device int32, cleared by the
+ *     caller): categorical.py's "Invalid category index".
+ *   vmp_cmm_tables: L = elog_p ((M, D K) category-major; NULL: zeros, the moments of Z under its
+ *     prior) and c[k] = elog_pi[k] - max_k elog_pi[k].
+ *   vmp_cmm_pass: logit_nk = c[k] + sum over the observed d of L[x_nd, d, k] (ascending d, c last),
+ *     lse and r = exp(logit - lse) over a lane group.  A byte b is observed when (unsigned) b < M;
+ *     no other byte ever becomes an address.  Out: S (M, D K) = sum_n r_nk [x_nd = m], Nk (K) and
+ *     scal[0] = sum lse over the rows with an observed entry, scal[1] = Nk . c, scal[2] = S . L;
+ *     with r_out (N x K) also r.  A row with nothing observed has r = softmax(c) (with labels: its
+ *     one-hot row), written to r_out, and adds exactly nothing to any sum.  `labels` (N int32)
+ *     non-NULL: r is one-hot, lse = 0 and L is not read.  ws: vmp_cmm_plan's doubles.  No atomics,
+ *     in LDS or in memory: the bits of every output depend on the inputs and (N, D, K, M) only,
+ *     with or without r_out.  N = 0 gives zeros.  The shape is judged before the pointers: a size
+ *     below 1 (N below 0): VMP_ERR_INVALID; above the limits: VMP_ERR_UNSUPPORTED; then a null
+ *     required argument: VMP_ERR_INVALID.  Nothing is launched after a refusal. */
+int32_t vmp_cmm_limits(int32_t *max_K, int32_t *min_M, int32_t *max_M, int32_t *max_cells);
+int32_t vmp_cmm_plan(int64_t N, int32_t D, int32_t K, int32_t M, int64_t *chunk_rows,
+                     int64_t *workspace_doubles);
+int32_t vmp_cmm_pack(vmp_ctx *ctx, int64_t N, int32_t D, int32_t M, int32_t dtype, const void *x,
+                     const uint8_t *mask, uint8_t *xb, int32_t *flag);
+int32_t vmp_cmm_tables(vmp_ctx *ctx, int32_t D, int32_t K, int32_t M, const double *elog_p,
+                       const double *elog_pi, double *L, double *c);
+int32_t vmp_cmm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, int32_t M, const uint8_t *xb,
+                     const int32_t *labels, const double *L, const double *c, double *ws,
+                     double *S, double *Nk, double *scal, double *r_out);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
