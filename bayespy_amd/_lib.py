@@ -270,6 +270,12 @@ SIGNATURES = {
     'vmp_cmm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'vmp_cmm_tables': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'vmp_cmm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 9),
+    'vmp_pmm_limits': (c_i32, [P(c_i32), P(c_i32), P(c_i32)]),
+    'vmp_pmm_plan': (c_i32, [c_i64, c_i32, c_i32, P(c_i64), P(c_i64)]),
+    'vmp_pmm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32] + [c_vp] * 7),
+    'vmp_pmm_tables': (c_i32, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 6),
+    'vmp_pmm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 11),
+    'vmp_pmm_update': (c_i32, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 7),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_hold_passes': (c_i32, [c_vp, c_i32]),

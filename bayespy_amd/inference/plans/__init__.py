@@ -15,6 +15,7 @@ from .hmm_cat import CategoricalHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
 from .cmm import CategoricalMixturePlan
+from .pmm import PoissonMixturePlan
 
 PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
 # engine='fused': a block's opt-in form takes the place of its default form
@@ -36,6 +37,9 @@ OPT_IN_MASKED = {DiagGaussianMixturePlan: [MaskedDiagGaussianMixturePlan]}
 # engine='fused': opt-in blocks tried after everything above (CategoricalMixturePlan takes the
 # mixtures of Categorical, with or without a mask, that every block above passes over in silence)
 OPT_IN_LAST = [CategoricalMixturePlan]
+# engine='fused': opt-in blocks for count data, tried after ``OPT_IN_LAST`` (PoissonMixturePlan takes
+# the mixtures of Poisson, with or without a mask, that every block above passes over in silence)
+OPT_IN_COUNTS = [PoissonMixturePlan]
 
 
 def _with_masked(types):
@@ -73,7 +77,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or type(p) in OPT_IN_MORE
                                  or any(type(p) in v for v in OPT_IN_AFTER.values())
                                  or any(type(p) in v for v in OPT_IN_MASKED.values())
-                                 or type(p) in OPT_IN_LAST
+                                 or type(p) in OPT_IN_LAST or type(p) in OPT_IN_COUNTS
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -124,7 +128,8 @@ def compile_model(nodes, engine=None, **options):
         plan._engine_request = 'generic'
         return [plan]
     types = [Q for P in PLAN_TYPES for Q in [OPT_IN_FORMS.get(P, P)] + OPT_IN_AFTER.get(P, [])] \
-        + _with_masked(opt_in_types() + OPT_IN_MORE) + OPT_IN_LAST if engine == 'fused' \
+        + _with_masked(opt_in_types() + OPT_IN_MORE) + OPT_IN_LAST + OPT_IN_COUNTS \
+        if engine == 'fused' \
         else PLAN_TYPES
     remaining = [n for n in nodes]
     plans = []

@@ -1,0 +1,591 @@
+"""
+Execution plan of the Poisson-mixture block (count clustering)
+
+    R = Dirichlet(const);  Z = Categorical(R, plates=(N, 1))
+    lam = Gamma(const, const, plates=(D, K));  X = Mixture(Z, Poisson, lam);  X.observe(x[, mask=m])
+
+with constant ``a``, ``a0``, ``b0``, x (N, D) counts of at most 65534, K <= 64 and D <= 1024; ``X``
+fully observed or observed with a mask of the full shape (N, D).  Opt-in:
+``VB(..., engine='fused')``; the default engine runs this model on the generic engine as before.
+The plan owns, in HBM: ``x`` as one uint16 per entry (0xFFFF = hidden), the parameters (a, b) and
+the moments (<lam>, <log lam>) of ``lam`` as (D K, 2) tables, those of ``R`` (K), the tables
+l = <log lam>, lb = <lam> and c that the last ``Z`` update used, and the statistics
+S[d, k] = sum_n r_nk x_nd, N_k and, with hidden entries, M[d, k] = sum_n r_nk m_nd.  Nothing of size
+(N, K) or (N, D, K) exists: the responsibilities of ``Z`` are formed inside ``vmp_pmm_pass`` and
+only on request written out (``Z.get_moments()``).
+
+All plate terms of the lower bound follow from the statistics, sum_n lse_n and the tables:
+    <log p(X)>           = S . <log lam> - M . <lam> - sum_observed lgamma(x + 1)   (M_dk = N_k
+                           where nothing is hidden; the last sum comes from the pack)
+    <log p(Z)> + entropy = sum_k N_k <log pi_k> + sum_n lse_n - N_k . c_used - scal[2]
+``l``, ``lb`` and ``c`` are written by a ``Z`` update only, so ``Z.get_moments()`` after a later
+``lam`` update is still that update's posterior.
+
+Masks: ``X.observe(x, mask=m)`` with ``m`` a boolean host array or a ``DeviceMask`` of shape
+exactly (N, D).  A hidden position becomes 0xFFFF when ``x`` is packed and is never interpreted:
+NaN, -1 or 1e300 may stand there.  The pack counts the hidden entries; the pass runs its form with
+two statistics only when there are any, so a mask of ones gives the bits of the unmasked run.  A
+row with nothing observed has ``Z.mask`` False: its moment is softmax(c) of the tables the last
+update used and it enters neither N_k nor the bound term of ``Z``.  A column with nothing observed
+leaves its ``lam`` at the prior, with a bound term of exactly zero.  A scalar mask or one that
+broadcasts over a plate is declined (generic engine).
+
+Checkpoints: the block writes its own ``plans/<i>/`` group (kind 'pmm'); a checkpoint whose mask
+differs is refused.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _delta
+from ._dirichlet import DirichletKernels, prior_table
+from .bmm import _mask_shape, _takes_mask
+
+from ... import _lib
+from ...device import get_runtime, ptr
+from ...nodes.node import Constant, DeviceMask
+from ...nodes.dirichlet import Dirichlet
+from ...nodes.categorical import Categorical
+from ...nodes.categorical_markov_chain import CategoricalMarkovChainToCategorical
+from ...nodes.gamma import Gamma
+from ...nodes.poisson import Poisson
+from ...nodes.mixture import Mixture
+
+_DTYPES = {'float64': 0, 'int64': 1, 'uint8': 2, 'int32': 3}
+_LIMITS = []
+
+
+def pmm_limits():
+    """(max K, max D, largest count) of the built pass: host-only ``vmp_pmm_limits``."""
+    if not _LIMITS:
+        v = [ctypes.c_int32() for _ in range(3)]
+        _lib.raise_for_status(_lib.load().vmp_pmm_limits(*[ctypes.byref(a) for a in v]))
+        _LIMITS.append(tuple(a.value for a in v))
+    return _LIMITS[0]
+
+
+def _limits_text():
+    return 'K <= %d, D <= %d and counts of at most %d' % pmm_limits()
+
+
+def _p(t):
+    return ptr(t) if t is not None else None
+
+
+class PMMKernels(DirichletKernels):
+
+    def __init__(self, rt):
+        self.rt, self.lib, self.ctx = rt, rt.lib, rt.ctx
+
+    def plan(self, N, D, K):
+        """(rows of a chunk, workspace doubles) of the pass."""
+        c, w = ctypes.c_int64(), ctypes.c_int64()
+        rc = self.lib.vmp_pmm_plan(N, D, K, ctypes.byref(c), ctypes.byref(w))
+        if rc != _lib.VMP_OK:
+            _lib.raise_for_status(rc, 'the fused Poisson-mixture block supports ' + _limits_text())
+        return c.value, w.value
+
+    def pack(self, N, D, dtype, x, mask, xp, flags, counts, lgam, ws):
+        self.rt.check(self.lib.vmp_pmm_pack(self.ctx, N, D, dtype, _p(x), _p(mask), _p(xp),
+                                            _p(flags), _p(counts), _p(lgam), _p(ws)))
+
+    def tables(self, D, K, form, lam_mom, elog_pi, l, lb, c, lsum=None):
+        self.rt.check(self.lib.vmp_pmm_tables(self.ctx, D, K, form, _p(lam_mom), _p(elog_pi),
+                                              _p(l), _p(lb), _p(c), _p(lsum)))
+
+    def pass_(self, N, D, K, hidden, xp, labels, l, lb, c, ws, S, M, Nk, scal, r_out=None):
+        self.rt.check(self.lib.vmp_pmm_pass(self.ctx, N, D, K, hidden, _p(xp), _p(labels), _p(l),
+                                            _p(lb), _p(c), _p(ws), _p(S), _p(M), _p(Nk), _p(scal),
+                                            _p(r_out)))
+
+    def update(self, D, K, per_element, prior_a, prior_b, S, cnt, par, mom, bound):
+        self.rt.check(self.lib.vmp_pmm_update(self.ctx, D, K, per_element, _p(prior_a),
+                                              _p(prior_b), _p(S), _p(cnt), _p(par), _p(mom),
+                                              _p(bound)))
+
+
+def _largest_host_count(X):
+    """The largest observed count where ``X`` holds a host array, else None (a device tensor is
+    judged by the pack)."""
+    x = X._data
+    if x is None or not isinstance(x, (np.ndarray, list, tuple, int, float, np.number)):
+        return None
+    a = np.asarray(x)
+    if a.dtype.kind not in 'iuf' or a.size == 0:
+        return None
+    m = X._mask
+    if m is not True and not isinstance(m, DeviceMask):
+        try:
+            a = a[np.broadcast_to(np.asarray(m, dtype=bool), a.shape)]
+        except ValueError:
+            return None
+    a = a[np.isfinite(a)] if a.dtype.kind == 'f' else a
+    return a.max() if a.size else None
+
+
+def _match(nodes, why):
+    for X in nodes:
+        if not isinstance(X, Mixture) or X.node_class is not Poisson:
+            continue
+        if isinstance(X.parents[0], CategoricalMarkovChainToCategorical):
+            continue            # a hidden Markov model: no block of this family
+
+        def no(msg, X=X):
+            if why is not None:
+                why.append('fused Poisson-mixture block, observed node %s: %s'
+                           % (X.name or '<unnamed>', msg))
+        if len(X.parents) != 2:
+            no('its parents are not (Categorical(Dirichlet), Gamma)')
+            continue
+        Z, lam = X.parents
+        if type(Z) is not Categorical or type(lam) is not Gamma \
+                or type(Z.parents[0]) is not Dirichlet:
+            no('its parents are not (Categorical(Dirichlet), Gamma)')
+            continue
+        R = Z.parents[0]
+        four = (X, Z, lam, R)
+        if not all(any(n is m for m in nodes) for n in four):
+            continue
+        if any(any(m != 1 for m in n.plates_multiplier) for n in four):
+            no('plates_multiplier (mini-batches) goes through the generic engine')
+            continue
+        if any(getattr(n, '_shard_axis', None) is not None for n in four):
+            no('a plate is sharded over ranks')
+            continue
+        if not _takes_mask(X):
+            no('it has a mask of shape %s: the block takes no mask or a mask of the full shape of '
+               'the plates of X, here %s; a scalar mask or one that broadcasts over a plate goes '
+               'through the generic engine' % (_mask_shape(X._mask), tuple(X.plates)))
+            continue
+        bad = [(n, p) for n in (lam, R) for p in n.parents if not isinstance(p, Constant)]
+        if bad:
+            no('a parameter of %s is a node (%s), not a constant'
+               % (bad[0][0].name, type(bad[0][1]).__name__))
+            continue
+        if X.cluster_plate != -1:
+            no('cluster_plate is %d, the block needs the clusters on the last plate axis (-1)'
+               % X.cluster_plate)
+            continue
+        if len(X.plates) != 2 or len(lam.plates) != 2:
+            no('it needs plates (N, D), X has plates %s and lam has plates %s'
+               % (X.plates, lam.plates))
+            continue
+        N, D = X.plates
+        K = X.clusters
+        if Z.plates != (N, 1) or lam.plates != (D, K) or any(p != 1 for p in R.plates):
+            no('plates of Z / lam / R are %s / %s / %s, not (N, 1) / (D, K) / ()'
+               % (Z.plates, lam.plates, R.plates))
+            continue
+        max_k, max_d, max_count = pmm_limits()
+        if K > max_k or D > max_d:
+            no('D = %d, K = %d exceed the limits of the block (%s)' % (D, K, _limits_text()))
+            continue
+        big = _largest_host_count(X)
+        if big is not None and big > max_count:
+            no('a count of %d exceeds the limits of the block (%s)' % (big, _limits_text()))
+            continue
+        kids = ((R, [Z]), (Z, [X]), (lam, [X]), (X, []))
+        if any([c for c, _ in n.children] != want for n, want in kids):
+            no('one of its roles has other children as well')
+            continue
+        if Z.observed or lam.observed or R.observed:
+            no('Z, lam or R is observed')
+            continue
+        inits = ((Z, 'Z', ('value',)), (lam, 'lam', ('value', 'parameters')),
+                 (R, 'R', ('parameters',)))
+        bad = [(nm, n._init[0]) for n, nm, ok in inits
+               if n._init is not None and n._init[0] not in ok]
+        if bad:
+            no('%s is initialised by %s' % bad[0])
+            continue
+        return dict(X=X, Z=Z, lam=lam, R=R)
+    return None
+
+
+class PoissonMixturePlan:
+
+    @staticmethod
+    def describe():
+        return ("Mixture(Categorical(Dirichlet(const), plates=(N, 1)), Poisson, "
+                "Gamma(const, const, plates=(D, K))), fully observed or observed with a mask of "
+                "the full shape (N, D), %s; a scalar mask or one that broadcasts over a plate is "
+                "declined" % _limits_text())
+
+    @staticmethod
+    def match(nodes, why=None):
+        return _match(nodes, why)
+
+    def __init__(self, roles, runtime=None, kernels=None):
+        self.roles = roles
+        self.X, self.Z, self.lam, self.R = roles['X'], roles['Z'], roles['lam'], roles['R']
+        self.N, self.D = self.X.plates
+        self.K = self.X.clusters
+        self._rt, self._kernels = runtime, kernels
+        self._ready = False
+        self._x_stale = False
+        self.maskd = None           # (N, D) uint8 in HBM when X has a mask
+        self.hidden = 0             # the form of the pass: 1 when the pack met a hidden entry
+        self._version = 0
+        self._L_version = -1
+        self._L = None
+        for nd in roles.values():
+            nd._plan = self
+
+    @property
+    def rt(self):
+        if self._rt is None:
+            self._rt = get_runtime()
+        return self._rt
+
+    @property
+    def kernels(self):
+        if self._kernels is None:
+            self._kernels = PMMKernels(self.rt)
+        return self._kernels
+
+    def nodes(self):
+        return list(self.roles.values())
+
+    def has_state(self):
+        return bool(self._ready)
+
+    def invalidate(self, node):
+        if node is self.X and node.observed and _takes_mask(node):
+            # new observations of the same shape, with any mask of the full shape or none: the
+            # counts are packed again, the posteriors stay
+            self._x_stale = True
+            self._version += 1
+            return
+        _delta.warn_state_discarded(self, node)
+        self._ready = False
+        self._version += 1
+        if PoissonMixturePlan.match(self.nodes()) is None:
+            from .generic import GenericPlan
+            GenericPlan(self.nodes())
+
+    # -- set-up ------------------------------------------------------------------------------------
+    def _up(self, a):
+        torch = self.rt.torch
+        return torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(self.rt.device)
+
+    def _upload_mask(self):
+        rt, torch = self.rt, self.rt.torch
+        m = self.X._mask
+        if m is True:
+            self.maskd = None
+        elif isinstance(m, DeviceMask):
+            self.maskd = m.tensor.to(rt.device).reshape(self.N, self.D).to(torch.uint8).contiguous()
+        else:
+            self.maskd = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(m, dtype=bool).reshape(self.N, self.D).astype(np.uint8))).to(rt.device)
+
+    def _pack(self):
+        """``X._data`` as 16 bits per entry; an observed value that is negative or no integer is
+        the reference's ValueError (poisson.py), one above the cap NotImplementedError."""
+        rt, torch = self.rt, self.rt.torch
+        N, D = self.N, self.D
+        x = self.X._data
+        if x is None:
+            raise ValueError('Node %s has not been observed' % self.X.name)
+        if isinstance(x, torch.Tensor):
+            t = x.to(rt.device)
+            if t.dtype == torch.bool:
+                t = t.to(torch.uint8)
+            if str(t.dtype).replace('torch.', '') not in _DTYPES:
+                t = t.to(torch.float64)
+        else:
+            a = np.asarray(x)
+            if a.dtype == bool:
+                a = a.astype(np.uint8)
+            if a.dtype.name not in _DTYPES:
+                a = a.astype(np.float64)
+            t = torch.from_numpy(np.array(np.broadcast_to(a, (N, D)), order='C')).to(rt.device)
+        if tuple(t.shape) != (N, D) or not t.is_contiguous():
+            t = t.expand(N, D).contiguous()
+        dtype = _DTYPES[str(t.dtype).replace('torch.', '')]
+        self.xp = torch.zeros(max(N * D, 4), dtype=torch.int16, device=rt.device)
+        flags = torch.zeros(3, dtype=torch.int32, device=rt.device)
+        counts = torch.zeros(2, dtype=torch.int64, device=rt.device)
+        self.kernels.pack(N, D, dtype, t, self.maskd, self.xp, flags, counts, self.lgam, self.ws)
+        f = flags.cpu().numpy()
+        if f[0]:
+            raise ValueError("Values must be integers" if f[2] else "Values must be positive")
+        if f[1]:
+            raise NotImplementedError('fused Poisson-mixture block: an observed count exceeds %d '
+                                      '(%s); the generic engine takes such data'
+                                      % (pmm_limits()[2], _limits_text()))
+        n = counts.cpu().numpy()
+        self.n_observed, self.n_hidden = int(n[0]), int(n[1])
+        self._x_stale = False
+
+    def _set_form(self):
+        """The form of the pass for the packed data; when it changes, the tables of the last ``Z``
+        update are formed again in the new one."""
+        hidden = 1 if self.n_hidden > 0 else 0
+        if hidden != self.hidden:
+            self.hidden = hidden
+            self._tables(self.lam_mom_used if self._used else None, self.elog_r_used)
+
+    def _const(self, i, what):
+        a = np.asarray(self.lam.parents[i].value, dtype=np.float64)
+        if np.any(a <= 0):
+            raise ValueError('%s of %s should be positive' % (what, self.lam.name))
+        return np.ascontiguousarray(np.broadcast_to(a, (self.D, self.K)))
+
+    def _materialize(self):
+        if self._ready:
+            if self._x_stale:
+                self._upload_mask()
+                self._pack()
+                self._set_form()
+                self._run_pass()
+            return
+        self._delta = _delta.delta_roles(self.roles)
+        rt, k = self.rt, self.kernels
+        torch = rt.torch
+        N, D, K = self.N, self.D, self.K
+        rt.sync_stream()
+        self._upload_mask()
+        self.chunk, wsd = k.plan(N, D, K)
+        self.ws = rt.empty(int(wsd))
+        self.lgam = rt.zeros(1)
+        self._pack()
+        self.hidden = 1 if self.n_hidden > 0 else 0
+        a0, b0 = self._const(0, 'a0'), self._const(1, 'b0')
+        pr = prior_table(self.R, (K,))
+        self.a0, self.b0, self.prior_r = self._up(a0), self._up(b0), self._up(pr)
+        self.lam_par, self.lam_mom = rt.empty(D * K, 2), rt.empty(D * K, 2)
+        self.lam_mom_used, self.elog_r_used = rt.zeros(D * K, 2), rt.zeros(K)
+        self._used = False          # whether the tables in use hold an observation term
+        self.alpha_r, self.elog_r = rt.empty(K), rt.empty(K)
+        self.l, self.lb, self.c = rt.zeros(D, K), rt.zeros(D, K), rt.zeros(K)
+        self.l_now, self.lb_now, self.c_now = rt.zeros(D, K), rt.zeros(D, K), rt.zeros(K)
+        self.lsum = rt.zeros(K)
+        self.S, self.M, self.Nk = rt.zeros(D, K), rt.zeros(D, K), rt.zeros(K)
+        self.ws_small = rt.empty(max(D * K, 1024))
+        # [0] sum lse, [1] N_k . c used, [2] S . l - M . lb used, [3] bound of lam, [4] of R,
+        # [5] S . <log lam>, [6] M . <lam> (N_k . sum_d <lam>), [7] N_k . <log pi>
+        self.scal = rt.zeros(8)
+        k.update(D, K, 0, self.a0, self.b0, None, None, self.lam_par, self.lam_mom,
+                 self.scal[3:4])
+        self._init_lam(a0, b0)
+        counts = None
+        init = self.R._init
+        if init is not None:
+            a = np.asarray(init[1][0], dtype=np.float64)
+            if np.any(a <= 0):
+                raise ValueError("Natural parameters should be positive")
+            counts = self._up(np.broadcast_to(a, (K,)) - pr)
+        k.dirichlet(1, K, K, 1, self.prior_r, counts, self.alpha_r, self.elog_r, self.ws_small,
+                    self.scal[4:5])
+        # Z: fixed labels, or its moments under the prior (no observation term)
+        self.labels = None
+        init = self.Z._init
+        if init is not None:
+            lab = np.asarray(init[1])
+            if lab.dtype.kind == 'f':
+                if np.any(lab != np.round(lab)):
+                    raise ValueError("Values must be integers")
+            elif lab.dtype.kind not in 'iub':
+                raise ValueError("Values must be integers")
+            lab = np.array(np.broadcast_to(lab, (N, 1)), dtype=np.int64).reshape(N)
+            if lab.size and (lab.min() < 0 or lab.max() >= K):
+                raise ValueError("Invalid category index")
+            self.labels = torch.from_numpy(lab.astype(np.int32)).to(rt.device)
+        self.elog_r_used.copy_(self.elog_r)
+        self._tables(None, self.elog_r_used)
+        self._ready = True
+        self._run_pass()
+
+    def _init_lam(self, a0, b0):
+        """A given initial state of ``lam`` (host, set-up): a point mass, or Gamma(a, b)."""
+        init = self.lam._init
+        if init is None:
+            return
+        D, K = self.D, self.K
+        if init[0] == 'value':
+            v = np.broadcast_to(np.asarray(init[1], dtype=np.float64), (D, K))
+            if np.any(v <= 0):
+                raise ValueError('the value given to %s should be positive' % self.lam.name)
+            self.lam_mom.copy_(self._up(np.stack([v, np.log(v)], -1).reshape(D * K, 2)))
+            self.lam_par.fill_(float('nan'))             # a point mass has no parameters
+            return
+        from scipy.special import digamma, gammaln
+        a, b = (np.broadcast_to(np.asarray(v, dtype=np.float64), (D, K)) for v in init[1][:2])
+        if np.any(a <= 0) or np.any(b <= 0):
+            raise ValueError('the parameters given to %s should be positive' % self.lam.name)
+        self.lam_par.copy_(self._up(np.stack([a, b], -1).reshape(D * K, 2)))
+        self.lam_mom.copy_(self._up(np.stack([a / b, digamma(a) - np.log(b)],
+                                             -1).reshape(D * K, 2)))
+        bound = a0 * (np.log(b0) - np.log(b)) - gammaln(a0) + gammaln(a) + (a0 - a) * digamma(a) \
+            + a - b0 * a / b
+        self.scal[3:4].copy_(self._up([bound.sum()]))
+
+    def _tables(self, lam_mom, elog_r):
+        """The tables of the pass, in its present form and centred (column 0 of every row taken
+        out: the logits stay small, the entropy does not notice), from the given moments (None: no
+        observation term)."""
+        self.kernels.tables(self.D, self.K, self.hidden | 2, lam_mom, elog_r, self.l, self.lb,
+                            self.c)
+
+    def _run_pass(self, r_out=None):
+        """The statistics of the present ``Z`` state (tables ``l`` / ``lb`` / ``c`` or labels)."""
+        self.kernels.pass_(self.N, self.D, self.K, self.hidden, self.xp, self.labels, self.l,
+                           self.lb, self.c, self.ws, self.S, self.M, self.Nk, self.scal, r_out)
+        self._version += 1
+
+    # -- operations ----------------------------------------------------------------------------------
+    def update(self, node):
+        self._materialize()
+        _delta.updated(self._delta, self.roles, node)
+        rt, k = self.rt, self.kernels
+        rt.sync_stream()
+        D, K = self.D, self.K
+        if node is self.Z:
+            self.labels = None
+            self.lam_mom_used.copy_(self.lam_mom)
+            self.elog_r_used.copy_(self.elog_r)
+            self._used = True
+            self._tables(self.lam_mom_used, self.elog_r_used)
+            self._run_pass()
+        elif node is self.lam:
+            k.update(D, K, self.hidden, self.a0, self.b0, self.S,
+                     self.M if self.hidden else self.Nk, self.lam_par, self.lam_mom,
+                     self.scal[3:4])
+        elif node is self.R:
+            k.dirichlet(1, K, K, 1, self.prior_r, self.Nk, self.alpha_r, self.elog_r,
+                        self.ws_small, self.scal[4:5])
+        else:
+            return
+        self._version += 1
+
+    def _lower_bound_terms(self):
+        self._materialize()
+        if self._L_version != self._version:
+            rt, k = self.rt, self.kernels
+            rt.sync_stream()
+            D, K = self.D, self.K
+            k.tables(D, K, self.hidden, self.lam_mom, self.elog_r, self.l_now, self.lb_now,
+                     self.c_now, self.lsum)
+            k.dot(D * K, self.S, self.l_now, self.ws_small, self.scal[5:6])
+            if self.hidden:
+                k.dot(D * K, self.M, self.lb_now, self.ws_small, self.scal[6:7])
+            else:
+                k.dot(K, self.Nk, self.lsum, self.ws_small, self.scal[6:7])
+            k.dot(K, self.Nk, self.elog_r, self.ws_small, self.scal[7:8])
+            s = self.scal.cpu().numpy()
+            lgam = float(self.lgam.cpu().numpy()[0])
+            entropy = 0.0 if self.labels is not None else float(s[0] - s[1] - s[2])
+            t = dict(X=float(s[5] - s[6]) - lgam, Z=float(s[7]) + entropy, lam=float(s[3]),
+                     R=float(s[4]))
+            t['total'] = t['X'] + t['Z'] + t['lam'] + t['R']
+            self._L = t
+            self._L_version = self._version
+        return _delta.bound_terms(self._L, self._delta)
+
+    def lower_bound_contribution(self, node):
+        terms = self._lower_bound_terms()
+        for key in ('X', 'Z', 'lam', 'R'):
+            if node is self.roles[key]:
+                return terms[key]
+        return 0.0
+
+    def responsibilities(self):
+        """(N, K) responsibilities of ``Z`` as a device array: formed by the pass in its write mode
+        from the tables of the last ``Z`` update; not kept."""
+        self._materialize()
+        rt = self.rt
+        rt.sync_stream()
+        r = rt.empty(self.N, self.K)
+        if self.N:
+            self._run_pass(r)
+        return r
+
+    def get_moments(self, node):
+        self._materialize()
+        D, K = self.D, self.K
+        if node is self.R:
+            return [self.elog_r.cpu().numpy().reshape(self.R.plates + (K,)).copy()]
+        if node is self.lam:
+            m = self.lam_mom.cpu().numpy().reshape(D, K, 2)
+            return [m[..., 0].copy(), m[..., 1].copy()]
+        if node is self.Z:
+            return [self.responsibilities().cpu().numpy().reshape(self.N, 1, K)]
+        if node is self.X:
+            xp = self.xp.cpu().numpy()[:self.N * D].view(np.uint16).reshape(self.N, D)
+            return [np.where(xp == 0xFFFF, 0, xp).astype(np.float64)]
+        raise NotImplementedError
+
+    def _host_mask(self):
+        """The mask as a boolean host array of shape (N, D), or None without one."""
+        m = self.X._mask
+        return None if m is True else np.asarray(m, dtype=bool).reshape(self.N, self.D)
+
+    def get_mask(self, node):
+        """``X``: its mask; ``Z``: any entry of the row observed, (N, 1); ``lam``: any entry of the
+        column observed, (D, 1); ``R``: any entry observed -- the masks the reference propagates
+        from ``X`` to its parents."""
+        m = self._host_mask()
+        if m is None:
+            return np.array(True)
+        if node is self.X:
+            return m.copy()
+        if node is self.Z:
+            return m.any(axis=1)[:, None]
+        if node is self.lam:
+            return m.any(axis=0)[:, None]
+        return np.array(bool(m.any()))
+
+    # -- persistence -----------------------------------------------------------------------------------
+    _SAVED = ('lam_par', 'lam_mom', 'lam_mom_used', 'alpha_r', 'elog_r', 'elog_r_used', 'l', 'lb',
+              'c', 'S', 'M', 'Nk', 'scal')
+
+    def save_state(self, put, nodes, index):
+        self._materialize()
+        base = 'plans/%d/' % index
+        _delta.save(put, base, self._delta)
+        put(base + 'kind', np.array([ord(ch) for ch in 'pmm'], dtype=np.uint8))
+        put(base + 'dims', np.array([self.N, self.D, self.K], dtype=np.int64))
+        put(base + 'flags', np.array([1 if self.labels is not None else 0,
+                                      1 if self._used else 0], dtype=np.int64))
+        if self.labels is not None:
+            put(base + 'labels', self.labels.cpu().numpy())
+        if self.maskd is not None:
+            put(base + 'mask', self.maskd.cpu().numpy())
+        for name in self._SAVED:
+            put(base + name, getattr(self, name).cpu().numpy())
+
+    def load_state(self, reader, nodes, index):
+        self._materialize()
+        base = 'plans/%d/' % index
+        if not reader.has(base + 'kind') or bytes(np.asarray(reader.get(base + 'kind'),
+                                                             dtype=np.uint8)) != b'pmm':
+            raise Exception("File does not contain the state of the fused Poisson-mixture block")
+        dims = tuple(int(v) for v in reader.get(base + 'dims'))
+        if dims != (self.N, self.D, self.K):
+            raise ValueError('checkpoint is for (N, D, K) = %s, the model has %s'
+                             % (dims, (self.N, self.D, self.K)))
+        saved = np.asarray(reader.get(base + 'mask'), dtype=np.uint8).reshape(-1) \
+            if reader.has(base + 'mask') else None
+        mine = None if self.maskd is None else self.maskd.cpu().numpy().reshape(-1)
+        if (saved is None) != (mine is None) or (saved is not None
+                                                 and not np.array_equal(saved != 0, mine != 0)):
+            raise ValueError('checkpoint was saved with %s, the model has %s: observe X with the '
+                             'mask of the checkpoint before loading it'
+                             % tuple('no mask on X' if m is None else
+                                     'a mask on X with %d of %d entries observed'
+                                     % (int(np.count_nonzero(m)), m.size) for m in (saved, mine)))
+        torch = self.rt.torch
+        self._delta = _delta.load(reader, base)
+        flags = np.asarray(reader.get(base + 'flags')).ravel()
+        if int(flags[0]):
+            self.labels = torch.from_numpy(
+                np.array(reader.get(base + 'labels'), dtype=np.int32)).to(self.rt.device)
+        else:
+            self.labels = None
+        self._used = bool(int(flags[1]))
+        for name in self._SAVED:
+            getattr(self, name).copy_(torch.from_numpy(
+                np.array(reader.get(base + name), dtype=np.float64)).reshape(
+                    getattr(self, name).shape).to(self.rt.device))
+        self._version += 1

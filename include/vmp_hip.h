@@ -1217,6 +1217,63 @@ int32_t vmp_cmm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, int32_t M, c
                      const int32_t *labels, const double *L, const double *c, double *ws,
                      double *S, double *Nk, double *scal, double *r_out);
 
+/* Poisson mixture: the plate pass and the update of the fused block
+ *     R = Dirichlet(a);  Z = Categorical(R, plates=(N, 1))
+ *     lam = Gamma(a0, b0, plates=(D, K));  X = Mixture(Z, Poisson, lam);  X.observe(x[, mask])
+ * (details: bayespy_amd/csrc/vmp_pmm.hip, vmp_pmm_dev.h).  N rows of D counts, K clusters; x is
+ * kept as one uint16 per entry, 0xFFFF = hidden; tables and statistics are (D x K), element (d, k)
+ * at d K + k; moment and parameter tables are (D K, 2): (<lam>, <log lam>) and (a, b).  No (N, K)
+ * or (N, D, K) array exists.
+ *   vmp_pmm_limits (host only): *max_K = 64, *max_D = 1024, *max_count = 65534.
+ *   vmp_pmm_plan (host only): for (N, D, K) the rows of a chunk *chunk_rows (one workgroup, a
+ *     function of the shape alone) and the scratch *workspace_doubles of the pass, which is never
+ *     below what vmp_pmm_pack needs (2048 doubles).
+ *   vmp_pmm_pack: x (N x D, row-major; dtype 0 = float64, 1 = int64, 2 = uint8, 3 = int32) and
+ *     mask (N x D bytes, non-zero = observed, or NULL: everything observed) to N D uint16.  A
+ *     hidden position gets 0xFFFF by a select whatever stands there (NaN, -1, 1e300).  An OBSERVED
+ *     value that is negative or no integer gets 0xFFFF as well and sets flags[0] (and flags[2] when
+ *     it is no integer: which of poisson.py's two messages applies); one above 65534 sets flags[1].
+ *     The checks come before any conversion to an integer.  flags: three device int32, cleared by
+ *     the caller.  counts[0] = the observed entries, counts[1] = the hidden ones (device int64);
+ *     *lgam = sum over the observed entries of lgamma(x + 1), per-block partials added in block
+ *     order, no atomics.  ws: 2048 doubles.
+ *   vmp_pmm_tables: l = <log lam>, lb = <lam>, lsum[k] = sum_d lb[d, k] (or NULL) and
+ *     c = elog_pi - lsum (nothing hidden) or elog_pi (bit 1 of form: hidden entries), less its
+ *     largest element.  Bit 2 of form: the tables of the pass, CENTRED -- column 0 of every row is
+ *     taken out of l and lb (and so of lsum), which moves all logits of a row alike: r and
+ *     scal[0] - scal[1] - scal[2] of the pass do not change, the logits stay small.  A NULL
+ *     lam_mom gives l = lb = 0: Z under its prior.
+ *   vmp_pmm_pass: hidden = 0: logit_nk = c[k] + sum_d x_nd l[d, k]; Out: S (D x K) = r^T x, Nk and
+ *     scal[0] = sum lse, scal[1] = Nk . c, scal[2] = S . l; M and lb are not touched.  hidden = 1:
+ *     logit_nk = c[k] + sum_d xt_nd l[d, k] - m_nd lb[d, k] with m = (x != 0xFFFF), xt = m o x; Out:
+ *     S = r^T xt, M = r^T m, Nk and scal[0] over the rows with an observed entry, scal[2] =
+ *     S . l - M . lb.  A row with nothing observed has r = softmax(c) (with labels: its one-hot
+ *     row), written to r_out, and adds nothing to Nk and scal[0].  `labels` (N int32) non-NULL: r
+ *     is one-hot, lse = 0.  r_out (N x K) is written on request only.  ws: vmp_pmm_plan's doubles.
+ *     No atomics: the bits of every output depend on x_packed, the tables and (N, D, K) only, with
+ *     or without r_out.  N = 0 gives zeros.  x_packed must be 2-byte aligned (8 for the fast loads).
+ *   vmp_pmm_update: one launch; a = a0 + S, b = b0 + cnt with cnt = Nk (K; per_element = 0) or M
+ *     (D x K; per_element = 1); par = (a, b), mom = (a / b, psi(a) - log b), *bound = <log p(lam)> -
+ *     <log q(lam)>, exactly zero for an element at its prior.  S or cnt NULL: the prior.
+ *   The shape is judged before the pointers: a size below 1 (N below 0): VMP_ERR_INVALID; K or D
+ *   above the limits: VMP_ERR_UNSUPPORTED; then a null required argument: VMP_ERR_INVALID.  Nothing
+ *   is launched after a refusal. */
+int32_t vmp_pmm_limits(int32_t *max_K, int32_t *max_D, int32_t *max_count);
+int32_t vmp_pmm_plan(int64_t N, int32_t D, int32_t K, int64_t *chunk_rows,
+                     int64_t *workspace_doubles);
+int32_t vmp_pmm_pack(vmp_ctx *ctx, int64_t N, int32_t D, int32_t dtype, const void *x,
+                     const uint8_t *mask, uint16_t *x_packed, int32_t *flags, int64_t *counts,
+                     double *lgam, double *ws);
+int32_t vmp_pmm_tables(vmp_ctx *ctx, int32_t D, int32_t K, int32_t form, const double *lam_mom,
+                       const double *elog_pi, double *l, double *lb, double *c, double *lsum);
+int32_t vmp_pmm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, int32_t hidden,
+                     const uint16_t *x_packed, const int32_t *labels, const double *l,
+                     const double *lb, const double *c, double *ws, double *S, double *M,
+                     double *Nk, double *scal, double *r_out);
+int32_t vmp_pmm_update(vmp_ctx *ctx, int32_t D, int32_t K, int32_t per_element,
+                       const double *prior_a, const double *prior_b, const double *S,
+                       const double *cnt, double *par, double *mom, double *bound);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
