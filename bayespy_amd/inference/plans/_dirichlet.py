@@ -1,6 +1,8 @@
 """
-What the blocks with Dirichlet tables (LDA, Bernoulli mixture, HMM) share: the wrappers of
-``vmp_lda_dirichlet`` / ``vmp_lda_dot`` and the host table of a constant concentration.
+What the blocks with Dirichlet tables share: the wrappers of ``vmp_lda_dirichlet`` /
+``vmp_lda_dot`` and the host table of a constant concentration.  Its users are the plans of lda.py,
+hmm.py, hmm_cat.py and the plate-mixture blocks (bmm.py, dgmm.py, dgmm_masked.py, cmm.py, pmm.py,
+through _mixture.py for the mixing weights).
 """
 import numpy as np
 

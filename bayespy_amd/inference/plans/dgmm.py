@@ -33,16 +33,12 @@ import numpy as np
 
 from . import _delta
 from ._dirichlet import DirichletKernels, prior_table
-from .bmm import _mask_shape
+from ._mixture import (MixtureSpec, PlateMixturePlan, _p, cluster_plate_reason,
+                       match_plate_mixture)
 
 from ... import _lib
-from ...device import get_runtime, ptr
-from ...nodes.node import Constant
-from ...nodes.dirichlet import Dirichlet
-from ...nodes.categorical import Categorical
 from ...nodes.gaussian import GaussianARD
 from ...nodes.gamma import Gamma
-from ...nodes.mixture import Mixture
 
 _LIMITS = []
 
@@ -54,10 +50,6 @@ def dgmm_limits():
         _lib.raise_for_status(_lib.load().vmp_dgmm_limits(ctypes.byref(k), ctypes.byref(d)))
         _LIMITS.append((k.value, d.value))
     return _LIMITS[0]
-
-
-def _p(t):
-    return ptr(t) if t is not None else None
 
 
 class DGMMKernels(DirichletKernels):
@@ -89,94 +81,48 @@ class DGMMKernels(DirichletKernels):
                                                _p(bound)))
 
 
-def _match(nodes, why, masked=False):
-    """``masked``: the matcher of the block with missing observations (dgmm_masked.py), which takes
-    a mask of the full shape of the plates of Y where this block takes none."""
-    for Y in nodes:
-        if not isinstance(Y, Mixture) or Y.node_class is not GaussianARD:
-            continue
+def _plates_reason(Y, mu):
+    if len(Y.plates) != 2 or len(mu.plates) != 2 or mu.ndim != 0 or Y.ndim != 0:
+        return ('it needs plates (N, D) and scalar GaussianARD variables, Y has plates %s and mu '
+                'has plates %s and shape %s' % (Y.plates, mu.plates, mu.shape))
 
-        def no(msg, Y=Y):
-            if why is not None:
-                why.append('fused diagonal-Gaussian-mixture block, observed node %s: %s'
-                           % (Y.name or '<unnamed>', msg))
-        if len(Y.parents) != 3:
-            no('the mixed GaussianARD has further constructor arguments')
-            continue
-        Z, mu, tau = Y.parents
-        if type(Z) is not Categorical or type(mu) is not GaussianARD or type(tau) is not Gamma \
-                or type(Z.parents[0]) is not Dirichlet:
-            no('its parents are not (Categorical(Dirichlet), GaussianARD, Gamma)')
-            continue
-        alpha = Z.parents[0]
-        five = (Y, Z, mu, tau, alpha)
-        if not all(any(n is m for m in nodes) for n in five):
-            continue
-        if any(any(m != 1 for m in n.plates_multiplier) for n in five):
-            no('plates_multiplier (mini-batches) goes through the generic engine')
-            continue
-        if any(getattr(n, '_shard_axis', None) is not None for n in five):
-            no('a plate is sharded over ranks')
-            continue
-        if not masked and Y._mask is not True:
-            no('it has a mask: the block takes fully observed data only; a mask goes through the '
-               'generic engine')
-            continue
-        if masked and Y._mask is True:
-            continue                    # no mask: the model of the block without one, no reason
-        if masked and _mask_shape(Y._mask) != tuple(Y.plates):
-            no('it has a mask of shape %s: the block with missing observations takes a mask of '
-               'the full shape of the plates of Y, here %s; a scalar mask or one that broadcasts '
-               'over a plate goes through the generic engine'
-               % (_mask_shape(Y._mask), tuple(Y.plates)))
-            continue
-        bad = [(n, p) for n in (mu, tau, alpha) for p in n.parents if not isinstance(p, Constant)]
-        if bad:
-            no('a parameter of %s is a node (%s), not a constant'
-               % (bad[0][0].name, type(bad[0][1]).__name__))
-            continue
-        if Y.cluster_plate != -1:
-            no('cluster_plate is %d, the block needs the clusters on the last plate axis (-1)'
-               % Y.cluster_plate)
-            continue
-        if len(Y.plates) != 2 or len(mu.plates) != 2 or mu.ndim != 0 or Y.ndim != 0:
-            no('it needs plates (N, D) and scalar GaussianARD variables, Y has plates %s and mu has '
-               'plates %s and shape %s' % (Y.plates, mu.plates, mu.shape))
-            continue
-        N, D = Y.plates
-        K = Y.clusters
-        if Z.plates != (N, 1) or mu.plates != (D, K) or tau.plates != (D, K) \
-                or any(p != 1 for p in alpha.plates):
-            no('plates of Z / mu / tau / alpha are %s / %s / %s / %s, not (N, 1) / (D, K) / (D, K) '
-               '/ ()' % (Z.plates, mu.plates, tau.plates, alpha.plates))
-            continue
-        if masked:
-            from .dgmm_masked import dgmm_masked_limits
-            max_k, max_d = dgmm_masked_limits()
-        else:
-            max_k, max_d = dgmm_limits()
+
+def _limits_reason(limits, which=''):
+    """The check of D and K against ``limits()`` of the block (``which``: ' with a mask')."""
+    def reason(r):
+        D, K = r['Y'].plates[1], r['Y'].clusters
+        max_k, max_d = limits()
         if K > max_k or D > max_d:
-            no('D = %d, K = %d exceed the limits of the block%s (D <= %d, K <= %d)'
-               % (D, K, ' with a mask' if masked else '', max_d, max_k))
-            continue
-        kids = ((alpha, [Z]), (Z, [Y]), (mu, [Y]), (tau, [Y]), (Y, []))
-        if any([c for c, _ in n.children] != want for n, want in kids):
-            no('one of its roles has other children as well')
-            continue
-        if Z.observed or mu.observed or tau.observed or alpha.observed:
-            no('Z, mu, tau or alpha is observed')
-            continue
-        inits = ((Z, 'Z', ('value',)), (mu, 'mu', ('value', 'parameters')),
-                 (tau, 'tau', ('parameters',)), (alpha, 'alpha', ('parameters',)))
-        bad = [(nm, n._init[0]) for n, nm, ok in inits if n._init is not None and n._init[0] not in ok]
-        if bad:
-            no('%s is initialised by %s' % bad[0])
-            continue
-        return dict(Y=Y, Z=Z, mu=mu, tau=tau, alpha=alpha)
-    return None
+            return ('D = %d, K = %d exceed the limits of the block%s (D <= %d, K <= %d)'
+                    % (D, K, which, max_d, max_k))
+    return reason
 
 
-class DiagGaussianMixturePlan:
+# dgmm_masked.py replaces ``mask`` and ``limits``: it takes a mask of the full shape of the plates
+# of Y where this block takes none
+_SPEC = MixtureSpec(
+    label='fused diagonal-Gaussian-mixture block',
+    takes=lambda Y: Y.node_class is GaussianARD,
+    observed='Y', weights='alpha',
+    params=(('mu', GaussianARD, ('value', 'parameters')), ('tau', Gamma, ('parameters',))),
+    arity='the mixed GaussianARD has further constructor arguments',
+    parents='its parents are not (Categorical(Dirichlet), GaussianARD, Gamma)',
+    constant='a parameter of %s is a node (%s), not a constant',
+    role_plates='plates of Z / mu / tau / alpha are {} / {} / {} / {}, not (N, 1) / (D, K) / '
+                '(D, K) / ()',
+    mask=lambda Y: None if Y._mask is True else
+    'it has a mask: the block takes fully observed data only; a mask goes through the generic '
+    'engine',
+    plates=lambda Y, mu: cluster_plate_reason(Y) or _plates_reason(Y, mu),
+    limits=_limits_reason(dgmm_limits))
+
+
+class DiagGaussianMixturePlan(PlateMixturePlan):
+
+    KERNELS = DGMMKernels
+    LABEL, KIND = _SPEC.label, 'dgmm'
+    OBSERVED, WEIGHTS = 'Y', 'alpha'
+    TERMS = ('Y', 'Z', 'mu', 'tau', 'alpha')
 
     @staticmethod
     def describe():
@@ -186,58 +132,18 @@ class DiagGaussianMixturePlan:
 
     @staticmethod
     def match(nodes, why=None):
-        return _match(nodes, why)
+        return match_plate_mixture(nodes, why, _SPEC)
 
-    def __init__(self, roles, runtime=None, kernels=None):
-        self.roles = roles
-        self.Y, self.Z, self.mu, self.tau, self.alpha = (roles[k] for k in
-                                                         ('Y', 'Z', 'mu', 'tau', 'alpha'))
-        self.N, self.D = self.Y.plates
-        self.K = self.Y.clusters
-        self._rt, self._kernels = runtime, kernels
-        self._ready = False
-        self._y_stale = False
-        self._version = 0
-        self._L_version = -1
-        self._L = None
-        for nd in roles.values():
-            nd._plan = self
+    def _repacks(self, node):
+        return node._mask is True
 
-    @property
-    def rt(self):
-        if self._rt is None:
-            self._rt = get_runtime()
-        return self._rt
-
-    @property
-    def kernels(self):
-        if self._kernels is None:
-            self._kernels = DGMMKernels(self.rt)
-        return self._kernels
-
-    def nodes(self):
-        return list(self.roles.values())
-
-    def has_state(self):
-        return bool(self._ready)
-
-    def invalidate(self, node):
-        if node is self.Y and node.observed and node._mask is True:
-            # new observations of the same shape: y is uploaded again, the posteriors stay
-            self._y_stale = True
-            self._version += 1
-            return
-        _delta.warn_state_discarded(self, node)
-        self._ready = False
-        self._version += 1
-        if DiagGaussianMixturePlan.match(self.nodes()) is None:
-            from .dgmm_masked import MaskedDiagGaussianMixturePlan
-            if MaskedDiagGaussianMixturePlan.match(self.nodes()) is not None:
-                # Y was observed with a mask of its full shape: the block for missing observations
-                MaskedDiagGaussianMixturePlan(self.roles, runtime=self._rt)
-                return
-            from .generic import GenericPlan
-            GenericPlan(self.nodes())
+    def _hand_over(self):
+        from .dgmm_masked import MaskedDiagGaussianMixturePlan
+        if MaskedDiagGaussianMixturePlan.match(self.nodes()) is not None:
+            # Y was observed with a mask of its full shape: the block for missing observations
+            MaskedDiagGaussianMixturePlan(self.roles, runtime=self._rt)
+        else:
+            super()._hand_over()
 
     # -- set-up ------------------------------------------------------------------------------------
     def _upload_y(self):
@@ -254,11 +160,7 @@ class DiagGaussianMixturePlan:
         if tuple(t.shape) != (N, D) or not t.is_contiguous():
             t = t.expand(N, D).contiguous()
         self.y = t
-        self._y_stale = False
-
-    def _up(self, a):
-        torch = self.rt.torch
-        return torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(self.rt.device)
+        self._stale = False
 
     def _const(self, node, i, positive, what):
         a = np.asarray(node.parents[i].value, dtype=np.float64)
@@ -268,14 +170,13 @@ class DiagGaussianMixturePlan:
 
     def _materialize(self):
         if self._ready:
-            if self._y_stale:
+            if self._stale:
                 self._upload_y()
                 self._run_pass()
             return
         self._delta = _delta.delta_roles(self.roles)
         rt, k = self.rt, self.kernels
-        torch = rt.torch
-        N, D, K = self.N, self.D, self.K
+        D, K = self.D, self.K
         rt.sync_stream()
         self.chunk, wsd = self._plan_pass()
         self._upload_y()
@@ -291,7 +192,6 @@ class DiagGaussianMixturePlan:
         self.h_now, self.q_now, self.c_now = rt.zeros(D, K), rt.zeros(D, K), rt.zeros(K)
         self.gsum = rt.zeros(K)
         self.S1, self.S2, self.Nk = rt.zeros(D, K), rt.zeros(D, K), rt.zeros(K)
-        self._alloc_more()
         self.ws = rt.empty(int(wsd))
         self.ws_small = rt.empty(max(D * K, 1024))
         # [0] sum lse, [1] N_k . c used, [2] S1 . h + S2 . q used, [3] bound of mu, [4] of tau,
@@ -304,29 +204,8 @@ class DiagGaussianMixturePlan:
                  self.scal[4:5])
         self._init_mu(m0, beta0)
         self._init_tau(a0, b0)
-        counts = None
-        init = self.alpha._init
-        if init is not None:
-            a = np.asarray(init[1][0], dtype=np.float64)
-            if np.any(a <= 0):
-                raise ValueError("Natural parameters should be positive")
-            counts = self._up(np.broadcast_to(a, (K,)) - pr)
-        k.dirichlet(1, K, K, 1, self.prior_r, counts, self.alpha_r, self.elog_r, self.ws_small,
-                    self.scal[5:6])
-        # Z: fixed labels, or its moments under the prior (no observation term)
-        self.labels = None
-        init = self.Z._init
-        if init is not None:
-            lab = np.asarray(init[1])
-            if lab.dtype.kind == 'f':
-                if np.any(lab != np.round(lab)):
-                    raise ValueError("Values must be integers")
-            elif lab.dtype.kind not in 'iub':
-                raise ValueError("Values must be integers")
-            lab = np.array(np.broadcast_to(lab, (N, 1)), dtype=np.int64).reshape(N)
-            if lab.size and (lab.min() < 0 or lab.max() >= K):
-                raise ValueError("Invalid category index")
-            self.labels = torch.from_numpy(lab.astype(np.int32)).to(rt.device)
+        self._weights_step(5, self._weights_init_counts(pr))
+        self._labels_from_init()
         self._tables(None, None)
         self._ready = True
         self._run_pass()
@@ -371,9 +250,6 @@ class DiagGaussianMixturePlan:
     def _plan_pass(self):
         return self.kernels.plan(self.N, self.D, self.K)
 
-    def _alloc_more(self):
-        pass
-
     def _tables(self, mu_mom, tau_mom):
         """The tables of the pass from the given moments (None: no observation term)."""
         self.kernels.tables(self.D, self.K, mu_mom, tau_mom, self.elog_r, self.h, self.q, self.c)
@@ -392,9 +268,7 @@ class DiagGaussianMixturePlan:
     def update(self, node):
         self._materialize()
         _delta.updated(self._delta, self.roles, node)
-        rt, k = self.rt, self.kernels
-        rt.sync_stream()
-        K = self.K
+        self.rt.sync_stream()
         if node is self.Z:
             self.labels = None
             self._tables(self.mu_mom, self.tau_mom)
@@ -406,50 +280,23 @@ class DiagGaussianMixturePlan:
             self._update_from_statistics(1, self.a0, self.b0, self.mu_mom, self.tau_par,
                                          self.tau_mom, self.scal[4:5])
         elif node is self.alpha:
-            k.dirichlet(1, K, K, 1, self.prior_r, self.Nk, self.alpha_r, self.elog_r,
-                        self.ws_small, self.scal[5:6])
+            self._weights_step(5, self.Nk)
         else:
             return
         self._version += 1
 
-    def _lower_bound_terms(self):
-        self._materialize()
-        if self._L_version != self._version:
-            rt, k = self.rt, self.kernels
-            rt.sync_stream()
-            D, K = self.D, self.K
-            k.tables(D, K, self.mu_mom, self.tau_mom, self.elog_r, self.h_now, self.q_now,
-                     self.c_now, self.gsum)
-            k.dot(D * K, self.S1, self.h_now, self.ws_small, self.scal[6:7])
-            k.dot(D * K, self.S2, self.q_now, self.ws_small, self.scal[7:8])
-            k.dot(K, self.Nk, self.gsum, self.ws_small, self.scal[8:9])
-            k.dot(K, self.Nk, self.elog_r, self.ws_small, self.scal[9:10])
-            s = self.scal.cpu().numpy()
-            entropy = 0.0 if self.labels is not None else float(s[0] - s[1] - s[2])
-            t = dict(Y=float(s[6] + s[7] + s[8]) - 0.5 * self.N * D * np.log(2 * np.pi),
-                     Z=float(s[9]) + entropy, mu=float(s[3]), tau=float(s[4]), alpha=float(s[5]))
-            t['total'] = t['Y'] + t['Z'] + t['mu'] + t['tau'] + t['alpha']
-            self._L = t
-            self._L_version = self._version
-        return _delta.bound_terms(self._L, self._delta)
-
-    def lower_bound_contribution(self, node):
-        terms = self._lower_bound_terms()
-        for key in ('Y', 'Z', 'mu', 'tau', 'alpha'):
-            if node is self.roles[key]:
-                return terms[key]
-        return 0.0
-
-    def responsibilities(self):
-        """(N, K) responsibilities of ``Z`` as a device array: formed by the pass in its write mode
-        from the tables of the last ``Z`` update; not kept."""
-        self._materialize()
-        rt = self.rt
-        rt.sync_stream()
-        r = rt.empty(self.N, self.K)
-        if self.N:
-            self._run_pass(r)
-        return r
+    def _bound_terms(self):
+        k = self.kernels
+        D, K = self.D, self.K
+        k.tables(D, K, self.mu_mom, self.tau_mom, self.elog_r, self.h_now, self.q_now,
+                 self.c_now, self.gsum)
+        k.dot(D * K, self.S1, self.h_now, self.ws_small, self.scal[6:7])
+        k.dot(D * K, self.S2, self.q_now, self.ws_small, self.scal[7:8])
+        k.dot(K, self.Nk, self.gsum, self.ws_small, self.scal[8:9])
+        k.dot(K, self.Nk, self.elog_r, self.ws_small, self.scal[9:10])
+        s, entropy = self._host_scal()
+        return dict(Y=float(s[6] + s[7] + s[8]) - 0.5 * self.N * D * np.log(2 * np.pi),
+                    Z=float(s[9]) + entropy, mu=float(s[3]), tau=float(s[4]), alpha=float(s[5]))
 
     def get_moments(self, node):
         self._materialize()
@@ -466,62 +313,6 @@ class DiagGaussianMixturePlan:
             return [y, y * y]
         raise NotImplementedError
 
-    def get_mask(self, node):
-        return np.array(True)
-
     # -- persistence -----------------------------------------------------------------------------------
     _SAVED = ('mu_par', 'mu_mom', 'tau_par', 'tau_mom', 'alpha_r', 'elog_r', 'h', 'q', 'c', 'S1',
               'S2', 'Nk', 'scal')
-
-    def save_state(self, put, nodes, index):
-        self._materialize()
-        base = 'plans/%d/' % index
-        _delta.save(put, base, self._delta)
-        put(base + 'kind', np.array([ord(ch) for ch in 'dgmm'], dtype=np.uint8))
-        put(base + 'dims', np.array([self.N, self.D, self.K], dtype=np.int64))
-        put(base + 'flags', np.array([1 if self.labels is not None else 0], dtype=np.int64))
-        if self.labels is not None:
-            put(base + 'labels', self.labels.cpu().numpy())
-        self._save_more(put, base)
-        for name in self._saved():
-            put(base + name, getattr(self, name).cpu().numpy())
-
-    def _saved(self):
-        return self._SAVED
-
-    def _save_more(self, put, base):
-        pass
-
-    def _check_more(self, reader, base):
-        """A checkpoint of the block with missing observations is not this block's."""
-        if reader.has(base + 'mask'):
-            saved = np.asarray(reader.get(base + 'mask'), dtype=np.uint8).reshape(-1)
-            raise ValueError('checkpoint was saved with a mask on Y with %d of %d entries '
-                             'observed, the model has no mask on Y: observe Y with the mask of '
-                             'the checkpoint before loading it'
-                             % (int(np.count_nonzero(saved)), saved.size))
-
-    def load_state(self, reader, nodes, index):
-        self._materialize()
-        base = 'plans/%d/' % index
-        if not reader.has(base + 'kind') or bytes(np.asarray(reader.get(base + 'kind'),
-                                                             dtype=np.uint8)) != b'dgmm':
-            raise Exception("File does not contain the state of the fused diagonal-Gaussian-"
-                            "mixture block")
-        dims = tuple(int(v) for v in reader.get(base + 'dims'))
-        if dims != (self.N, self.D, self.K):
-            raise ValueError('checkpoint is for (N, D, K) = %s, the model has %s'
-                             % (dims, (self.N, self.D, self.K)))
-        self._check_more(reader, base)
-        torch = self.rt.torch
-        self._delta = _delta.load(reader, base)
-        if int(np.asarray(reader.get(base + 'flags')).ravel()[0]):
-            self.labels = torch.from_numpy(
-                np.array(reader.get(base + 'labels'), dtype=np.int32)).to(self.rt.device)
-        else:
-            self.labels = None
-        for name in self._saved():
-            getattr(self, name).copy_(torch.from_numpy(
-                np.array(reader.get(base + name), dtype=np.float64)).reshape(
-                    getattr(self, name).shape).to(self.rt.device))
-        self._version += 1

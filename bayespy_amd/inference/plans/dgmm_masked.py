@@ -33,13 +33,11 @@ import ctypes
 
 import numpy as np
 
-from . import _delta
-from .bmm import _mask_shape
-from .dgmm import DiagGaussianMixturePlan, DGMMKernels, _match, _p
+from ._mixture import _mask_shape, _p, match_plate_mixture
+from .dgmm import DiagGaussianMixturePlan, DGMMKernels, _SPEC, _limits_reason
 
 from ... import _lib
 from ...device import ptr
-from ...nodes.node import DeviceMask
 
 _LIMITS = []
 
@@ -87,7 +85,23 @@ def _full_mask(node):
     return node._mask is not True and _mask_shape(node._mask) == tuple(node.plates)
 
 
+def _mask_reason(Y):
+    if Y._mask is True:
+        return ''                   # no mask: the model of the block without one, no reason
+    if not _full_mask(Y):
+        return ('it has a mask of shape %s: the block with missing observations takes a mask of '
+                'the full shape of the plates of Y, here %s; a scalar mask or one that broadcasts '
+                'over a plate goes through the generic engine'
+                % (_mask_shape(Y._mask), tuple(Y.plates)))
+
+
+_MASKED_SPEC = _SPEC._replace(mask=_mask_reason,
+                              limits=_limits_reason(dgmm_masked_limits, ' with a mask'))
+
+
 class MaskedDiagGaussianMixturePlan(DiagGaussianMixturePlan):
+
+    KERNELS = MaskedDGMMKernels
 
     @staticmethod
     def describe():
@@ -99,55 +113,30 @@ class MaskedDiagGaussianMixturePlan(DiagGaussianMixturePlan):
 
     @staticmethod
     def match(nodes, why=None):
-        return _match(nodes, why, masked=True)
+        return match_plate_mixture(nodes, why, _MASKED_SPEC)
 
-    def __init__(self, roles, runtime=None, kernels=None):
-        super().__init__(roles, runtime=runtime, kernels=kernels)
-        self.maskd = None           # (N, D) uint8 in HBM
-
-    @property
-    def kernels(self):
-        if self._kernels is None:
-            self._kernels = MaskedDGMMKernels(self.rt)
-        return self._kernels
-
-    def invalidate(self, node):
-        if node is self.Y and node.observed and _full_mask(node):
-            # new observations and a new mask of the same shape: y is packed again, the
-            # posteriors stay
-            self._y_stale = True
-            self._version += 1
-            return
-        _delta.warn_state_discarded(self, node)
-        self._ready = False
-        self._version += 1
-        if MaskedDiagGaussianMixturePlan.match(self.nodes()) is None:
-            from .generic import GenericPlan
-            GenericPlan(self.nodes())
+    def _repacks(self, node):
+        return _full_mask(node)
 
     # -- set-up ------------------------------------------------------------------------------------
     def _upload_y(self):
         """The mask, then the plan's own copy of y with the hidden pattern in it."""
         rt, torch = self.rt, self.rt.torch
-        N, D = self.N, self.D
-        m = self.Y._mask
-        if isinstance(m, DeviceMask):
-            self.maskd = m.tensor.to(rt.device).reshape(N, D).to(torch.uint8).contiguous()
-        else:
-            self.maskd = torch.from_numpy(np.ascontiguousarray(
-                np.asarray(m, dtype=bool).reshape(N, D).astype(np.uint8))).to(rt.device)
+        self._upload_mask()
         super()._upload_y()
         raw = self.y
         self.y = torch.empty_like(raw)
         self.n_obs = torch.zeros(1, dtype=torch.int64, device=rt.device)
-        self.kernels.pack_masked(N, D, raw, self.maskd, self.y, self.n_obs)
+        self.kernels.pack_masked(self.N, self.D, raw, self.maskd, self.y, self.n_obs)
+
+    def _materialize(self):
+        if not self._ready:
+            rt, D, K = self.rt, self.D, self.K
+            self.M, self.g, self.g_now = rt.zeros(D, K), rt.zeros(D, K), rt.zeros(D, K)
+        super()._materialize()
 
     def _plan_pass(self):
         return self.kernels.plan_masked(self.N, self.D, self.K)
-
-    def _alloc_more(self):
-        rt, D, K = self.rt, self.D, self.K
-        self.M, self.g, self.g_now = rt.zeros(D, K), rt.zeros(D, K), rt.zeros(D, K)
 
     def _tables(self, mu_mom, tau_mom):
         self.kernels.tables_masked(self.D, self.K, mu_mom, tau_mom, self.elog_r, self.h, self.q,
@@ -164,27 +153,19 @@ class MaskedDiagGaussianMixturePlan(DiagGaussianMixturePlan):
         self._version += 1
 
     # -- operations ----------------------------------------------------------------------------------
-    def _lower_bound_terms(self):
-        self._materialize()
-        if self._L_version != self._version:
-            rt, k = self.rt, self.kernels
-            rt.sync_stream()
-            D, K = self.D, self.K
-            k.tables_masked(D, K, self.mu_mom, self.tau_mom, self.elog_r, self.h_now, self.q_now,
-                            self.g_now, self.c_now)
-            k.dot(D * K, self.S1, self.h_now, self.ws_small, self.scal[6:7])
-            k.dot(D * K, self.S2, self.q_now, self.ws_small, self.scal[7:8])
-            k.dot(D * K, self.M, self.g_now, self.ws_small, self.scal[8:9])
-            k.dot(K, self.Nk, self.elog_r, self.ws_small, self.scal[9:10])
-            s = self.scal.cpu().numpy()
-            n_obs = int(self.n_obs.cpu().numpy()[0])
-            entropy = 0.0 if self.labels is not None else float(s[0] - s[1] - s[2])
-            t = dict(Y=float(s[6] + s[7] + s[8]) - 0.5 * n_obs * np.log(2 * np.pi),
-                     Z=float(s[9]) + entropy, mu=float(s[3]), tau=float(s[4]), alpha=float(s[5]))
-            t['total'] = t['Y'] + t['Z'] + t['mu'] + t['tau'] + t['alpha']
-            self._L = t
-            self._L_version = self._version
-        return _delta.bound_terms(self._L, self._delta)
+    def _bound_terms(self):
+        k = self.kernels
+        D, K = self.D, self.K
+        k.tables_masked(D, K, self.mu_mom, self.tau_mom, self.elog_r, self.h_now, self.q_now,
+                        self.g_now, self.c_now)
+        k.dot(D * K, self.S1, self.h_now, self.ws_small, self.scal[6:7])
+        k.dot(D * K, self.S2, self.q_now, self.ws_small, self.scal[7:8])
+        k.dot(D * K, self.M, self.g_now, self.ws_small, self.scal[8:9])
+        k.dot(K, self.Nk, self.elog_r, self.ws_small, self.scal[9:10])
+        s, entropy = self._host_scal()
+        n_obs = int(self.n_obs.cpu().numpy()[0])
+        return dict(Y=float(s[6] + s[7] + s[8]) - 0.5 * n_obs * np.log(2 * np.pi),
+                    Z=float(s[9]) + entropy, mu=float(s[3]), tau=float(s[4]), alpha=float(s[5]))
 
     def get_moments(self, node):
         if node is self.Y:
@@ -193,36 +174,6 @@ class MaskedDiagGaussianMixturePlan(DiagGaussianMixturePlan):
             return [y, y * y]
         return super().get_moments(node)
 
-    def _host_mask(self):
-        return np.asarray(self.Y._mask, dtype=bool).reshape(self.N, self.D)
-
-    def get_mask(self, node):
-        """``Y``: its mask; ``Z``: any entry of the row observed, (N, 1); ``mu`` and ``tau``: any
-        entry of the column observed, (D, 1); ``alpha``: any entry observed -- the masks the
-        reference propagates from ``Y`` to its parents."""
-        m = self._host_mask()
-        if node is self.Y:
-            return m.copy()
-        if node is self.Z:
-            return m.any(axis=1)[:, None]
-        if node is self.mu or node is self.tau:
-            return m.any(axis=0)[:, None]
-        return np.array(bool(m.any()))
-
     # -- persistence -----------------------------------------------------------------------------------
     def _saved(self):
         return self._SAVED + ('M', 'g')
-
-    def _save_more(self, put, base):
-        put(base + 'mask', self.maskd.cpu().numpy())
-
-    def _check_more(self, reader, base):
-        saved = np.asarray(reader.get(base + 'mask'), dtype=np.uint8).reshape(-1) \
-            if reader.has(base + 'mask') else None
-        mine = self.maskd.cpu().numpy().reshape(-1)
-        if saved is None or not np.array_equal(saved != 0, mine != 0):
-            raise ValueError('checkpoint was saved with %s, the model has %s: observe Y with the '
-                             'mask of the checkpoint before loading it'
-                             % tuple('no mask on Y' if m is None else
-                                     'a mask on Y with %d of %d entries observed'
-                                     % (int(np.count_nonzero(m)), m.size) for m in (saved, mine)))

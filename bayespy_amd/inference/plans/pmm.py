@@ -39,17 +39,14 @@ import numpy as np
 
 from . import _delta
 from ._dirichlet import DirichletKernels, prior_table
-from .bmm import _mask_shape, _takes_mask
+from ._mixture import (MixtureSpec, PlateMixturePlan, _p, _takes_mask, cluster_plate_reason,
+                       full_mask_reason, match_plate_mixture, observed_tensor)
 
 from ... import _lib
-from ...device import get_runtime, ptr
-from ...nodes.node import Constant, DeviceMask
-from ...nodes.dirichlet import Dirichlet
-from ...nodes.categorical import Categorical
+from ...nodes.node import DeviceMask
 from ...nodes.categorical_markov_chain import CategoricalMarkovChainToCategorical
 from ...nodes.gamma import Gamma
 from ...nodes.poisson import Poisson
-from ...nodes.mixture import Mixture
 
 _DTYPES = {'float64': 0, 'int64': 1, 'uint8': 2, 'int32': 3}
 _LIMITS = []
@@ -66,10 +63,6 @@ def pmm_limits():
 
 def _limits_text():
     return 'K <= %d, D <= %d and counts of at most %d' % pmm_limits()
-
-
-def _p(t):
-    return ptr(t) if t is not None else None
 
 
 class PMMKernels(DirichletKernels):
@@ -123,86 +116,43 @@ def _largest_host_count(X):
     return a.max() if a.size else None
 
 
-def _match(nodes, why):
-    for X in nodes:
-        if not isinstance(X, Mixture) or X.node_class is not Poisson:
-            continue
-        if isinstance(X.parents[0], CategoricalMarkovChainToCategorical):
-            continue            # a hidden Markov model: no block of this family
-
-        def no(msg, X=X):
-            if why is not None:
-                why.append('fused Poisson-mixture block, observed node %s: %s'
-                           % (X.name or '<unnamed>', msg))
-        if len(X.parents) != 2:
-            no('its parents are not (Categorical(Dirichlet), Gamma)')
-            continue
-        Z, lam = X.parents
-        if type(Z) is not Categorical or type(lam) is not Gamma \
-                or type(Z.parents[0]) is not Dirichlet:
-            no('its parents are not (Categorical(Dirichlet), Gamma)')
-            continue
-        R = Z.parents[0]
-        four = (X, Z, lam, R)
-        if not all(any(n is m for m in nodes) for n in four):
-            continue
-        if any(any(m != 1 for m in n.plates_multiplier) for n in four):
-            no('plates_multiplier (mini-batches) goes through the generic engine')
-            continue
-        if any(getattr(n, '_shard_axis', None) is not None for n in four):
-            no('a plate is sharded over ranks')
-            continue
-        if not _takes_mask(X):
-            no('it has a mask of shape %s: the block takes no mask or a mask of the full shape of '
-               'the plates of X, here %s; a scalar mask or one that broadcasts over a plate goes '
-               'through the generic engine' % (_mask_shape(X._mask), tuple(X.plates)))
-            continue
-        bad = [(n, p) for n in (lam, R) for p in n.parents if not isinstance(p, Constant)]
-        if bad:
-            no('a parameter of %s is a node (%s), not a constant'
-               % (bad[0][0].name, type(bad[0][1]).__name__))
-            continue
-        if X.cluster_plate != -1:
-            no('cluster_plate is %d, the block needs the clusters on the last plate axis (-1)'
-               % X.cluster_plate)
-            continue
-        if len(X.plates) != 2 or len(lam.plates) != 2:
-            no('it needs plates (N, D), X has plates %s and lam has plates %s'
-               % (X.plates, lam.plates))
-            continue
-        N, D = X.plates
-        K = X.clusters
-        if Z.plates != (N, 1) or lam.plates != (D, K) or any(p != 1 for p in R.plates):
-            no('plates of Z / lam / R are %s / %s / %s, not (N, 1) / (D, K) / ()'
-               % (Z.plates, lam.plates, R.plates))
-            continue
-        max_k, max_d, max_count = pmm_limits()
-        if K > max_k or D > max_d:
-            no('D = %d, K = %d exceed the limits of the block (%s)' % (D, K, _limits_text()))
-            continue
-        big = _largest_host_count(X)
-        if big is not None and big > max_count:
-            no('a count of %d exceeds the limits of the block (%s)' % (big, _limits_text()))
-            continue
-        kids = ((R, [Z]), (Z, [X]), (lam, [X]), (X, []))
-        if any([c for c, _ in n.children] != want for n, want in kids):
-            no('one of its roles has other children as well')
-            continue
-        if Z.observed or lam.observed or R.observed:
-            no('Z, lam or R is observed')
-            continue
-        inits = ((Z, 'Z', ('value',)), (lam, 'lam', ('value', 'parameters')),
-                 (R, 'R', ('parameters',)))
-        bad = [(nm, n._init[0]) for n, nm, ok in inits
-               if n._init is not None and n._init[0] not in ok]
-        if bad:
-            no('%s is initialised by %s' % bad[0])
-            continue
-        return dict(X=X, Z=Z, lam=lam, R=R)
-    return None
+def _plates_reason(X, lam):
+    if len(X.plates) != 2 or len(lam.plates) != 2:
+        return ('it needs plates (N, D), X has plates %s and lam has plates %s'
+                % (X.plates, lam.plates))
 
 
-class PoissonMixturePlan:
+def _limits_reason(r):
+    X = r['X']
+    D, K = X.plates[1], X.clusters
+    max_k, max_d, max_count = pmm_limits()
+    if K > max_k or D > max_d:
+        return 'D = %d, K = %d exceed the limits of the block (%s)' % (D, K, _limits_text())
+    big = _largest_host_count(X)
+    if big is not None and big > max_count:
+        return 'a count of %d exceeds the limits of the block (%s)' % (big, _limits_text())
+
+
+_SPEC = MixtureSpec(
+    label='fused Poisson-mixture block',
+    # a hidden Markov model: no block of this family
+    takes=lambda X: X.node_class is Poisson
+    and not isinstance(X.parents[0], CategoricalMarkovChainToCategorical),
+    observed='X', weights='R', params=(('lam', Gamma, ('value', 'parameters')),),
+    parents='its parents are not (Categorical(Dirichlet), Gamma)',
+    constant='a parameter of %s is a node (%s), not a constant',
+    role_plates='plates of Z / lam / R are {} / {} / {}, not (N, 1) / (D, K) / ()',
+    mask=full_mask_reason,
+    plates=lambda X, lam: cluster_plate_reason(X) or _plates_reason(X, lam),
+    limits=_limits_reason)
+
+
+class PoissonMixturePlan(PlateMixturePlan):
+
+    KERNELS = PMMKernels
+    LABEL, KIND = _SPEC.label, 'pmm'
+    TERMS = ('X', 'Z', 'lam', 'R')
+    _FLAGS = ('_used',)
 
     @staticmethod
     def describe():
@@ -213,96 +163,23 @@ class PoissonMixturePlan:
 
     @staticmethod
     def match(nodes, why=None):
-        return _match(nodes, why)
+        return match_plate_mixture(nodes, why, _SPEC)
 
     def __init__(self, roles, runtime=None, kernels=None):
-        self.roles = roles
-        self.X, self.Z, self.lam, self.R = roles['X'], roles['Z'], roles['lam'], roles['R']
-        self.N, self.D = self.X.plates
-        self.K = self.X.clusters
-        self._rt, self._kernels = runtime, kernels
-        self._ready = False
-        self._x_stale = False
-        self.maskd = None           # (N, D) uint8 in HBM when X has a mask
+        super().__init__(roles, runtime=runtime, kernels=kernels)
         self.hidden = 0             # the form of the pass: 1 when the pack met a hidden entry
-        self._version = 0
-        self._L_version = -1
-        self._L = None
-        for nd in roles.values():
-            nd._plan = self
 
-    @property
-    def rt(self):
-        if self._rt is None:
-            self._rt = get_runtime()
-        return self._rt
-
-    @property
-    def kernels(self):
-        if self._kernels is None:
-            self._kernels = PMMKernels(self.rt)
-        return self._kernels
-
-    def nodes(self):
-        return list(self.roles.values())
-
-    def has_state(self):
-        return bool(self._ready)
-
-    def invalidate(self, node):
-        if node is self.X and node.observed and _takes_mask(node):
-            # new observations of the same shape, with any mask of the full shape or none: the
-            # counts are packed again, the posteriors stay
-            self._x_stale = True
-            self._version += 1
-            return
-        _delta.warn_state_discarded(self, node)
-        self._ready = False
-        self._version += 1
-        if PoissonMixturePlan.match(self.nodes()) is None:
-            from .generic import GenericPlan
-            GenericPlan(self.nodes())
+    def _repacks(self, node):
+        """With any mask of the full shape or none."""
+        return _takes_mask(node)
 
     # -- set-up ------------------------------------------------------------------------------------
-    def _up(self, a):
-        torch = self.rt.torch
-        return torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(self.rt.device)
-
-    def _upload_mask(self):
-        rt, torch = self.rt, self.rt.torch
-        m = self.X._mask
-        if m is True:
-            self.maskd = None
-        elif isinstance(m, DeviceMask):
-            self.maskd = m.tensor.to(rt.device).reshape(self.N, self.D).to(torch.uint8).contiguous()
-        else:
-            self.maskd = torch.from_numpy(np.ascontiguousarray(
-                np.asarray(m, dtype=bool).reshape(self.N, self.D).astype(np.uint8))).to(rt.device)
-
     def _pack(self):
         """``X._data`` as 16 bits per entry; an observed value that is negative or no integer is
         the reference's ValueError (poisson.py), one above the cap NotImplementedError."""
         rt, torch = self.rt, self.rt.torch
         N, D = self.N, self.D
-        x = self.X._data
-        if x is None:
-            raise ValueError('Node %s has not been observed' % self.X.name)
-        if isinstance(x, torch.Tensor):
-            t = x.to(rt.device)
-            if t.dtype == torch.bool:
-                t = t.to(torch.uint8)
-            if str(t.dtype).replace('torch.', '') not in _DTYPES:
-                t = t.to(torch.float64)
-        else:
-            a = np.asarray(x)
-            if a.dtype == bool:
-                a = a.astype(np.uint8)
-            if a.dtype.name not in _DTYPES:
-                a = a.astype(np.float64)
-            t = torch.from_numpy(np.array(np.broadcast_to(a, (N, D)), order='C')).to(rt.device)
-        if tuple(t.shape) != (N, D) or not t.is_contiguous():
-            t = t.expand(N, D).contiguous()
-        dtype = _DTYPES[str(t.dtype).replace('torch.', '')]
+        t, dtype = observed_tensor(rt, self.X, N, D, _DTYPES)
         self.xp = torch.zeros(max(N * D, 4), dtype=torch.int16, device=rt.device)
         flags = torch.zeros(3, dtype=torch.int32, device=rt.device)
         counts = torch.zeros(2, dtype=torch.int64, device=rt.device)
@@ -316,7 +193,7 @@ class PoissonMixturePlan:
                                       % (pmm_limits()[2], _limits_text()))
         n = counts.cpu().numpy()
         self.n_observed, self.n_hidden = int(n[0]), int(n[1])
-        self._x_stale = False
+        self._stale = False
 
     def _set_form(self):
         """The form of the pass for the packed data; when it changes, the tables of the last ``Z``
@@ -334,7 +211,7 @@ class PoissonMixturePlan:
 
     def _materialize(self):
         if self._ready:
-            if self._x_stale:
+            if self._stale:
                 self._upload_mask()
                 self._pack()
                 self._set_form()
@@ -342,7 +219,6 @@ class PoissonMixturePlan:
             return
         self._delta = _delta.delta_roles(self.roles)
         rt, k = self.rt, self.kernels
-        torch = rt.torch
         N, D, K = self.N, self.D, self.K
         rt.sync_stream()
         self._upload_mask()
@@ -369,29 +245,8 @@ class PoissonMixturePlan:
         k.update(D, K, 0, self.a0, self.b0, None, None, self.lam_par, self.lam_mom,
                  self.scal[3:4])
         self._init_lam(a0, b0)
-        counts = None
-        init = self.R._init
-        if init is not None:
-            a = np.asarray(init[1][0], dtype=np.float64)
-            if np.any(a <= 0):
-                raise ValueError("Natural parameters should be positive")
-            counts = self._up(np.broadcast_to(a, (K,)) - pr)
-        k.dirichlet(1, K, K, 1, self.prior_r, counts, self.alpha_r, self.elog_r, self.ws_small,
-                    self.scal[4:5])
-        # Z: fixed labels, or its moments under the prior (no observation term)
-        self.labels = None
-        init = self.Z._init
-        if init is not None:
-            lab = np.asarray(init[1])
-            if lab.dtype.kind == 'f':
-                if np.any(lab != np.round(lab)):
-                    raise ValueError("Values must be integers")
-            elif lab.dtype.kind not in 'iub':
-                raise ValueError("Values must be integers")
-            lab = np.array(np.broadcast_to(lab, (N, 1)), dtype=np.int64).reshape(N)
-            if lab.size and (lab.min() < 0 or lab.max() >= K):
-                raise ValueError("Invalid category index")
-            self.labels = torch.from_numpy(lab.astype(np.int32)).to(rt.device)
+        self._weights_step(4, self._weights_init_counts(pr))
+        self._labels_from_init()
         self.elog_r_used.copy_(self.elog_r)
         self._tables(None, self.elog_r_used)
         self._ready = True
@@ -453,53 +308,26 @@ class PoissonMixturePlan:
                      self.M if self.hidden else self.Nk, self.lam_par, self.lam_mom,
                      self.scal[3:4])
         elif node is self.R:
-            k.dirichlet(1, K, K, 1, self.prior_r, self.Nk, self.alpha_r, self.elog_r,
-                        self.ws_small, self.scal[4:5])
+            self._weights_step(4, self.Nk)
         else:
             return
         self._version += 1
 
-    def _lower_bound_terms(self):
-        self._materialize()
-        if self._L_version != self._version:
-            rt, k = self.rt, self.kernels
-            rt.sync_stream()
-            D, K = self.D, self.K
-            k.tables(D, K, self.hidden, self.lam_mom, self.elog_r, self.l_now, self.lb_now,
-                     self.c_now, self.lsum)
-            k.dot(D * K, self.S, self.l_now, self.ws_small, self.scal[5:6])
-            if self.hidden:
-                k.dot(D * K, self.M, self.lb_now, self.ws_small, self.scal[6:7])
-            else:
-                k.dot(K, self.Nk, self.lsum, self.ws_small, self.scal[6:7])
-            k.dot(K, self.Nk, self.elog_r, self.ws_small, self.scal[7:8])
-            s = self.scal.cpu().numpy()
-            lgam = float(self.lgam.cpu().numpy()[0])
-            entropy = 0.0 if self.labels is not None else float(s[0] - s[1] - s[2])
-            t = dict(X=float(s[5] - s[6]) - lgam, Z=float(s[7]) + entropy, lam=float(s[3]),
-                     R=float(s[4]))
-            t['total'] = t['X'] + t['Z'] + t['lam'] + t['R']
-            self._L = t
-            self._L_version = self._version
-        return _delta.bound_terms(self._L, self._delta)
-
-    def lower_bound_contribution(self, node):
-        terms = self._lower_bound_terms()
-        for key in ('X', 'Z', 'lam', 'R'):
-            if node is self.roles[key]:
-                return terms[key]
-        return 0.0
-
-    def responsibilities(self):
-        """(N, K) responsibilities of ``Z`` as a device array: formed by the pass in its write mode
-        from the tables of the last ``Z`` update; not kept."""
-        self._materialize()
-        rt = self.rt
-        rt.sync_stream()
-        r = rt.empty(self.N, self.K)
-        if self.N:
-            self._run_pass(r)
-        return r
+    def _bound_terms(self):
+        k = self.kernels
+        D, K = self.D, self.K
+        k.tables(D, K, self.hidden, self.lam_mom, self.elog_r, self.l_now, self.lb_now,
+                 self.c_now, self.lsum)
+        k.dot(D * K, self.S, self.l_now, self.ws_small, self.scal[5:6])
+        if self.hidden:
+            k.dot(D * K, self.M, self.lb_now, self.ws_small, self.scal[6:7])
+        else:
+            k.dot(K, self.Nk, self.lsum, self.ws_small, self.scal[6:7])
+        k.dot(K, self.Nk, self.elog_r, self.ws_small, self.scal[7:8])
+        s, entropy = self._host_scal()
+        lgam = float(self.lgam.cpu().numpy()[0])
+        return dict(X=float(s[5] - s[6]) - lgam, Z=float(s[7]) + entropy, lam=float(s[3]),
+                    R=float(s[4]))
 
     def get_moments(self, node):
         self._materialize()
@@ -516,76 +344,6 @@ class PoissonMixturePlan:
             return [np.where(xp == 0xFFFF, 0, xp).astype(np.float64)]
         raise NotImplementedError
 
-    def _host_mask(self):
-        """The mask as a boolean host array of shape (N, D), or None without one."""
-        m = self.X._mask
-        return None if m is True else np.asarray(m, dtype=bool).reshape(self.N, self.D)
-
-    def get_mask(self, node):
-        """``X``: its mask; ``Z``: any entry of the row observed, (N, 1); ``lam``: any entry of the
-        column observed, (D, 1); ``R``: any entry observed -- the masks the reference propagates
-        from ``X`` to its parents."""
-        m = self._host_mask()
-        if m is None:
-            return np.array(True)
-        if node is self.X:
-            return m.copy()
-        if node is self.Z:
-            return m.any(axis=1)[:, None]
-        if node is self.lam:
-            return m.any(axis=0)[:, None]
-        return np.array(bool(m.any()))
-
     # -- persistence -----------------------------------------------------------------------------------
     _SAVED = ('lam_par', 'lam_mom', 'lam_mom_used', 'alpha_r', 'elog_r', 'elog_r_used', 'l', 'lb',
               'c', 'S', 'M', 'Nk', 'scal')
-
-    def save_state(self, put, nodes, index):
-        self._materialize()
-        base = 'plans/%d/' % index
-        _delta.save(put, base, self._delta)
-        put(base + 'kind', np.array([ord(ch) for ch in 'pmm'], dtype=np.uint8))
-        put(base + 'dims', np.array([self.N, self.D, self.K], dtype=np.int64))
-        put(base + 'flags', np.array([1 if self.labels is not None else 0,
-                                      1 if self._used else 0], dtype=np.int64))
-        if self.labels is not None:
-            put(base + 'labels', self.labels.cpu().numpy())
-        if self.maskd is not None:
-            put(base + 'mask', self.maskd.cpu().numpy())
-        for name in self._SAVED:
-            put(base + name, getattr(self, name).cpu().numpy())
-
-    def load_state(self, reader, nodes, index):
-        self._materialize()
-        base = 'plans/%d/' % index
-        if not reader.has(base + 'kind') or bytes(np.asarray(reader.get(base + 'kind'),
-                                                             dtype=np.uint8)) != b'pmm':
-            raise Exception("File does not contain the state of the fused Poisson-mixture block")
-        dims = tuple(int(v) for v in reader.get(base + 'dims'))
-        if dims != (self.N, self.D, self.K):
-            raise ValueError('checkpoint is for (N, D, K) = %s, the model has %s'
-                             % (dims, (self.N, self.D, self.K)))
-        saved = np.asarray(reader.get(base + 'mask'), dtype=np.uint8).reshape(-1) \
-            if reader.has(base + 'mask') else None
-        mine = None if self.maskd is None else self.maskd.cpu().numpy().reshape(-1)
-        if (saved is None) != (mine is None) or (saved is not None
-                                                 and not np.array_equal(saved != 0, mine != 0)):
-            raise ValueError('checkpoint was saved with %s, the model has %s: observe X with the '
-                             'mask of the checkpoint before loading it'
-                             % tuple('no mask on X' if m is None else
-                                     'a mask on X with %d of %d entries observed'
-                                     % (int(np.count_nonzero(m)), m.size) for m in (saved, mine)))
-        torch = self.rt.torch
-        self._delta = _delta.load(reader, base)
-        flags = np.asarray(reader.get(base + 'flags')).ravel()
-        if int(flags[0]):
-            self.labels = torch.from_numpy(
-                np.array(reader.get(base + 'labels'), dtype=np.int32)).to(self.rt.device)
-        else:
-            self.labels = None
-        self._used = bool(int(flags[1]))
-        for name in self._SAVED:
-            getattr(self, name).copy_(torch.from_numpy(
-                np.array(reader.get(base + name), dtype=np.float64)).reshape(
-                    getattr(self, name).shape).to(self.rt.device))
-        self._version += 1
