@@ -55,6 +55,11 @@ struct vmp_ctx {
     // tail kernel keeps -- and the sweeps enqueued so far
     double *sweep_ctl;
     int64_t sweeps_enqueued;
+    // ... and the ticket words of the one-launch sweeps (pca_sweep_mid_kernel): one 32-bit word per
+    // sweep of a chunk, cleared ahead of the chunk's first launch, never reused within a chunk;
+    // launches of that kernel so far
+    unsigned int *sweep_tickets;
+    int64_t sweep_mid_launches;
     // streams / events of the pipelined plate pass of the missing-data PCA block (vmp_mpca.hip)
     hipStream_t ms[3];
     hipEvent_t me[VMP_NME];
@@ -102,6 +107,14 @@ int32_t vmp_pca_launch_sweep_head(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_
 int32_t vmp_pca_launch_sweep_tail(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                                   double a0t, double b0t, double a0a, double b0a, double *state,
                                   const vmp_sweep_tail &t);
+
+// sweeps 1 .. n-1 of a chunk: Gram statistics, tail and the next sweep's head in ONE launch of DP / 8
+// workgroups (pca_sweep_mid_kernel, vmp_pca_small.hip); `ticket` is the sweep's own zeroed word
+int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                                 double a0t, double b0t, double a0a, double b0a, double *state,
+                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket);
+// the Gram statistics of that kernel alone: Syx rows into the state, DP / 8 partial blocks into P
+int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P);
 
 // forms the pending S = [G A^T; A G A^T] of the Gram-form PCA block, if any (vmp_pca.hip)
 int32_t vmp_pca_ensure_gram(vmp_ctx *ctx);

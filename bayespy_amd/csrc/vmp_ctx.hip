@@ -97,6 +97,8 @@ int32_t vmp_ctx_create(int32_t device, void *stream, vmp_ctx **out)
     ctx->x_launched = ctx->x_superseded = 0;
     ctx->sweep_ctl = nullptr;
     ctx->sweeps_enqueued = 0;
+    ctx->sweep_tickets = nullptr;
+    ctx->sweep_mid_launches = 0;
     for (int i = 0; i < 3; ++i) ctx->ms[i] = nullptr;
     for (int i = 0; i < VMP_NME; ++i) ctx->me[i] = nullptr;
     ctx->comm = nullptr;
@@ -131,6 +133,7 @@ int32_t vmp_ctx_destroy(vmp_ctx *ctx)
     for (int i = 0; i < VMP_NME; ++i)
         if (ctx->me[i]) (void)hipEventDestroy(ctx->me[i]);
     if (ctx->sweep_ctl) (void)hipFree(ctx->sweep_ctl);       // (waits for the device itself)
+    if (ctx->sweep_tickets) (void)hipFree(ctx->sweep_tickets);
     if (ctx->ev_xfork) (void)hipEventDestroy(ctx->ev_xfork);
     if (ctx->ev_xdone) (void)hipEventDestroy(ctx->ev_xdone);
     for (int i = 0; i < 2; ++i)

@@ -1336,13 +1336,32 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
     t.tol = tol;
     t.norder = norder;
     for (int i = 0; i < 8; ++i) t.order[i] = i < norder ? order[i] : -1;
+    // Sweeps 1 .. n-1 are ONE launch each (pca_sweep_mid_kernel: Gram statistics on DP / 8 workgroups,
+    // then tail and the next sweep's head in the workgroup that draws the last ticket), so a chunk is
+    // head, n-1 mid launches, and for the last sweep -- which runs beside the pass, where a workgroup
+    // with the mid kernel's LDS would not be placed -- the pass, the Gram statistics and the tail:
+    // n + 2 launches instead of 3 n.  "pca_sweep_ticket" = 0 (VMP_PCA_SWEEP_TICKET=0): three per sweep;
+    // so does a state block that is not 16-byte aligned (the mid kernel loads it 16 bytes at a time).
+    const bool ticket = n > 1 && ((uintptr_t)state % 16) == 0 &&
+                        vmp_tune_get("pca_sweep_ticket", env_int("VMP_PCA_SWEEP_TICKET", 1, 0, 1));
+    if (ticket) {
+        if (!ctx->sweep_tickets)
+            VMP_HIP_CHECK(ctx, hipMalloc(&ctx->sweep_tickets,
+                                         VMP_PCA_MAX_SWEEPS * sizeof(unsigned int)));
+        VMP_HIP_CHECK(ctx, hipMemsetAsync(ctx->sweep_tickets, 0, (size_t)(n - 1) * sizeof(unsigned int),
+                                          ctx->stream));
+    }
     for (int i = 0; i < n; ++i) {
         // the first sweep of the batch reads no stop word: whatever an earlier batch left is stale
         const double *stop = i == 0 ? nullptr : ctx->sweep_ctl;
-        rc = vmp_pca_launch_sweep_head(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
-                                       b0_alpha, state, stop);
-        if (rc != VMP_OK) return rc;
-        if (i + 1 == n) {
+        const bool last = i + 1 == n;
+        // the head of this sweep: its own launch, unless the mid launch of sweep i - 1 has run it
+        if (!ticket || i == 0) {
+            rc = vmp_pca_launch_sweep_head(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
+                                           b0_alpha, state, stop);
+            if (rc != VMP_OK) return rc;
+        }
+        if (last) {
             // the one pass of the batch that anything can read: from the A of the last EXECUTED
             // sweep (after a stop the head kernels have left the state alone)
             rc = issue_xpass(ctx, Y, ldy, N, D, K, X, ldx, state, workspace, lay);
@@ -1350,13 +1369,21 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
         } else {
             ctx->x_superseded += 1;      // never described, copied for or forked
         }
-        rc = run_gram_stats(ctx, L, D, K, state, P, ctx->stream, stop, false);
-        if (rc != VMP_OK) return rc;
         t.slot = ring + (int64_t)i * VMP_PCA_SWEEP_SLOT;
         t.first = i == 0;
-        rc = vmp_pca_launch_sweep_tail(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha, b0_alpha,
-                                       state, t);
-        if (rc != VMP_OK) return rc;
+        if (ticket && !last) {
+            // Gram statistics, tail and the head of sweep i + 1 in one launch
+            rc = vmp_pca_launch_sweep_mid(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
+                                          b0_alpha, state, P, t, ctx->sweep_tickets + i);
+            if (rc != VMP_OK) return rc;
+            ctx->sweep_mid_launches += 1;
+        } else {
+            rc = run_gram_stats(ctx, L, D, K, state, P, ctx->stream, stop, false);
+            if (rc != VMP_OK) return rc;
+            rc = vmp_pca_launch_sweep_tail(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
+                                           b0_alpha, state, t);
+            if (rc != VMP_OK) return rc;
+        }
         ctx->sweeps_enqueued += 1;
     }
     return VMP_OK;
@@ -1374,6 +1401,25 @@ int32_t vmp_pca_sweep_counts(vmp_ctx *ctx, int64_t *enqueued, int64_t *executed,
     if (executed) *executed = (int64_t)c[VMP_SWEEP_EXECUTED];
     if (skipped) *skipped = (int64_t)c[VMP_SWEEP_SKIPPED];
     return VMP_OK;
+}
+
+int32_t vmp_pca_sweep_mid_count(vmp_ctx *ctx, int64_t *launches)
+{
+    VMP_REQUIRE(ctx, ctx && launches, VMP_ERR_INVALID, "null argument");
+    *launches = ctx->sweep_mid_launches;
+    return VMP_OK;
+}
+
+int32_t vmp_pca_gram_stats_form(vmp_ctx *ctx, int32_t D, int32_t K, double *state, void *workspace,
+                                int32_t form)
+{
+    VMP_REQUIRE(ctx, ctx && state && workspace, VMP_ERR_INVALID, "null argument");
+    vmp_pca_layout L;
+    const int32_t rc = vmp_pca_get_layout(D, K, &L);
+    VMP_REQUIRE(ctx, rc == VMP_OK, rc, "unsupported dims D=%d K=%d", D, K);
+    double *P = reinterpret_cast<double *>(workspace);
+    if (form == 0) return run_gram_stats(ctx, L, D, K, state, P, ctx->stream, nullptr, false);
+    return vmp_pca_launch_gram_fast(ctx, D, K, state, P);
 }
 
 int32_t vmp_pca_last_pass_ms(vmp_ctx *ctx, double *ms_pass, double *ms_reduce)

@@ -521,25 +521,29 @@ __device__ __forceinline__ v4f64 wave_tile_mma_acc(v4f64 acc, const double *As, 
 // back from global memory for the last product instead of waiting in registers, the inverses are
 // inlined (no call, no scratch) and the file is compiled with the VGPR form of the MFMAs (Makefile):
 // 25.6 KB, 96 VGPRs, no AGPRs, no scratch.
-template <int KP>
-__global__ void __launch_bounds__(NTF, 4)
-pca_head_fast_kernel(small_args a, double *st, const double *stop)
+//
+// The body is shared with pca_sweep_mid_kernel below, where the tail of the previous sweep has just
+// run in the same workgroup: HANDOFF = what that tail holds in LDS -- Cov_X in M, sum <x><x>^T in T,
+// <alpha> in alm and <tau> in tau_in, the very values it stored to the state -- is not loaded again.
+template <int KP, bool HANDOFF>
+__device__ __forceinline__ void pca_head_body(const small_args &a, double *st, double *Mh, double *Th,
+                                              double *almh, double tau_in)
 {
-    // batched sweeps (vmp_pca_sweeps): an earlier sweep of the batch has stopped the loop
-    if (stop && stop[VMP_SWEEP_STOP] != 0.0) return;
     constexpr int LDM = KP + 1, E = KP * KP / NTF, RB = 32;
+    constexpr int OWN = HANDOFF ? 1 : KP * LDM;
+    __shared__ double Mo[OWN];              // Lambda_W -> Cov_W -> Lambda_X -> Cov_X
+    __shared__ double To[OWN];              // sum <x x^T> (shard sum) -> Sww
+    __shared__ double SWb[RB * LDM];        // one row block: Syx rows -> <W> rows
+    __shared__ double almo[HANDOFF ? 1 : KP];
+    __shared__ double logdet;
+    __shared__ int bad;
+    double *M = HANDOFF ? Mh : Mo, *T = HANDOFF ? Th : To, *alm = HANDOFF ? almh : almo;
     constexpr int KT = KP / 16;
     constexpr int NB = FAST_D / RB;               // row blocks
     constexpr int NLB = RB * KP / NTF;            // loads per thread and row block
     constexpr int TPB = 2 * KT;                   // 16 x 16 tiles of a row block
     constexpr int WT = (TPB + 3) / 4;             // ... per wavefront
     constexpr int ST = (KT * KT + 3) / 4;         // tiles of Sww per wavefront
-    __shared__ double M[KP * LDM];          // Lambda_W -> Cov_W -> Lambda_X -> Cov_X
-    __shared__ double T[KP * LDM];          // sum <x x^T> (shard sum) -> Sww
-    __shared__ double SWb[RB * LDM];        // one row block: Syx rows -> <W> rows
-    __shared__ double alm[KP];
-    __shared__ double logdet;
-    __shared__ int bad;
     const lay32 L(a.L);
     int tid = threadIdx.x;
     const int D = a.D, K = a.K;
@@ -548,8 +552,8 @@ pca_head_fast_kernel(small_args a, double *st, const double *stop)
     __builtin_amdgcn_s_setprio(3);   // latency-critical: win issue arbitration on a shared CU
     if (tid == 0) bad = 0;
     // ---- one batch of loads ------------------------------------------------------------
-    const double tau = st[L.off_tau + 2];
-    {
+    const double tau = HANDOFF ? tau_in : st[L.off_tau + 2];
+    if constexpr (!HANDOFF) {
         double cx[E], sx[E];
 #pragma unroll
         for (int m = 0; m < E; ++m) {
@@ -739,6 +743,15 @@ pca_head_fast_kernel(small_args a, double *st, const double *stop)
     }
 }
 
+template <int KP>
+__global__ void __launch_bounds__(NTF, 5)       // 5 waves per SIMD: holds the allocator to 96 VGPRs
+pca_head_fast_kernel(small_args a, double *st, const double *stop)
+{
+    // batched sweeps (vmp_pca_sweeps): an earlier sweep of the batch has stopped the loop
+    if (stop && stop[VMP_SWEEP_STOP] != 0.0) return;
+    pca_head_body<KP, false>(a, st, nullptr, nullptr, nullptr, 0.0);
+}
+
 // (tau.update(), alpha.update(), lower bound)
 // GRAM: the messages to W of the Gram form, S = [G A^T ; A G A^T] (sum y <x>^T and
 // sum <x><x>^T collapsed onto the constant Gram matrix), are formed HERE first -- G streamed through
@@ -752,18 +765,27 @@ pca_head_fast_kernel(small_args a, double *st, const double *stop)
 // rule (vmp_stop_rule.h) and leaves the stop word and the bound for the next sweep.
 constexpr int GB = 32;            // rows of G per batch
 constexpr int TAIL_PLAIN = 0, TAIL_GRAM = 1, TAIL_SWEEP = 2;
+// LDS of the tail (a struct: pca_sweep_mid_kernel hands Cx, Sx, al and sc on to the next head)
+template <int KP>
+struct alignas(16) tail_lds {
+    double Sw[KP * (KP + 1)];       // Sww
+    double Cx[KP * (KP + 1)];       // Cov_X
+    double Sx[KP * (KP + 1)];       // sum <x><x>^T (shard sum)
+    double al[4 * KP];              // alpha: a, b, <alpha>, <log alpha>
+    double sc[8];                   // tau a, b, mean, logmean ; Syy ; log|LW| ; log|LX|
+    double red[NTF / 64 + 1];
+    double stop;                    // SWEEP: the stop word this tail left, for its own workgroup
+};
+// (a multiple of 16 bytes: the dynamic LDS behind it is accessed 16 bytes at a time)
+static_assert(sizeof(tail_lds<16>) % 16 == 0 && sizeof(tail_lds<32>) % 16 == 0, "tail_lds size");
 template <int KP, int MODE>
-__device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, const vmp_sweep_tail *sw)
+__device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, const vmp_sweep_tail *sw,
+                                              tail_lds<KP> &s)
 {
     constexpr bool GRAM = (MODE == TAIL_GRAM);
     constexpr int LDM = KP + 1, E = KP * KP / NTF;
-    extern __shared__ double gl[];          // GRAM: A (KP x (DP+1)) | G batch (GB x (DP+1)) | S batch (GB x LDM)
-    __shared__ double Sw[KP * LDM];         // Sww
-    __shared__ double Cx[KP * LDM];         // Cov_X
-    __shared__ double Sx[KP * LDM];         // sum <x><x>^T (shard sum)
-    __shared__ double al[4 * KP];           // alpha: a, b, <alpha>, <log alpha>
-    __shared__ double sc[8];                // tau a, b, mean, logmean ; Syy ; log|LW| ; log|LX|
-    __shared__ double red[NTF / 64 + 1];
+    extern __shared__ __align__(16) double gl[];          // GRAM: A (KP x (DP+1)) | G batch (GB x (DP+1)) | S batch (GB x LDM)
+    double *Sw = s.Sw, *Cx = s.Cx, *Sx = s.Sx, *al = s.al, *sc = s.sc, *red = s.red;
     const lay32 L(a.L);
     const int tid = threadIdx.x, D = a.D, K = a.K;
     if constexpr (MODE == TAIL_SWEEP) {
@@ -926,7 +948,12 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
         // the status word as the host would read it after this kernel
         if constexpr (MODE == TAIL_SWEEP)
             sc[7] = !(tb > 0.0) ? (double)VMP_ERR_FLOATING : st[L.off_scal + 3];
+        // tau's term of the bound, here and not after the barrier: this wavefront has nothing else
+        // to do while wavefront 0 works on alpha
+        red[NTF / 64] = gamma_elbo(a.a0t, a.b0t, ta, tb, sc[2], sc[3]);
     }
+    // ---- lower bound (expfamily.py:400-480): the Gamma terms beside their updates ----------
+    double sla = 0.0, saw = 0.0, lal = 0.0;
     if (tid < K) {
         const double aa = a.a0a + 0.5 * (double)D;
         const double ab = a.b0a + 0.5 * Sw[tid * LDM + tid];
@@ -939,23 +966,10 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
         st[L.off_alpha + 1 * KP + tid] = ab;
         st[L.off_alpha + 2 * KP + tid] = am;
         st[L.off_alpha + 3 * KP + tid] = alg;
-    }
-    __syncthreads();
-    // ---- lower bound (expfamily.py:400-480) ----------------------------------------------
-    double sla = 0.0, saw = 0.0, lal = 0.0;
-    if (tid <= K) {
-        const bool is_tau = (tid == K);
-        const double *p = is_tau ? sc : al + tid;
-        const int sp = is_tau ? 1 : KP;
-        const double g = gamma_elbo(is_tau ? a.a0t : a.a0a, is_tau ? a.b0t : a.b0a, p[0], p[sp],
-                                    p[2 * sp], p[3 * sp]);
-        if (is_tau) {
-            red[NTF / 64] = g;
-        } else {
-            sla = p[3 * sp];
-            saw = p[2 * sp] * Sw[tid * LDM + tid];
-            lal = g;
-        }
+        // alpha's terms do not need tau: they run while wavefront 1 is still on tau's digamma
+        sla = alg;
+        saw = am * Sw[tid * LDM + tid];
+        lal = gamma_elbo(a.a0a, a.b0a, aa, ab, am, alg);
     }
     sla = block_sum<NTF>(sla, red);
     saw = block_sum<NTF>(saw, red);
@@ -997,6 +1011,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             int stop = status != 0.0;
             if (sw->compare && vmp_stop_rule(Lb, L0, sw->tol)) stop = 1;
             sw->ctl[VMP_SWEEP_STOP] = stop ? 1.0 : 0.0;
+            s.stop = stop ? 1.0 : 0.0;
             sw->ctl[VMP_SWEEP_L] = Lb;
             sw->ctl[VMP_SWEEP_EXECUTED] += 1.0;
         }
@@ -1007,14 +1022,159 @@ template <int KP, bool GRAM>
 __global__ void __launch_bounds__(NTF)
 pca_tail_fast_kernel(small_args a, double *st)
 {
-    pca_tail_body<KP, GRAM ? TAIL_GRAM : TAIL_PLAIN>(a, st, nullptr);
+    __shared__ tail_lds<KP> s;
+    pca_tail_body<KP, GRAM ? TAIL_GRAM : TAIL_PLAIN>(a, st, nullptr, s);
 }
 
 template <int KP>
 __global__ void __launch_bounds__(NTF)
 pca_tail_sweep_kernel(small_args a, double *st, vmp_sweep_tail sw)
 {
-    pca_tail_body<KP, TAIL_SWEEP>(a, st, &sw);
+    __shared__ tail_lds<KP> s;
+    pca_tail_body<KP, TAIL_SWEEP>(a, st, &sw, s);
+}
+
+// ---------------------------------------------------------------------------
+// One launch per held sweep (vmp_pca_sweeps, sweeps 1 .. n-1 of a chunk).
+//
+// Phase A, every workgroup: the Gram statistics of the sweep for one group of GRA rows of G, what
+// pca_gram_stats_kernel (vmp_pca.hip) computes and bit for bit the same -- every output is its own
+// chain of fused multiply-adds over d = 0 .. D-1 (Syx) or over the 8 rows of the group (Pxx), from
+// zero, in ascending order.  What differs is the bookkeeping: LDS is filled with 16-byte loads and
+// shifts instead of a division per element, and a thread owns a 2 x 2 block of (row, column)
+// outputs, so that four multiply-adds share four LDS reads instead of eight.
+// ---------------------------------------------------------------------------
+constexpr int GRA = 8;
+
+__host__ __device__ inline size_t gram_phase_a_lds(int KP, int DP)
+{
+    return ((size_t)KP * (DP + 1) + (size_t)GRA * DP + (size_t)GRA * (KP + 1)) * sizeof(double);
+}
+
+template <int KP>
+__device__ __forceinline__ void gram_phase_a(const vmp_pca_layout &L, int D, int K, double *st,
+                                             double *P, double *lds, int blk)
+{
+    constexpr int LDS_S = KP + 1, H = KP / 2, E = KP * KP / NTF;
+    const int DP = (int)L.DP, LA = DP + 1;
+    const int DP2 = DP >> 1, sh = __builtin_ctz(DP2);       // DP = 32, 64 or 128
+    double *As = lds;                    // KP x LA (rows >= K zero)
+    double *Gs = As + KP * LA;           // GRA x DP
+    double *Ss = Gs + GRA * DP;          // GRA x LDS_S
+    const int tid = threadIdx.x;
+    const int r0 = blk * GRA;
+    const double *A = st + L.off_A;
+    const double *G = st + L.off_G + (int64_t)r0 * DP;
+#pragma unroll 4
+    for (int e = tid; e < KP * DP2; e += NTF) {
+        const int k = e >> sh, c = (e & (DP2 - 1)) * 2;
+        v2f64 v = {0.0, 0.0};
+        if (k < K) v = *reinterpret_cast<const v2f64 *>(A + k * DP + c);
+        As[k * LA + c] = v[0];
+        As[k * LA + c + 1] = v[1];
+    }
+    for (int e = tid; e < GRA * DP2; e += NTF)
+        *reinterpret_cast<v2f64 *>(Gs + 2 * e) = *reinterpret_cast<const v2f64 *>(G + 2 * e);
+    __syncthreads();
+    // Syx[r][k] = sum_d G[r][d] A[k][d]: rows (ra, ra + 4) x columns (k0, k0 + H) per thread
+    if (tid < 4 * H) {
+        const int k0 = tid % H, ra = tid / H;
+        const double *g0 = Gs + ra * DP, *g1 = Gs + (ra + 4) * DP;
+        const double *a0 = As + k0 * LA, *a1 = As + (k0 + H) * LA;
+        double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;
+#pragma unroll 4
+        for (int d = 0; d < D; ++d) {
+            const double x0 = g0[d], x1 = g1[d], y0 = a0[d], y1 = a1[d];
+            s00 = __builtin_fma(x0, y0, s00);
+            s01 = __builtin_fma(x0, y1, s01);
+            s10 = __builtin_fma(x1, y0, s10);
+            s11 = __builtin_fma(x1, y1, s11);
+        }
+        Ss[ra * LDS_S + k0] = s00;
+        Ss[ra * LDS_S + k0 + H] = s01;
+        Ss[(ra + 4) * LDS_S + k0] = s10;
+        Ss[(ra + 4) * LDS_S + k0 + H] = s11;
+        double *So = st + L.off_S;
+        if (r0 + ra < D) {
+            if (k0 < K) So[(r0 + ra) * KP + k0] = s00;
+            if (k0 + H < K) So[(r0 + ra) * KP + k0 + H] = s01;
+        }
+        if (r0 + ra + 4 < D) {
+            if (k0 < K) So[(r0 + ra + 4) * KP + k0] = s10;
+            if (k0 + H < K) So[(r0 + ra + 4) * KP + k0 + H] = s11;
+        }
+    }
+    __syncthreads();
+    // Pxx_b[k][k'] = sum_{r in group} A[k][r] Syx[r][k']  (added up in fixed order by the tail)
+    double *Pb = P + (int64_t)blk * KP * KP;
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int e = tid + m * NTF;
+        const int k = e / KP, k2 = e % KP;
+        double s = 0.0;
+        if (k < K && k2 < K) {
+#pragma unroll
+            for (int r = 0; r < GRA; ++r) s = __builtin_fma(As[k * LA + r0 + r], Ss[r * LDS_S + k2], s);
+        }
+        Pb[e] = s;
+    }
+}
+
+// phase A alone (tests: bitwise against pca_gram_stats_kernel)
+template <int KP>
+__global__ void __launch_bounds__(NTF)
+pca_gram_fast_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
+{
+    extern __shared__ __align__(16) double gl[];
+    gram_phase_a<KP>(L, D, K, st, P, gl, blockIdx.x);
+}
+
+// Phase B, the workgroup that draws the last ticket: the tail of this sweep and, unless that tail
+// stops the loop, the head of the next one.  The ticket is the counter form of the in-launch
+// reduction: every workgroup drains its stores, lane 0 releases at agent scope and draws; the one
+// that draws nb - 1 knows that every other workgroup's Syx rows and Pxx block are released, acquires
+// once and reads them with plain loads.  A ticket is drawn once and nobody waits for anybody: the
+// other workgroups return, so there is no order of dispatch in which the launch cannot finish.
+// `ticket` is this sweep's own word, zero at the launch (one memset per chunk, vmp_pca_sweeps).
+// This kernel never runs beside a latent pass (no pass is in flight during held sweeps), so the
+// placement budget of pca_head_fast_kernel does not bind it.
+template <int KP>
+__global__ void __launch_bounds__(NTF)
+pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, unsigned int *ticket)
+{
+    extern __shared__ __align__(16) double gl[];
+    __shared__ tail_lds<KP> ts;
+    const int tid = threadIdx.x;
+    // an earlier sweep of the batch has stopped the loop: no ticket is drawn
+    if (!sw.first && sw.ctl[VMP_SWEEP_STOP] != 0.0) {
+        if (blockIdx.x == 0 && tid == 0) {
+            sw.slot[7] = 0.0;                          // not executed
+            sw.ctl[VMP_SWEEP_SKIPPED] += 1.0;
+        }
+        return;
+    }
+    gram_phase_a<KP>(a.L, a.D, a.K, st, P, gl, blockIdx.x);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    unsigned int *word = reinterpret_cast<unsigned int *>(gl);     // (phase A's LDS is free now)
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        *word = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (*word != gridDim.x - 1) return;
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    pca_tail_body<KP, TAIL_SWEEP>(a, st, &sw, ts);
+    __syncthreads();
+    if (ts.stop != 0.0) return;
+    // Cov_X, sum <x><x>^T, <alpha> and <tau> go over in LDS; the Syx rows the head loads were
+    // written by phase A (acquired above), the rows of <W> it reads back are its own
+    pca_head_body<KP, true>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2]);
 }
 
 bool fast_small_enabled()
@@ -1200,6 +1360,65 @@ int32_t vmp_pca_launch_sweep_tail(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_
         hipLaunchKernelGGL(pca_tail_sweep_kernel<16>, dim3(1), dim3(NTF), 0, ctx->stream, a, state, t);
     else
         hipLaunchKernelGGL(pca_tail_sweep_kernel<32>, dim3(1), dim3(NTF), 0, ctx->stream, a, state, t);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+// the dynamic LDS of phase A (at most 43 KB) beside 35 KB of static LDS needs the limit raised
+template <typename F>
+static int32_t raise_lds_once(vmp_ctx *ctx, F *k16, F *k32, bool *raised)
+{
+    const int dev = ctx->device & 63;
+    if (raised[dev]) return VMP_OK;
+    VMP_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k16,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    VMP_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k32,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    raised[dev] = true;
+    return VMP_OK;
+}
+
+int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P)
+{
+    vmp_pca_layout L;
+    const int32_t rc = vmp_pca_get_layout(D, K, &L);
+    VMP_REQUIRE(ctx, rc == VMP_OK, rc, "unsupported dims D=%d K=%d", D, K);
+    VMP_REQUIRE(ctx, L.KP <= 32 && D <= FAST_D, VMP_ERR_UNSUPPORTED,
+                "the fast Gram statistics cover K <= 32, D <= %d", FAST_D);
+    VMP_REQUIRE(ctx, ((uintptr_t)state % 16) == 0, VMP_ERR_INVALID, "state must be 16-byte aligned");
+    static bool raised[64] = {false};
+    const int32_t rr = raise_lds_once(ctx, pca_gram_fast_kernel<16>, pca_gram_fast_kernel<32>, raised);
+    if (rr != VMP_OK) return rr;
+    const int nb = (int)(L.DP / GRA);
+    const size_t lds = gram_phase_a_lds((int)L.KP, (int)L.DP);
+    if (L.KP == 16)
+        hipLaunchKernelGGL(pca_gram_fast_kernel<16>, dim3(nb), dim3(NTF), lds, ctx->stream, L, D, K,
+                           state, P);
+    else
+        hipLaunchKernelGGL(pca_gram_fast_kernel<32>, dim3(nb), dim3(NTF), lds, ctx->stream, L, D, K,
+                           state, P);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                                 double a0t, double b0t, double a0a, double b0a, double *state,
+                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket)
+{
+    small_args a;
+    const int32_t rc = fill_small_args(ctx, a, D, K, n_total, x_prec, a0t, b0t, a0a, b0a);
+    if (rc != VMP_OK) return rc;
+    static bool raised[64] = {false};
+    const int32_t rr = raise_lds_once(ctx, pca_sweep_mid_kernel<16>, pca_sweep_mid_kernel<32>, raised);
+    if (rr != VMP_OK) return rr;
+    const int nb = (int)(a.L.DP / GRA);
+    const size_t lds = gram_phase_a_lds((int)a.L.KP, (int)a.L.DP);
+    if (a.L.KP == 16)
+        hipLaunchKernelGGL(pca_sweep_mid_kernel<16>, dim3(nb), dim3(NTF), lds, ctx->stream, a, state,
+                           P, t, ticket);
+    else
+        hipLaunchKernelGGL(pca_sweep_mid_kernel<32>, dim3(nb), dim3(NTF), lds, ctx->stream, a, state,
+                           P, t, ticket);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }

@@ -144,6 +144,12 @@ class HIPKernels:
                                                     ctypes.byref(c)))
         return a.value, b.value, c.value
 
+    def sweep_mid_count(self):
+        """One-launch sweeps (Gram statistics, tail and next head) of the context so far."""
+        a = ctypes.c_int64()
+        self.rt.check(self.lib.vmp_pca_sweep_mid_count(self.ctx, ctypes.byref(a)))
+        return a.value
+
     def ensure_gram(self):
         """The Gram-form messages to W are formed lazily by the library (vmp_pca_ensure_gram):
         before the state block is read directly."""

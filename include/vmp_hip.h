@@ -248,6 +248,19 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
 /* Sweeps enqueued by vmp_pca_sweeps on this context since it was created, and how many of them the
  * device executed / skipped after a stop (waits for the context's stream). */
 int32_t vmp_pca_sweep_counts(vmp_ctx *ctx, int64_t *enqueued, int64_t *executed, int64_t *skipped);
+/* Sweeps 1 .. n-1 of a batch of n are one launch each: the Gram statistics on DP / 8 workgroups, and
+ * in the workgroup that draws the last ticket the tail of the sweep and the head of the next (tune
+ * key "pca_sweep_ticket" / VMP_PCA_SWEEP_TICKET, default 1; 0: three launches per sweep, the same
+ * arithmetic).  A state block that is not 16-byte aligned also takes the three launches, without an
+ * error: this count is where that shows.  Launches of that kernel on this context since it was
+ * created (no device read). */
+int32_t vmp_pca_sweep_mid_count(vmp_ctx *ctx, int64_t *launches);
+/* The Gram statistics of one sweep alone, from the A and G of the state block: rows of sum y<x>^T
+ * into the state, the DP / 8 partial blocks of sum <x><x>^T into the workspace (not added up).
+ * form 0: the kernel every other path uses; form 1: the body of the one-launch sweep (K <= 32,
+ * D <= 128, 16-byte aligned state).  The two agree bitwise. */
+int32_t vmp_pca_gram_stats_form(vmp_ctx *ctx, int32_t D, int32_t K, double *state, void *workspace,
+                                int32_t form);
 /* Gram form: the messages to W of the latest latent pass, S = [G A^T ; A G A^T] in the state block
  * (dot.py:581 collapsed onto the Gram matrix), are formed lazily -- by the fused tau / alpha / bound
  * kernel when it comes next, else by this call, which every other entry point that reads S makes
