@@ -10,7 +10,8 @@ step of the mixing weights, the mask of the observed node and the masks of its p
 checkpoint group.  ``match_plate_mixture`` holds the checks every matcher makes, in the order
 they were always made; a ``MixtureSpec`` supplies the family's own checks and every text that
 differs between the blocks.  A family's file keeps its limits, kernels class, allocations, priors,
-tables, pass, updates, the launches behind the bound terms and the moments.
+tables, pass, updates, the launches behind the bound terms and the moments.  mmm.py (count vectors,
+plates (N,) and (K,)) derives from ``PlateMixturePlan`` too, with a matcher of its own.
 """
 from collections import namedtuple
 
@@ -193,7 +194,7 @@ class PlateMixturePlan:
         self.roles = roles
         for key, nd in roles.items():
             setattr(self, key, nd)
-        self.N, self.D = roles[self.OBSERVED].plates
+        self._set_shape(roles)
         self.K = roles[self.OBSERVED].clusters
         self._rt, self._kernels = runtime, kernels
         self._ready = False
@@ -204,6 +205,10 @@ class PlateMixturePlan:
         self._L = None
         for nd in roles.values():
             nd._plan = self
+
+    def _set_shape(self, roles):
+        """The plate sizes of the block; mmm.py, whose rows are count vectors, has (N,) and M."""
+        self.N, self.D = roles[self.OBSERVED].plates
 
     @property
     def rt(self):
@@ -269,7 +274,7 @@ class PlateMixturePlan:
                 raise ValueError("Values must be integers")
         elif lab.dtype.kind not in 'iub':
             raise ValueError("Values must be integers")
-        lab = np.array(np.broadcast_to(lab, (N, 1)), dtype=np.int64).reshape(N)
+        lab = np.array(np.broadcast_to(lab, self.Z.plates), dtype=np.int64).reshape(N)
         if lab.size and (lab.min() < 0 or lab.max() >= self.K):
             raise ValueError("Invalid category index")
         self.labels = self.rt.torch.from_numpy(lab.astype(np.int32)).to(self.rt.device)

@@ -35,13 +35,18 @@ class Mixture(Stochastic):
             # arguments of that class (the reference forwards them to ``_constructor``, e.g. the
             # ``ndim`` of ``Mixture(z, GaussianARD, mu, alpha, 1)``)
             npar = getattr(node_class, '_parent_count', None)
+            # constructor arguments that stand before the parents and are no parents: the number
+            # of trials of ``Mixture(z, Multinomial, n, p)`` (multinomial.py:276-306 returns
+            # ``parents = [p]`` and keeps ``n`` in the distribution)
+            lead = getattr(node_class, '_leading_args', 0)
+            head, params = params[:lead], params[lead:]
             extra = ()
             if npar is not None and len(params) > npar:
                 params, extra = params[:npar], params[npar:]
             super().__init__(z, *params, plates=(), dims=((), ()), name=name)
             # a throw-away instance of the mixed node class gives dims and plates
             # (with the cluster axis still among the plates)
-            proto = node_class(*self.parents[1:], *extra, **node_kwargs)
+            proto = node_class(*head, *self.parents[1:], *extra, **node_kwargs)
         self._plates_multiplier_arg = plates_multiplier
         self.node_class = node_class
         self.cluster_plate = cluster_plate
@@ -87,10 +92,18 @@ class Mixture(Stochastic):
         # Poisson, ...) on this node's plates
         saved = self._proto.plates
         self._proto.plates = self.plates
+        # trials of a Multinomial given per row, (N, 1) beside the cluster axis: the rows of x
+        # are compared with them without that axis
+        trials = getattr(self._proto, 'trials', None)
+        if trials is not None and trials.ndim >= -self.cluster_plate \
+                and trials.shape[self.cluster_plate] == 1:
+            self._proto.trials = np.squeeze(trials, axis=self.cluster_plate)
         try:
             self._proto._check_value_shape(x)
         finally:
             self._proto.plates = saved
+            if trials is not None:
+                self._proto.trials = trials
 
 
 def MultiMixture(thetas, *mixture_args, **kwargs):

@@ -13,6 +13,9 @@ from ..utils.shapes import broadcasted_shape
 
 class Multinomial(Stochastic):
 
+    _parent_count = 1
+    _leading_args = 1           # ``n``: a constructor argument ahead of the parent, no parent
+
     def __init__(self, n, p, plates=None, name=None, plates_multiplier=None):
         trials = np.asarray(n)
         if not np.issubdtype(trials.dtype, np.integer):

@@ -1287,6 +1287,48 @@ int32_t vmp_pmm_update(vmp_ctx *ctx, int32_t D, int32_t K, int32_t per_element,
                        const double *prior_a, const double *prior_b, const double *S,
                        const double *cnt, double *par, double *mom, double *bound);
 
+/* The fused multinomial-mixture block (mixture of unigrams, count-vector clustering):
+ *     R = Dirichlet(a);  Z = Categorical(R, plates=(N,))
+ *     P = Dirichlet(a0, plates=(K,)) over M words;  X = Mixture(Z, Multinomial, n, P);  X.observe(x)
+ * (details: bayespy_amd/csrc/vmp_mmm.hip, vmp_mmm_dev.h).  N rows of M counts that add up to the
+ * row's number of trials, K clusters; x is kept as one uint16 per entry.  <log p> and the statistic
+ * S are (K x M), element (k, m) at k M + m: K Dirichlet rows for vmp_lda_dirichlet (rows K, cols M,
+ * row_stride M, col_stride 1).  The table of the pass is (M x K), word-major.  No (N, K) or
+ * (N, K, M) array exists.
+ *   vmp_mmm_limits (host only): *max_K = 64, *max_M = 1024, *max_count = 65534.
+ *   vmp_mmm_plan (host only): for (N, M, K) the rows of a chunk *chunk_rows (one workgroup, a
+ *     function of the shape alone) and the scratch *workspace_doubles of the pass, which is never
+ *     below what vmp_mmm_pack needs (1024 doubles).
+ *   vmp_mmm_pack: x (N x M, row-major; dtype 0 = float64, 1 = int64, 2 = uint8, 3 = int32) and
+ *     trials (N int64) to N M uint16.  A value that is negative or no integer sets flags[0] (no
+ *     integer: flags[2] as well), one above 65534 sets flags[1]; such an entry is packed as zero.
+ *     A row of valid counts that do not add up to its trials sets flags[3].  flags (4 int32) are
+ *     only ever set.  *lcoef = sum_n [lgamma(trials_n + 1) - sum_m lgamma(x_nm + 1)], per-block
+ *     partials added in block order, no atomics.  ws: 1024 doubles.
+ *   vmp_mmm_tables: L[m, k] = elog_p[k, m] - elog_p[0, m] (CENTRED: cluster 0 taken out of every
+ *     word, which moves all logits of a row by one amount, so r and scal[0] - scal[1] - scal[2] of
+ *     the pass do not change) and c = elog_pi less its largest element.  A NULL elog_p gives
+ *     L = 0: Z under its prior.
+ *   vmp_mmm_pass: logit_nk = c[k] + sum_m x_nm L[m, k]; Out: S (K x M) = r^T x, Nk and
+ *     scal[0] = sum lse, scal[1] = Nk . c, scal[2] = S . L.  `labels` (N int32) non-NULL: r is
+ *     one-hot, lse = 0.  r_out (N x K) is written on request only.  ws: vmp_mmm_plan's doubles.
+ *     No atomics: the bits of every output depend on x_packed, the tables and (N, M, K) only, with
+ *     or without r_out.  N = 0 gives zeros.  x_packed must be 2-byte aligned (8 for the fast loads).
+ *   Order of the checks: null context, negative or zero sizes: VMP_ERR_INVALID; then K or M above
+ *   the limits: VMP_ERR_UNSUPPORTED; then a null required argument: VMP_ERR_INVALID.  Nothing is
+ *   launched after a refusal. */
+int32_t vmp_mmm_limits(int32_t *max_K, int32_t *max_M, int32_t *max_count);
+int32_t vmp_mmm_plan(int64_t N, int32_t M, int32_t K, int64_t *chunk_rows,
+                     int64_t *workspace_doubles);
+int32_t vmp_mmm_pack(vmp_ctx *ctx, int64_t N, int32_t M, int32_t dtype, const void *x,
+                     const int64_t *trials, uint16_t *x_packed, int32_t *flags, double *lcoef,
+                     double *ws);
+int32_t vmp_mmm_tables(vmp_ctx *ctx, int32_t M, int32_t K, const double *elog_p,
+                       const double *elog_pi, double *L, double *c);
+int32_t vmp_mmm_pass(vmp_ctx *ctx, int64_t N, int32_t M, int32_t K, const uint16_t *x_packed,
+                     const int32_t *labels, const double *L, const double *c, double *ws,
+                     double *S, double *Nk, double *scal, double *r_out);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
