@@ -281,6 +281,11 @@ SIGNATURES = {
     'vmp_mmm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32] + [c_vp] * 6),
     'vmp_mmm_tables': (c_i32, [c_vp, c_i32, c_i32] + [c_vp] * 4),
     'vmp_mmm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32] + [c_vp] * 9),
+    'vmp_binm_limits': (c_i32, [P(c_i32), P(c_i32), P(c_i32)]),
+    'vmp_binm_plan': (c_i32, [c_i64, c_i32, c_i32, P(c_i64), P(c_i64)]),
+    'vmp_binm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_i64] + [c_vp] * 7),
+    'vmp_binm_tables': (c_i32, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 7),
+    'vmp_binm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 14),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_hold_passes': (c_i32, [c_vp, c_i32]),

@@ -17,6 +17,7 @@ from .dgmm_masked import MaskedDiagGaussianMixturePlan
 from .cmm import CategoricalMixturePlan
 from .pmm import PoissonMixturePlan
 from .mmm import MultinomialMixturePlan
+from .binm import BinomialMixturePlan
 
 PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
 # engine='fused': a block's opt-in form takes the place of its default form
@@ -44,6 +45,9 @@ OPT_IN_COUNTS = [PoissonMixturePlan]
 # engine='fused': opt-in blocks for count vectors, tried after ``OPT_IN_COUNTS`` (MultinomialMixturePlan
 # takes the mixtures of Multinomial, which CategoricalMixturePlan declines with a reason)
 OPT_IN_VECTORS = [MultinomialMixturePlan]
+# engine='fused': opt-in blocks for successes out of trials, tried after ``OPT_IN_VECTORS``
+# (BinomialMixturePlan takes the mixtures of Binomial, which BernoulliMixturePlan declines with a reason)
+OPT_IN_TRIALS = [BinomialMixturePlan]
 
 
 def _with_masked(types):
@@ -82,7 +86,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or any(type(p) in v for v in OPT_IN_AFTER.values())
                                  or any(type(p) in v for v in OPT_IN_MASKED.values())
                                  or type(p) in OPT_IN_LAST or type(p) in OPT_IN_COUNTS
-                                 or type(p) in OPT_IN_VECTORS
+                                 or type(p) in OPT_IN_VECTORS or type(p) in OPT_IN_TRIALS
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -134,7 +138,7 @@ def compile_model(nodes, engine=None, **options):
         return [plan]
     types = [Q for P in PLAN_TYPES for Q in [OPT_IN_FORMS.get(P, P)] + OPT_IN_AFTER.get(P, [])] \
         + _with_masked(opt_in_types() + OPT_IN_MORE) + OPT_IN_LAST + OPT_IN_COUNTS \
-        + OPT_IN_VECTORS \
+        + OPT_IN_VECTORS + OPT_IN_TRIALS \
         if engine == 'fused' \
         else PLAN_TYPES
     remaining = [n for n in nodes]

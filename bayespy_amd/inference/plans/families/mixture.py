@@ -146,8 +146,18 @@ class MixtureFamily(Family):
             out.append(misc.sum_multiply(_trail(p, nd), ph, axis=-(nd + 1)))
         return out
 
+    def _squeezed(self):
+        """The mixed family for the formulas that see no cluster axis (mixture.py:249-300,
+        ``squeezed_distribution``): constants of the family with that axis, such as the trials
+        of a Binomial, lose it."""
+        f = getattr(self, '_squeezed_base', None)
+        if f is None:
+            sq = getattr(self.base, 'squeezed', None)
+            f = self._squeezed_base = sq(self.cp) if sq is not None else self.base
+        return f
+
     def moments_and_cgf(self, phi):
-        return self.base.moments_and_cgf(phi)
+        return self._squeezed().moments_and_cgf(phi)
 
     def cgf_from_parents(self, up):
         up = self._cluster_last(up)
@@ -156,7 +166,7 @@ class MixtureFamily(Family):
         return misc.sum_multiply(p, _arr(gk), axis=-1)
 
     def fixed_moments_and_f(self, x):
-        return self.base.fixed_moments_and_f(x)
+        return self._squeezed().fixed_moments_and_f(x)
 
     def gradient(self, rg, u, phi):
         return self.base.gradient(rg, u, phi)          # mixture.py:352-356

@@ -78,6 +78,18 @@ class BinomialFamily(Family):
         self.trials = np.asarray(node.trials, dtype=np.float64)
         self.Nd = DArray.from_host(self.trials)
 
+    def squeezed(self, axis):
+        """The family with the trials' plate axis ``axis`` (negative, of extent one) taken out:
+        what a mixture over that axis uses wherever the cluster axis is gone already
+        (binomial.py:144-160, mixture.py:249-300)."""
+        if self.trials.ndim < -axis:
+            return self
+        import copy
+        f = copy.copy(self)
+        f.trials = np.squeeze(self.trials, axis=axis)
+        f.Nd = DArray.from_host(f.trials)
+        return f
+
     def constant_moments(self, index, value):
         return [fuse(lambda q: da.log(q), _pair(value))]          # BetaMoments, beta.py:33-37
 

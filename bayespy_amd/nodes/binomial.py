@@ -15,6 +15,9 @@ from ..utils.shapes import broadcasted_shape
 
 
 class Binomial(Stochastic):
+    # ``Mixture(z, Binomial, n, p)``: the number of trials stands before the parent and is none
+    # (binomial.py:214-232 returns ``parents = [p]`` and keeps ``n`` in the distribution)
+    _leading_args = 1
 
     def __init__(self, n, p, plates=None, name=None, plates_multiplier=None):
         trials = np.asarray(n)
@@ -58,6 +61,7 @@ class Binomial(Stochastic):
 
 class Bernoulli(Binomial):
     _parent_count = 1
+    _leading_args = 0           # ``Mixture(z, Bernoulli, p)``: nothing before the parent
 
     def __init__(self, p, plates=None, name=None, plates_multiplier=None):
         super().__init__(1, p, plates=plates, name=name, plates_multiplier=plates_multiplier)

@@ -47,6 +47,19 @@ class Mixture(Stochastic):
             # a throw-away instance of the mixed node class gives dims and plates
             # (with the cluster axis still among the plates)
             proto = node_class(*head, *self.parents[1:], *extra, **node_kwargs)
+        from .binomial import Binomial
+        if isinstance(proto, Binomial) and proto.trials.ndim >= -cluster_plate \
+                and proto.trials.shape[cluster_plate] != 1:
+            # BinomialDistribution.squeeze (binomial.py:144-160) through MixtureDistribution
+            # (mixture.py:38-46): a ValueError when the node is built
+            for p in self.parents:
+                p.children = [(c, i) for (c, i) in p.children if c is not proto and c is not self]
+            raise ValueError(
+                "Cannot mix over plate axis {0}: The number of trials must be constant over a "
+                "squeezed axis, so the corresponding array axis must be singleton. Cannot squeeze "
+                "axis {0} from a binomial distribution because the number of trials arrays has "
+                "shape {2}, so the given axis has length {1} != 1. ".format(
+                    cluster_plate, proto.trials.shape[cluster_plate], proto.trials.shape))
         self._plates_multiplier_arg = plates_multiplier
         self.node_class = node_class
         self.cluster_plate = cluster_plate

@@ -1329,6 +1329,71 @@ int32_t vmp_mmm_pass(vmp_ctx *ctx, int64_t N, int32_t M, int32_t K, const uint16
                      const int32_t *labels, const double *L, const double *c, double *ws,
                      double *S, double *Nk, double *scal, double *r_out);
 
+/* Binomial mixture (successes out of trials): the pack, the tables and the plate pass of the fused block
+ *     R = Dirichlet(a);  Z = Categorical(R, plates=(N, 1))
+ *     P = Beta(a0, plates=(D, K));  X = Mixture(Z, Binomial, n, P);  X.observe(x[, mask])
+ * (details: bayespy_amd/csrc/vmp_binm.hip, vmp_binm_dev.h).  N rows of D counts x_nd out of n_nd
+ * trials, K clusters; counts and trials are kept as one uint16 per entry each (two planes), a hidden
+ * entry as count 0 and trials 0xFFFF; tables and statistics are (D x K), element (d, k) at d K + k;
+ * elog_p and counts are (D K, 2): (<log p>, <log(1 - p)>) and (S, T - S), the Dirichlet rows of two
+ * columns that vmp_lda_dirichlet updates (alpha = alpha0 + S, beta = beta0 + T - S, the bound
+ * exactly zero for an element at its prior) as for the Bernoulli block.  No (N, K) or (N, D, K)
+ * array exists.
+ *   vmp_binm_limits (host only): *max_K = 64, *max_D = 1024, *max_trials = 65534.
+ *   vmp_binm_plan (host only): for (N, D, K) the rows of a chunk *chunk_rows (one workgroup, a
+ *     function of the shape alone) and the scratch *workspace_doubles of the pass, which is never
+ *     below what vmp_binm_pack needs (3072 doubles).
+ *   vmp_binm_pack: x (N x D, row-major; dtype 0 = float64, 1 = int64, 2 = uint8, 3 = int32), the
+ *     trials of entry (n, d) at trials[n trials_stride_n + d trials_stride_d] (int64, strides in
+ *     elements, zero for an axis the trials do not vary along: a scalar, (D, 1), (N, 1, 1) and
+ *     (N, D, 1) are read in place) and mask (N x D bytes, non-zero = observed, or NULL) to two planes
+ *     of N D uint16.  A hidden position gets trials 0xFFFF and count 0 by a select whatever stands
+ *     there (NaN, -1, 1e300).  An OBSERVED entry that fails a check is packed as hidden and sets
+ *     one flag: flags[0] a negative count, flags[1] a count that is no integer, flags[2] a count
+ *     above its trials, flags[3] trials above 65534.  The checks come before any conversion to an
+ *     integer.  flags: four device int32, cleared by the caller.  counts (three device int64):
+ *     the observed entries, the hidden ones, and 1 when the trials of every entry equal those of
+ *     row 0 of its column (constant along the rows), else 0.  *lcoef = sum over the observed entries
+ *     of lgamma(n + 1) - lgamma(x + 1) - lgamma(n - x + 1), per-block partials added in block order,
+ *     no atomics.  ws: 3072 doubles.
+ *   vmp_binm_tables: l1 = <log p> - <log(1 - p)>, l0 = <log(1 - p)> and c = elog_pi less its
+ *     largest element.  Bit 1 of form: the tables of the pass, CENTRED -- column 0 of every row is
+ *     taken out of l1 and l0, which moves all logits of a row alike (vmp_pmm_tables).  With ncol
+ *     (D doubles, the trials of a column) and cfold non-NULL also cfold[k] = elog_pi[k] +
+ *     sum_d ncol[d] l0[d, k] (l0 as written), less its largest element: the c of the one-plane form.
+ *     A NULL elog_p gives l1 = l0 = 0: Z under its prior.
+ *   vmp_binm_pass: one_plane = 0: logit_nk = c[k] + sum_d xt_nd l1[d, k] + nt_nd l0[d, k] with
+ *     m = (n_packed != 0xFFFF), xt = m o x, nt = m o n; Out: S = r^T xt, T = r^T nt (D x K), Nk and
+ *     scal[0] = sum lse over the rows with an observed entry, scal[1] = Nk . c, scal[2] = S . l1 +
+ *     T . l0 (formed row by row inside the pass as sum_n r_n . (logit_n - c), the same number with
+ *     less rounding; with labels from S and T), counts = (S, T - S).  A row with nothing observed has r = softmax(c) (with labels: its
+ *     one-hot row), written to r_out, and adds nothing to Nk and scal[0] and zeros to S and T.
+ *     ncol is not read.  one_plane = 1, for trials that are constant along the rows with nothing
+ *     hidden: c is the cfold of vmp_binm_tables and ncol the trials of the columns; only x_packed is
+ *     read, by the kernel of vmp_pmm_pass (hidden = 0, l = l1): logit_nk = c[k] + sum_d x_nd l1[d, k];
+ *     Out: S, Nk, scal[0], scal[1] = Nk . c, scal[2] = S . l1, then T[d, k] = ncol[d] Nk[k] and
+ *     counts.  `labels` (N int32) non-NULL: r is one-hot, lse = 0.  r_out (N x K) is written on
+ *     request only.  ws: vmp_binm_plan's doubles.  No atomics: the bits of every output depend on
+ *     the packed planes, the tables and (N, D, K) only, with or without r_out.  N = 0 gives zeros.
+ *   Order of the checks: null context, a size below 1 (N below 0), a form, dtype or stride out of
+ *   range: VMP_ERR_INVALID; then K or D above the limits: VMP_ERR_UNSUPPORTED; then a null required
+ *   argument: VMP_ERR_INVALID.  Nothing is launched after a refusal. */
+int32_t vmp_binm_limits(int32_t *max_K, int32_t *max_D, int32_t *max_trials);
+int32_t vmp_binm_plan(int64_t N, int32_t D, int32_t K, int64_t *chunk_rows,
+                      int64_t *workspace_doubles);
+int32_t vmp_binm_pack(vmp_ctx *ctx, int64_t N, int32_t D, int32_t dtype, const void *x,
+                      const int64_t *trials, int64_t trials_stride_n, int64_t trials_stride_d,
+                      const uint8_t *mask, uint16_t *x_packed, uint16_t *n_packed, int32_t *flags,
+                      int64_t *counts, double *lcoef, double *ws);
+int32_t vmp_binm_tables(vmp_ctx *ctx, int32_t D, int32_t K, int32_t form, const double *elog_p,
+                        const double *elog_pi, const double *ncol, double *l1, double *l0,
+                        double *c, double *cfold);
+int32_t vmp_binm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, int32_t one_plane,
+                      const uint16_t *x_packed, const uint16_t *n_packed, const double *ncol,
+                      const int32_t *labels, const double *l1, const double *l0, const double *c,
+                      double *ws, double *S, double *T, double *Nk, double *counts, double *scal,
+                      double *r_out);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
