@@ -286,6 +286,10 @@ SIGNATURES = {
     'vmp_binm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_i64] + [c_vp] * 7),
     'vmp_binm_tables': (c_i32, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 7),
     'vmp_binm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 14),
+    'vmp_mix_natural_step_workspace': (c_i32, [c_i32, c_i64, c_i64, c_i32, P(c_i64)]),
+    'vmp_mix_natural_step': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                     c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                     c_f64, c_f64, c_vp, c_vp]),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_hold_passes': (c_i32, [c_vp, c_i32]),

@@ -26,10 +26,11 @@
 // the second kernel; nothing needs clearing beforehand.
 #include "vmp_common.h"
 #include "vmp_lda_dev.h"
+#include "vmp_table_dev.h"
 
 namespace {
 
-constexpr int LDA_NT = 256;          // token pass, combine kernel, dot partials
+constexpr int LDA_NT = VMP_TABLE_NT; // token pass, combine kernel, dot partials, Dirichlet rows
 constexpr int LDA_RED_NT = 1024;     // the one workgroup that adds partial sums in index order
 constexpr int LDA_MAX_K = 64;
 constexpr int LDA_MAX_PART = 1024;   // partial sums of a dot product
@@ -180,21 +181,8 @@ lda_sum_final_kernel(int64_t cnt, const double *__restrict__ x, double *__restri
     if (threadIdx.x == 0) out[0] = v;
 }
 
-// The parameter a Dirichlet step leaves at element e: q = prior + mult * counts, and from the
-// present alpha a step of length `scale` towards q.  scale == 1 does not read alpha (it may hold the
-// NaN of a point mass).
-__device__ __forceinline__ double lda_step_value(double p, const double *__restrict__ counts,
-                                                 int64_t e, double mult, double scale,
-                                                 const double *alpha)
-{
-    const double q = counts ? p + mult * counts[e] : p;
-    if (scale == 1.0) return q;
-    const double a = alpha[e];
-    return a + scale * (q - a);
-}
-
-// Dirichlet rows with few columns: one thread per row.  Element (r, c) of every array stands at
-// r * rs + c * cs.  STEP: alpha moves by lda_step_value instead of being set to prior + counts.
+// Dirichlet rows with few columns: one thread per row (vmp_table_dev.h).  STEP: alpha moves by
+// vmp_table_step_value instead of being set to prior + counts.
 template <bool STEP>
 __global__ void __launch_bounds__(LDA_NT)
 lda_dirichlet_rows_kernel(int64_t rows, int cols, int64_t rs, int64_t cs,
@@ -204,28 +192,8 @@ lda_dirichlet_rows_kernel(int64_t rows, int cols, int64_t rs, int64_t cs,
 {
     const int64_t r = (int64_t)blockIdx.x * LDA_NT + threadIdx.x;
     if (r >= rows) return;
-    double s = 0.0, s0 = 0.0;
-    for (int c = 0; c < cols; ++c) {
-        const int64_t e = r * rs + c * cs;
-        const double p = prior[e];
-        const double v = STEP ? lda_step_value(p, counts, e, mult, scale, alpha)
-                              : (counts ? p + counts[e] : p);
-        alpha[e] = v;
-        s += v;
-        s0 += p;
-    }
-    const double psis = vmp_digamma(s);
-    double g = vmp_lgamma(s), g0 = vmp_lgamma(s0), L = 0.0;
-    for (int c = 0; c < cols; ++c) {
-        const int64_t e = r * rs + c * cs;
-        const double p = prior[e], v = alpha[e];
-        const double el = vmp_digamma(v) - psis;
-        elog[e] = el;
-        g -= vmp_lgamma(v);
-        g0 -= vmp_lgamma(p);
-        L += (p - v) * el;
-    }
-    rowL[r] = L + g0 - g;
+    rowL[r] = vmp_dirichlet_row_thread<STEP>(r, cols, rs, cs, prior, counts, mult, scale, alpha,
+                                             elog);
 }
 
 // Dirichlet rows with many columns: one workgroup per row
@@ -237,33 +205,9 @@ lda_dirichlet_wide_kernel(int64_t cols, int64_t rs, int64_t cs, const double *__
 {
     __shared__ double red[LDA_NT / 64];
     const int64_t r = blockIdx.x;
-    double s = 0.0, s0 = 0.0;
-    for (int64_t c = threadIdx.x; c < cols; c += LDA_NT) {
-        const int64_t e = r * rs + c * cs;
-        const double p = prior[e];
-        const double v = STEP ? lda_step_value(p, counts, e, mult, scale, alpha)
-                              : (counts ? p + counts[e] : p);
-        alpha[e] = v;
-        s += v;
-        s0 += p;
-    }
-    s = block_sum<LDA_NT>(s, red);
-    s0 = block_sum<LDA_NT>(s0, red);
-    const double psis = vmp_digamma(s);
-    double g = 0.0, g0 = 0.0, L = 0.0;
-    for (int64_t c = threadIdx.x; c < cols; c += LDA_NT) {
-        const int64_t e = r * rs + c * cs;
-        const double p = prior[e], v = alpha[e];       // this thread's own stores
-        const double el = vmp_digamma(v) - psis;
-        elog[e] = el;
-        g += vmp_lgamma(v);
-        g0 += vmp_lgamma(p);
-        L += (p - v) * el;
-    }
-    g = block_sum<LDA_NT>(g, red);
-    g0 = block_sum<LDA_NT>(g0, red);
-    L = block_sum<LDA_NT>(L, red);
-    if (threadIdx.x == 0) rowL[r] = L + (vmp_lgamma(s0) - g0) - (vmp_lgamma(s) - g);
+    const double L = vmp_dirichlet_row_block<STEP, LDA_NT>(r, cols, rs, cs, prior, counts, mult,
+                                                           scale, alpha, elog, red);
+    if (threadIdx.x == 0) rowL[r] = L;
 }
 
 // -- the step on a transposed table ------------------------------------------------------------------
@@ -315,7 +259,7 @@ lda_step_t_alpha_kernel(int64_t V, int K, int64_t cpb, const double *__restrict_
         const int64_t end = c1 * K, stride = (int64_t)per * K;
         for (int64_t e = c0 * K + t; e < end; e += stride) {
             const double p = prior[e];
-            const double v = lda_step_value(p, counts, e, mult, scale, alpha);
+            const double v = vmp_table_step_value(p, counts, e, mult, scale, alpha);
             alpha[e] = v;
             s += v;
             s0 += p;
@@ -528,7 +472,7 @@ int32_t vmp_lda_dirichlet(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t row_
         VMP_HIP_CHECK(ctx, hipMemsetAsync(bound, 0, sizeof(double), ctx->stream));
         return VMP_OK;
     }
-    if (cols <= 64)
+    if (cols <= VMP_TABLE_THREAD_COLS)
         hipLaunchKernelGGL(lda_dirichlet_rows_kernel<false>,
                            dim3((unsigned)((rows + LDA_NT - 1) / LDA_NT)), dim3(LDA_NT), 0,
                            ctx->stream, rows, (int)cols, row_stride, col_stride, prior, counts, 1.0,
@@ -592,7 +536,7 @@ int32_t vmp_lda_dirichlet_step(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t
         hipLaunchKernelGGL(lda_sum_final_kernel, dim3(1), dim3(LDA_RED_NT), 0, ctx->stream,
                            g.nb + K, ws, bound);
     } else {
-        if (cols <= 64)
+        if (cols <= VMP_TABLE_THREAD_COLS)
             hipLaunchKernelGGL(lda_dirichlet_rows_kernel<true>,
                                dim3((unsigned)((rows + LDA_NT - 1) / LDA_NT)), dim3(LDA_NT), 0,
                                ctx->stream, rows, (int)cols, row_stride, col_stride, prior, counts,

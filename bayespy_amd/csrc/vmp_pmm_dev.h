@@ -268,14 +268,22 @@ __host__ __device__ inline double vmp_pmm_lgamma_psi_diff(double a0, double s)
     return ((st - logs) - lost) + s * (gap + recip);
 }
 
-__host__ __device__ inline double vmp_pmm_update_lam(double a0, double b0, double s, double cnt,
-                                                     double *par, double *mom)
+// q = Gamma(a, b) that stands s = a - a0 and cnt = b - b0 away from its prior: par, mom and the
+// bound term.  The update has s and cnt as they are; a natural-gradient step (vmp_mix_svi.hip) forms
+// them from the stepped parameters.
+__host__ __device__ inline double vmp_pmm_lam_state(double a0, double b0, double a, double b,
+                                                    double s, double cnt, double *par, double *mom)
 {
-    const double a = a0 + s, b = b0 + cnt;
     const double psi = vmp_digamma(a), lam = a / b;
     par[0] = a;
     par[1] = b;
     mom[0] = lam;
     mom[1] = psi - log(b);
     return -a0 * log1p(cnt / b0) + vmp_pmm_lgamma_psi_diff(a0, s) + cnt * lam;
+}
+
+__host__ __device__ inline double vmp_pmm_update_lam(double a0, double b0, double s, double cnt,
+                                                     double *par, double *mom)
+{
+    return vmp_pmm_lam_state(a0, b0, a0 + s, b0 + cnt, s, cnt, par, mom);
 }

@@ -9,15 +9,15 @@ from .gmm import GMMPlan, GMMSVIPlan
 from .lssm import LSSMPlan
 from .lssm_masked import MaskedLSSMPlan
 from .lda import LDAPlan, LDASVIPlan
-from .bmm import BernoulliMixturePlan
+from .bmm import BernoulliMixturePlan, BernoulliMixtureSVIPlan
 from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
-from .cmm import CategoricalMixturePlan
-from .pmm import PoissonMixturePlan
-from .mmm import MultinomialMixturePlan
-from .binm import BinomialMixturePlan
+from .cmm import CategoricalMixturePlan, CategoricalMixtureSVIPlan
+from .pmm import PoissonMixturePlan, PoissonMixtureSVIPlan
+from .mmm import MultinomialMixturePlan, MultinomialMixtureSVIPlan
+from .binm import BinomialMixturePlan, BinomialMixtureSVIPlan
 
 PLAN_TYPES = [PCAPlan, MaskedPCAPlan, GMMPlan, LSSMPlan, MaskedLSSMPlan, LDAPlan]
 # engine='fused': a block's opt-in form takes the place of its default form
@@ -48,11 +48,25 @@ OPT_IN_VECTORS = [MultinomialMixturePlan]
 # engine='fused': opt-in blocks for successes out of trials, tried after ``OPT_IN_VECTORS``
 # (BinomialMixturePlan takes the mixtures of Binomial, which BernoulliMixturePlan declines with a reason)
 OPT_IN_TRIALS = [BinomialMixturePlan]
+# engine='fused+batches': the form of a count-mixture block under mini-batches (stochastic VI,
+# plans/_mixture_svi.py), a plan class of its own, tried right after that block (which declines every
+# plates_multiplier with a reason).  Everything else is engine='fused'; plain 'fused' does not try
+# these forms and keeps raising for such a model with the blocks' reasons
+OPT_IN_BATCHES = {BernoulliMixturePlan: [BernoulliMixtureSVIPlan],
+                  CategoricalMixturePlan: [CategoricalMixtureSVIPlan],
+                  PoissonMixturePlan: [PoissonMixtureSVIPlan],
+                  MultinomialMixturePlan: [MultinomialMixtureSVIPlan],
+                  BinomialMixturePlan: [BinomialMixtureSVIPlan]}
 
 
 def _with_masked(types):
     """``types`` with the plan classes of ``OPT_IN_MASKED`` inserted after their block."""
     return [Q for P in types for Q in [P] + OPT_IN_MASKED.get(P, [])]
+
+
+def _with_batches(types):
+    """``types`` with the plan classes of ``OPT_IN_BATCHES`` inserted after their block."""
+    return [Q for P in types for Q in [P] + OPT_IN_BATCHES.get(P, [])]
 
 
 def opt_in_types():
@@ -122,7 +136,13 @@ def compile_model(nodes, engine=None, **options):
     import os
     if engine is None:
         engine = os.environ.get('BAYESPY_AMD_ENGINE', 'auto')
+    batches = engine == 'fused+batches'
+    if batches:
+        engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
+    if kept is not None and not batches \
+            and any(type(p) in v for p in kept for v in OPT_IN_BATCHES.values()):
+        kept = None             # a mini-batch form is kept only where it is asked for
     if kept is not None:
         return kept
     stale = [n.name for n in nodes if isinstance(n, Stochastic) and n._plan is not None
@@ -141,6 +161,8 @@ def compile_model(nodes, engine=None, **options):
         + OPT_IN_VECTORS + OPT_IN_TRIALS \
         if engine == 'fused' \
         else PLAN_TYPES
+    if batches:
+        types = _with_batches(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

@@ -17,6 +17,24 @@ class DirichletKernels:
             self.ctx, rows, cols, rs, cs, ptr(prior), ptr(counts) if counts is not None else None,
             ptr(alpha), ptr(elog), ptr(ws), ptr(bound)))
 
+    def natural_step_workspace(self, kind, rows, cols, K):
+        """The doubles of ``ws`` that ``natural_step`` needs for a table of that shape."""
+        import ctypes
+        w = ctypes.c_int64()
+        self.rt.check(self.lib.vmp_mix_natural_step_workspace(kind, rows, cols, K, ctypes.byref(w)))
+        return w.value
+
+    def natural_step(self, kind, nodes, rows, cols, rs, cs, prior, prior_b, stat, cnt, per_element,
+                     par, mom, K, prior_r, Nk, alpha_r, elog_r, mult, scale, ws, bound):
+        """``vmp_mix_natural_step``: the parameter table of a mixture block (bit 1 of ``nodes``)
+        and its weights row (bit 2) one step along their natural gradients, in one launch."""
+        def p(t):
+            return ptr(t) if t is not None else None
+        self.rt.check(self.lib.vmp_mix_natural_step(
+            self.ctx, kind, nodes, rows, cols, rs, cs, p(prior), p(prior_b), p(stat), p(cnt),
+            per_element, p(par), p(mom), K, p(prior_r), p(Nk), p(alpha_r), p(elog_r), float(mult),
+            float(scale), p(ws), p(bound)))
+
     def dot(self, m, a, b, ws, out):
         self.rt.check(self.lib.vmp_lda_dot(self.ctx, m, ptr(a), ptr(b), ptr(ws), ptr(out)))
 

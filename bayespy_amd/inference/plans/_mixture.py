@@ -100,16 +100,43 @@ def plates_of_p_reason(X, P):
                 'plates %s and P has plates %s' % (X.plates, P.plates))
 
 
-def match_plate_mixture(nodes, why, spec):
+def batch_multiplier(Z):
+    """The factor on the row axis of ``Z`` (the mini-batch stands for that many times its rows)."""
+    m = tuple(np.ravel(Z.plates_multiplier))
+    return float(m[0]) if m else 1.0
+
+
+def batch_reason(X, Z, globals_):
+    """What is wrong with the plate multipliers of a block under mini-batches (a reason), or None:
+    ``Z`` and ``X`` carry one and the same positive factor on the row axis and nothing else does."""
+    if any(any(m != 1 for m in n.plates_multiplier) for n in globals_):
+        return ('a global node (%s) carries a plates_multiplier; only the mini-batch plate of Z and '
+                'the observed node may' % ', '.join(
+                    n.name or '<unnamed>' for n in globals_
+                    if any(m != 1 for m in n.plates_multiplier)))
+    mz, mx = tuple(np.ravel(Z.plates_multiplier)), tuple(np.ravel(X.plates_multiplier))
+    if any(m != 1 for m in mz[1:]) or any(m != 1 for m in mx[1:]):
+        return ('a plates_multiplier on an axis other than the rows: %s on Z, %s on the observed '
+                'node' % (mz, mx))
+    if not mz or not mx or not (mz[0] > 0 and mx[0] > 0) or mz[0] != mx[0]:
+        return ('the plates_multiplier of Z / the observed node is not one positive factor on the '
+                'row axis: %s, %s' % (mz, mx))
+    return None
+
+
+def match_plate_mixture(nodes, why, spec, batches=False):
     """The roles of the first Mixture among ``nodes`` that the block of ``spec`` takes, or None;
-    the reason of every one it looks at and declines goes to ``why`` (a list, or None)."""
+    the reason of every one it looks at and declines goes to ``why`` (a list, or None).
+    ``batches``: the form under stochastic VI (_mixture_svi.py), which differs in the check of the
+    plate multipliers and in the label of its reasons."""
+    label = spec.label + (' (stochastic VI)' if batches else '')
     for X in nodes:
         if not isinstance(X, Mixture) or not spec.takes(X):
             continue
 
         def no(msg, X=X):
             if why is not None:
-                why.append('%s, observed node %s: %s' % (spec.label, X.name or '<unnamed>', msg))
+                why.append('%s, observed node %s: %s' % (label, X.name or '<unnamed>', msg))
         msg = spec.first(X) if spec.first is not None else None
         if msg is not None:
             no(msg)
@@ -127,7 +154,12 @@ def match_plate_mixture(nodes, why, spec):
         below = (Z,) + params + (W,)
         if not all(any(n is m for m in nodes) for n in (X,) + below):
             continue
-        if any(any(m != 1 for m in n.plates_multiplier) for n in (X,) + below):
+        if batches:
+            msg = batch_reason(X, Z, params + (W,))
+            if msg is not None:
+                no(msg)
+                continue
+        elif any(any(m != 1 for m in n.plates_multiplier) for n in (X,) + below):
             no('plates_multiplier (mini-batches) goes through the generic engine')
             continue
         if any(getattr(n, '_shard_axis', None) is not None for n in (X,) + below):
@@ -259,6 +291,24 @@ class PlateMixturePlan:
         else:
             self.maskd = torch.from_numpy(np.ascontiguousarray(
                 np.asarray(m, dtype=bool).reshape(self.N, self.D).astype(np.uint8))).to(rt.device)
+
+    def _repack(self):
+        """New observations of the same shape: the mask and the pack."""
+        self._upload_mask()
+        self._pack()
+
+    def _adopt_form(self):
+        """The form of the pass for the packed data, where a block has more than one."""
+
+    def _set_form(self):
+        """... and, when it changes, the tables of the last ``Z`` update formed again in it."""
+
+    def _restate(self):
+        """New observations: packed again, then the statistics of the present ``Z`` state on
+        them."""
+        self._repack()
+        self._set_form()
+        self._run_pass()
 
     def _labels_from_init(self):
         """``labels``: the fixed labels of an initialised ``Z`` (device, int32), or None: its

@@ -43,6 +43,7 @@ import numpy as np
 
 from . import _delta
 from ._dirichlet import DirichletKernels, prior_table
+from ._mixture_svi import MixtureSVI
 from ._mixture import (MixtureSpec, PlateMixturePlan, _p, _takes_mask, full_mask_reason,
                        match_plate_mixture, observed_tensor, plates_of_p_reason)
 
@@ -194,21 +195,21 @@ class BinomialMixturePlan(PlateMixturePlan):
     def _form(self):
         return 1 if self.trials_constant and self.n_hidden == 0 else 0
 
+    def _adopt_form(self):
+        self.one_plane = self._form()
+
     def _set_form(self):
         """The form of the pass for the packed data; when it changes, the tables of the last ``Z``
         update are formed again for the new one."""
-        form = self._form()
+        form = self.one_plane
+        self._adopt_form()
         if form != self.one_plane:
-            self.one_plane = form
             self._tables(self.elog_p_used if self._used else None, self.elog_r_used)
 
     def _materialize(self):
         if self._ready:
             if self._stale:
-                self._upload_mask()
-                self._pack()
-                self._set_form()
-                self._run_pass()
+                self._restate()
             return
         self._delta = _delta.delta_roles(self.roles)
         rt, k = self.rt, self.kernels
@@ -329,3 +330,28 @@ class BinomialMixturePlan(PlateMixturePlan):
     # -- persistence -----------------------------------------------------------------------------------
     _SAVED = ('alpha_p', 'elog_p', 'elog_p_used', 'alpha_r', 'elog_r', 'elog_r_used', 'l1', 'l0',
               'c', 'cfold', 'S', 'T', 'Nk', 'counts', 'scal')
+
+
+class BinomialMixtureSVIPlan(MixtureSVI, BinomialMixturePlan):
+    """The block under stochastic variational inference (_mixture_svi.py): ``Z`` and ``X`` hold a
+    mini-batch that stands for ``m`` times as many rows (``plates_multiplier``), every step
+    re-observes ``X`` -- the device state stays -- and updates ``Z`` (one pack, one pass), and
+    ``gradient_step`` moves P and R along their natural gradients in one launch.  Opt-in:
+    ``VB(..., engine='fused+batches')`` (everything of ``engine='fused'`` plus these forms),
+    tried after ``BinomialMixturePlan``."""
+
+    KIND, PARAM = 'binm_svi', 'P'
+
+    @staticmethod
+    def describe():
+        return ('the model of the fused binomial-mixture block with plates_multiplier=(m, 1) on Z (mini-batches: one '
+                'positive factor on the row axis of Z and X, none on P or R)')
+
+    @staticmethod
+    def match(nodes, why=None):
+        return match_plate_mixture(nodes, why, _SPEC, batches=True)
+
+    def _step_table(self):
+        DK = self.D * self.K
+        return dict(kind=0, rows=DK, cols=2, rs=2, cs=1, prior=self.prior_p, prior_b=None,
+                    stat=self.counts, cnt=None, per_element=0, par=self.alpha_p, mom=self.elog_p)

@@ -42,6 +42,7 @@ import numpy as np
 
 from . import _delta
 from ._dirichlet import DirichletKernels, prior_table
+from ._mixture_svi import MixtureSVI
 from ._mixture import (MixtureSpec, PlateMixturePlan, _p, _takes_mask, full_mask_reason,
                        match_plate_mixture, observed_tensor, plates_of_p_reason)
 
@@ -185,9 +186,7 @@ class BernoulliMixturePlan(PlateMixturePlan):
     def _materialize(self):
         if self._ready:
             if self._stale:
-                self._upload_mask()
-                self._pack()
-                self._run_pass()
+                self._restate()
             return
         self._delta = _delta.delta_roles(self.roles)
         rt, k = self.rt, self.kernels
@@ -306,3 +305,28 @@ class BernoulliMixturePlan(PlateMixturePlan):
 
     def _saved(self):
         return self._SAVED + (('M', 'l0') if self.maskd is not None else ())
+
+
+class BernoulliMixtureSVIPlan(MixtureSVI, BernoulliMixturePlan):
+    """The block under stochastic variational inference (_mixture_svi.py): ``Z`` and ``X`` hold a
+    mini-batch that stands for ``m`` times as many rows (``plates_multiplier``), every step
+    re-observes ``X`` -- the device state stays -- and updates ``Z`` (one pack, one pass), and
+    ``gradient_step`` moves P and R along their natural gradients in one launch.  Opt-in:
+    ``VB(..., engine='fused+batches')`` (everything of ``engine='fused'`` plus these forms),
+    tried after ``BernoulliMixturePlan``."""
+
+    KIND, PARAM = 'bmm_svi', 'P'
+
+    @staticmethod
+    def describe():
+        return ('the model of the fused Bernoulli-mixture block with plates_multiplier=(m, 1) on Z (mini-batches: one '
+                'positive factor on the row axis of Z and X, none on P or R)')
+
+    @staticmethod
+    def match(nodes, why=None):
+        return match_plate_mixture(nodes, why, _SPEC, batches=True)
+
+    def _step_table(self):
+        DK = self.D * self.K
+        return dict(kind=0, rows=DK, cols=2, rs=2, cs=1, prior=self.prior_p, prior_b=None,
+                    stat=self.counts, cnt=None, per_element=0, par=self.alpha_p, mom=self.elog_p)

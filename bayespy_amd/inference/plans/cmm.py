@@ -42,6 +42,7 @@ import numpy as np
 
 from . import _delta
 from ._dirichlet import DirichletKernels, prior_table
+from ._mixture_svi import MixtureSVI
 from ._mixture import (MixtureSpec, PlateMixturePlan, _p, _takes_mask, full_mask_reason,
                        match_plate_mixture, observed_tensor, plates_of_p_reason)
 
@@ -170,9 +171,7 @@ class CategoricalMixturePlan(PlateMixturePlan):
     def _materialize(self):
         if self._ready:
             if self._stale:
-                self._upload_mask()
-                self._pack()
-                self._run_pass()
+                self._restate()
             return
         self._delta = _delta.delta_roles(self.roles)
         rt, k = self.rt, self.kernels
@@ -283,3 +282,28 @@ class CategoricalMixturePlan(PlateMixturePlan):
 
     # -- persistence -----------------------------------------------------------------------------------
     _SAVED = ('alpha_p', 'elog_p', 'alpha_r', 'elog_r', 'L', 'c', 'S', 'Nk', 'scal')
+
+
+class CategoricalMixtureSVIPlan(MixtureSVI, CategoricalMixturePlan):
+    """The block under stochastic variational inference (_mixture_svi.py): ``Z`` and ``X`` hold a
+    mini-batch that stands for ``m`` times as many rows (``plates_multiplier``), every step
+    re-observes ``X`` -- the device state stays -- and updates ``Z`` (one pack, one pass), and
+    ``gradient_step`` moves P and R along their natural gradients in one launch.  Opt-in:
+    ``VB(..., engine='fused+batches')`` (everything of ``engine='fused'`` plus these forms),
+    tried after ``CategoricalMixturePlan``."""
+
+    KIND, PARAM = 'cmm_svi', 'P'
+
+    @staticmethod
+    def describe():
+        return ('the model of the fused categorical-mixture block with plates_multiplier=(m, 1) on Z (mini-batches: one '
+                'positive factor on the row axis of Z and X, none on P or R)')
+
+    @staticmethod
+    def match(nodes, why=None):
+        return match_plate_mixture(nodes, why, _SPEC, batches=True)
+
+    def _step_table(self):
+        DK = self.D * self.K      # the category-major table: element (dk, m) at dk + m D K
+        return dict(kind=0, rows=DK, cols=self.M, rs=1, cs=DK, prior=self.prior_p, prior_b=None,
+                    stat=self.S, cnt=None, per_element=0, par=self.alpha_p, mom=self.elog_p)

@@ -30,7 +30,9 @@ import numpy as np
 
 from . import _delta
 from ._dirichlet import DirichletKernels, prior_table
-from ._mixture import PlateMixturePlan, _mask_shape, _p, cluster_plate_reason, observed_tensor
+from ._mixture_svi import MixtureSVI
+from ._mixture import (PlateMixturePlan, _mask_shape, _p, batch_reason, cluster_plate_reason,
+                       observed_tensor)
 from .pmm import _largest_host_count
 
 from ... import _lib
@@ -100,9 +102,11 @@ def row_trials(X):
         return None
 
 
-def match_multinomial_mixture(nodes, why=None):
+def match_multinomial_mixture(nodes, why=None, batches=False):
     """The roles of the first Mixture of Multinomial among ``nodes`` that the block takes, or None;
-    the reason of every one it looks at and declines goes to ``why`` (a list, or None)."""
+    the reason of every one it looks at and declines goes to ``why`` (a list, or None).
+    ``batches``: the form under stochastic VI, as in ``match_plate_mixture``."""
+    label = LABEL + (' (stochastic VI)' if batches else '')
     for X in nodes:
         if not isinstance(X, Mixture) or X.node_class is not Multinomial \
                 or isinstance(X.parents[0], CategoricalMarkovChainToCategorical):
@@ -110,7 +114,7 @@ def match_multinomial_mixture(nodes, why=None):
 
         def no(msg, X=X):
             if why is not None:
-                why.append('%s, observed node %s: %s' % (LABEL, X.name or '<unnamed>', msg))
+                why.append('%s, observed node %s: %s' % (label, X.name or '<unnamed>', msg))
         if len(X.parents) != 2 or type(X.parents[0]) is not Categorical \
                 or type(X.parents[0].parents[0]) is not Dirichlet \
                 or type(X.parents[1]) is not Dirichlet:
@@ -121,7 +125,12 @@ def match_multinomial_mixture(nodes, why=None):
         below = (Z, P, R)
         if not all(any(n is m for m in nodes) for n in (X,) + below):
             continue
-        if any(any(m != 1 for m in n.plates_multiplier) for n in (X,) + below):
+        if batches:
+            msg = batch_reason(X, Z, (P, R))
+            if msg is not None:
+                no(msg)
+                continue
+        elif any(any(m != 1 for m in n.plates_multiplier) for n in (X,) + below):
             no('plates_multiplier (mini-batches) goes through the generic engine')
             continue
         if any(getattr(n, '_shard_axis', None) is not None for n in (X,) + below):
@@ -232,8 +241,7 @@ class MultinomialMixturePlan(PlateMixturePlan):
     def _materialize(self):
         if self._ready:
             if self._stale:
-                self._pack()
-                self._run_pass()
+                self._restate()
             return
         self._delta = _delta.delta_roles(self.roles)
         rt, k = self.rt, self.kernels
@@ -341,3 +349,28 @@ class MultinomialMixturePlan(PlateMixturePlan):
 
     # -- persistence -----------------------------------------------------------------------------------
     _SAVED = ('alpha_p', 'elog_p', 'alpha_r', 'elog_r', 'L', 'c', 'S', 'Nk', 'scal')
+
+
+class MultinomialMixtureSVIPlan(MixtureSVI, MultinomialMixturePlan):
+    """The block under stochastic variational inference (_mixture_svi.py): ``Z`` and ``X`` hold a
+    mini-batch that stands for ``m`` times as many rows (``plates_multiplier``), every step
+    re-observes ``X`` -- the device state stays -- and updates ``Z`` (one pack, one pass), and
+    ``gradient_step`` moves P and R along their natural gradients in one launch.  Opt-in:
+    ``VB(..., engine='fused+batches')`` (everything of ``engine='fused'`` plus these forms),
+    tried after ``MultinomialMixturePlan``."""
+
+    KIND, PARAM = 'mmm_svi', 'P'
+
+    @staticmethod
+    def describe():
+        return ('the model of the fused multinomial-mixture block with plates_multiplier=(m,) on Z (mini-batches: one '
+                'positive factor on the row axis of Z and X, none on P or R)')
+
+    @staticmethod
+    def match(nodes, why=None):
+        return match_multinomial_mixture(nodes, why, batches=True)
+
+    def _step_table(self):
+        return dict(kind=0, rows=self.K, cols=self.M, rs=self.M, cs=1, prior=self.prior_p,
+                    prior_b=None, stat=self.S, cnt=None, per_element=0, par=self.alpha_p,
+                    mom=self.elog_p)

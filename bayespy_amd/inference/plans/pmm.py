@@ -39,6 +39,7 @@ import numpy as np
 
 from . import _delta
 from ._dirichlet import DirichletKernels, prior_table
+from ._mixture_svi import MixtureSVI
 from ._mixture import (MixtureSpec, PlateMixturePlan, _p, _takes_mask, cluster_plate_reason,
                        full_mask_reason, match_plate_mixture, observed_tensor)
 
@@ -195,12 +196,15 @@ class PoissonMixturePlan(PlateMixturePlan):
         self.n_observed, self.n_hidden = int(n[0]), int(n[1])
         self._stale = False
 
+    def _adopt_form(self):
+        self.hidden = 1 if self.n_hidden > 0 else 0
+
     def _set_form(self):
         """The form of the pass for the packed data; when it changes, the tables of the last ``Z``
         update are formed again in the new one."""
-        hidden = 1 if self.n_hidden > 0 else 0
+        hidden = self.hidden
+        self._adopt_form()
         if hidden != self.hidden:
-            self.hidden = hidden
             self._tables(self.lam_mom_used if self._used else None, self.elog_r_used)
 
     def _const(self, i, what):
@@ -212,10 +216,7 @@ class PoissonMixturePlan(PlateMixturePlan):
     def _materialize(self):
         if self._ready:
             if self._stale:
-                self._upload_mask()
-                self._pack()
-                self._set_form()
-                self._run_pass()
+                self._restate()
             return
         self._delta = _delta.delta_roles(self.roles)
         rt, k = self.rt, self.kernels
@@ -347,3 +348,29 @@ class PoissonMixturePlan(PlateMixturePlan):
     # -- persistence -----------------------------------------------------------------------------------
     _SAVED = ('lam_par', 'lam_mom', 'lam_mom_used', 'alpha_r', 'elog_r', 'elog_r_used', 'l', 'lb',
               'c', 'S', 'M', 'Nk', 'scal')
+
+
+class PoissonMixtureSVIPlan(MixtureSVI, PoissonMixturePlan):
+    """The block under stochastic variational inference (_mixture_svi.py): ``Z`` and ``X`` hold a
+    mini-batch that stands for ``m`` times as many rows (``plates_multiplier``), every step
+    re-observes ``X`` -- the device state stays -- and updates ``Z`` (one pack, one pass), and
+    ``gradient_step`` moves lam and R along their natural gradients in one launch.  Opt-in:
+    ``VB(..., engine='fused+batches')`` (everything of ``engine='fused'`` plus these forms),
+    tried after ``PoissonMixturePlan``."""
+
+    KIND, PARAM = 'pmm_svi', 'lam'
+
+    @staticmethod
+    def describe():
+        return ('the model of the fused Poisson-mixture block with plates_multiplier=(m, 1) on Z (mini-batches: one '
+                'positive factor on the row axis of Z and X, none on lam or R)')
+
+    @staticmethod
+    def match(nodes, why=None):
+        return match_plate_mixture(nodes, why, _SPEC, batches=True)
+
+    def _step_table(self):
+        # the Gamma pairs; with hidden entries M takes the place of N_k
+        return dict(kind=1, rows=self.D * self.K, cols=2, rs=2, cs=1, prior=self.a0,
+                    prior_b=self.b0, stat=self.S, cnt=self.M if self.hidden else self.Nk,
+                    per_element=self.hidden, par=self.lam_par, mom=self.lam_mom)

@@ -46,13 +46,17 @@ class Binomial(Stochastic):
             raise ValueError('Plates of the parents do not broadcast to plates %s' % (given,))
 
     def _check_value_shape(self, x):
-        x = np.asarray(x)
+        tensor = hasattr(x, 'is_cuda')      # a device tensor: its values are checked where it is read
+        x = x if tensor else np.asarray(x)
         try:
             ok = broadcasted_shape(x.shape, self.plates) == self.plates
         except ValueError:
             ok = False
         if not ok:
-            raise ValueError('Counts of shape %s do not match plates %s' % (x.shape, self.plates))
+            raise ValueError('Counts of shape %s do not match plates %s'
+                             % (tuple(x.shape), self.plates))
+        if tensor:
+            return
         if np.any(x != np.round(x)):
             raise ValueError("Counts must be integer")
         if np.any(x < 0) or np.any(x > self.trials):

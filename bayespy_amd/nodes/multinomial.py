@@ -44,12 +44,15 @@ class Multinomial(Stochastic):
             raise ValueError('Plates of the parents do not broadcast to plates %s' % (given,))
 
     def _check_value_shape(self, x):
-        x = np.asarray(x)
+        tensor = hasattr(x, 'is_cuda')      # a device tensor: its values are checked where it is read
+        x = x if tensor else np.asarray(x)
         shape = tuple(x.shape)
         if len(shape) < 1 or shape[-1] != self.categories or \
                 broadcasted_shape(shape[:-1], self.plates) != self.plates:
             raise ValueError('Counts of shape %s do not match plates %s and %d categories'
                              % (shape, self.plates, self.categories))
+        if tensor:
+            return
         if np.any(x != np.round(x)):
             raise ValueError("Counts must be integers")
         if np.any(x < 0):

@@ -1394,6 +1394,37 @@ int32_t vmp_binm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, int32_t one
                       double *ws, double *S, double *T, double *Nk, double *counts, double *scal,
                       double *r_out);
 
+/* Stochastic VI on the count-mixture blocks: the global half of a step in one launch (details:
+ * bayespy_amd/csrc/vmp_mix_svi.hip).  The parameter table of the block and the Dirichlet row of the
+ * mixing weights move by phi <- phi + scale (phi* - phi) with phi* = prior + mult * statistic; both
+ * optima come from the statistics present at entry.  `nodes` is a bit set: 1 = the table, 2 = the
+ * weights (K <= 64 contiguous columns: prior_r, Nk (null: the prior), alpha_r, elog_r); what a node
+ * that is not named owns is neither read nor written.
+ *   kind 0: Dirichlet rows in the addressing of vmp_lda_dirichlet (element (r, c) at r * row_stride +
+ *     c * col_stride; cols <= 1024, rows <= 65536, rows * cols <= 2^21): par = alpha, mom = <log>,
+ *     stat = the counts (null: the prior); prior_b, cnt, per_element are not used.
+ *   kind 1: Gamma pairs in the layout of vmp_pmm_update (cols = 2, rows <= 65536): prior = a0,
+ *     prior_b = b0, stat = S, cnt = N_k (per_element 0: rows = D K walked as (D, K), element e reads
+ *     cnt[e % K]) or M (per_element 1); a <- a + scale (a0 + mult S - a), b likewise.
+ *   scale == 1 does not read the old parameters (they may be NaN) and, with mult == 1, leaves the
+ *   parameters and moments of vmp_lda_dirichlet / vmp_pmm_update bit for bit; scale == 0 leaves the
+ *   parameters as they are and forms moments and bound again.
+ *   bound[0] = <log p> - <log q> of the table (0 for rows == 0), bound[1] that of the weights, each
+ *   written only when its node is named.  No floating-point atomics: the workgroups leave partials in
+ *   ws (vmp_mix_natural_step_workspace doubles, host only; its last word is the ticket, cleared on the
+ *   stream ahead of the launch) and the one that finishes last adds them in index order; the bits of every output depend on the inputs and the shape only.
+ *   mult <= 0, a NaN mult or scale, a null required pointer, a negative size, nodes outside 1..3:
+ *   VMP_ERR_INVALID, nothing is launched.  K > 64 or a shape beyond the limits above:
+ *   VMP_ERR_UNSUPPORTED. */
+int32_t vmp_mix_natural_step_workspace(int32_t kind, int64_t rows, int64_t cols, int32_t K,
+                                       int64_t *workspace_doubles);
+int32_t vmp_mix_natural_step(vmp_ctx *ctx, int32_t kind, int32_t nodes, int64_t rows, int64_t cols,
+                             int64_t row_stride, int64_t col_stride, const double *prior,
+                             const double *prior_b, const double *stat, const double *cnt,
+                             int32_t per_element, double *par, double *mom, int32_t K,
+                             const double *prior_r, const double *Nk, double *alpha_r,
+                             double *elog_r, double mult, double scale, double *ws, double *bound);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
