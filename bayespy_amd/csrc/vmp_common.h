@@ -60,6 +60,10 @@ struct vmp_ctx {
     // launches of that kernel so far
     unsigned int *sweep_tickets;
     int64_t sweep_mid_launches;
+    // wall_clock64 stamps of those launches, VMP_SWEEP_NSTAMP words per sweep of the latest chunk:
+    // allocated and written only while the tune key "pca_sweep_stamps" is on (vmp_pca_sweep_stamps)
+    unsigned long long *sweep_stamps;
+    int sweep_stamp_rows;
     // streams / events of the pipelined plate pass of the missing-data PCA block (vmp_mpca.hip)
     hipStream_t ms[3];
     hipEvent_t me[VMP_NME];
@@ -79,6 +83,9 @@ struct vmp_ctx {
     void *queue;
     char err[512];
 };
+
+// words per launch of the stamped one-launch sweep (vmp_ctx::sweep_stamps)
+enum { VMP_SWEEP_NSTAMP = VMP_PCA_SWEEP_NSTAMP };
 
 // control block of vmp_pca_sweeps (vmp_ctx::sweep_ctl), in doubles
 enum { VMP_SWEEP_STOP = 0, VMP_SWEEP_L = 1, VMP_SWEEP_EXECUTED = 2, VMP_SWEEP_SKIPPED = 3,
@@ -109,12 +116,15 @@ int32_t vmp_pca_launch_sweep_tail(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_
                                   const vmp_sweep_tail &t);
 
 // sweeps 1 .. n-1 of a chunk: Gram statistics, tail and the next sweep's head in ONE launch of DP / 8
-// workgroups (pca_sweep_mid_kernel, vmp_pca_small.hip); `ticket` is the sweep's own zeroed word
+// workgroups (pca_sweep_mid_kernel, vmp_pca_small.hip); `ticket` is the sweep's own zeroed word,
+// `wide` selects the wide tail and head of phase B, `stamps` (null: none) the stamped build and its row
 int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                                  double a0t, double b0t, double a0a, double b0a, double *state,
-                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket);
+                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket, int32_t wide,
+                                 unsigned long long *stamps);
 // the Gram statistics of that kernel alone: Syx rows into the state, DP / 8 partial blocks into P
-int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P);
+int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P,
+                                 int32_t wide);
 
 // forms the pending S = [G A^T; A G A^T] of the Gram-form PCA block, if any (vmp_pca.hip)
 int32_t vmp_pca_ensure_gram(vmp_ctx *ctx);

@@ -99,6 +99,8 @@ int32_t vmp_ctx_create(int32_t device, void *stream, vmp_ctx **out)
     ctx->sweeps_enqueued = 0;
     ctx->sweep_tickets = nullptr;
     ctx->sweep_mid_launches = 0;
+    ctx->sweep_stamps = nullptr;
+    ctx->sweep_stamp_rows = 0;
     for (int i = 0; i < 3; ++i) ctx->ms[i] = nullptr;
     for (int i = 0; i < VMP_NME; ++i) ctx->me[i] = nullptr;
     ctx->comm = nullptr;
@@ -134,6 +136,7 @@ int32_t vmp_ctx_destroy(vmp_ctx *ctx)
         if (ctx->me[i]) (void)hipEventDestroy(ctx->me[i]);
     if (ctx->sweep_ctl) (void)hipFree(ctx->sweep_ctl);       // (waits for the device itself)
     if (ctx->sweep_tickets) (void)hipFree(ctx->sweep_tickets);
+    if (ctx->sweep_stamps) (void)hipFree(ctx->sweep_stamps);
     if (ctx->ev_xfork) (void)hipEventDestroy(ctx->ev_xfork);
     if (ctx->ev_xdone) (void)hipEventDestroy(ctx->ev_xdone);
     for (int i = 0; i < 2; ++i)

@@ -1342,8 +1342,21 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
     // with the mid kernel's LDS would not be placed -- the pass, the Gram statistics and the tail:
     // n + 2 launches instead of 3 n.  "pca_sweep_ticket" = 0 (VMP_PCA_SWEEP_TICKET=0): three per sweep;
     // so does a state block that is not 16-byte aligned (the mid kernel loads it 16 bytes at a time).
+    // "pca_sweep_wide" = 0 (VMP_PCA_SWEEP_WIDE=0): phase B of the mid kernel runs the tail and head
+    // bodies of the three-launch sweep instead of the wide ones (the same bits).  "pca_sweep_stamps" = 1:
+    // the stamped build of the mid kernel, a measurement (tools/sweep_stamps.py).
     const bool ticket = n > 1 && ((uintptr_t)state % 16) == 0 &&
                         vmp_tune_get("pca_sweep_ticket", env_int("VMP_PCA_SWEEP_TICKET", 1, 0, 1));
+    const int wide = vmp_tune_get("pca_sweep_wide", env_int("VMP_PCA_SWEEP_WIDE", 1, 0, 1));
+    const bool stamps = ticket && vmp_tune_get("pca_sweep_stamps", 0);
+    if (stamps) {
+        const size_t bytes = (size_t)VMP_PCA_MAX_SWEEPS * VMP_SWEEP_NSTAMP * sizeof(unsigned long long);
+        if (!ctx->sweep_stamps) VMP_HIP_CHECK(ctx, hipMalloc(&ctx->sweep_stamps, bytes));
+        VMP_HIP_CHECK(ctx, hipMemsetAsync(ctx->sweep_stamps, 0,
+                                          (size_t)(n - 1) * VMP_SWEEP_NSTAMP * sizeof(unsigned long long),
+                                          ctx->stream));
+        ctx->sweep_stamp_rows = n - 1;
+    }
     if (ticket) {
         if (!ctx->sweep_tickets)
             VMP_HIP_CHECK(ctx, hipMalloc(&ctx->sweep_tickets,
@@ -1374,7 +1387,9 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
         if (ticket && !last) {
             // Gram statistics, tail and the head of sweep i + 1 in one launch
             rc = vmp_pca_launch_sweep_mid(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
-                                          b0_alpha, state, P, t, ctx->sweep_tickets + i);
+                                          b0_alpha, state, P, t, ctx->sweep_tickets + i, wide,
+                                          stamps ? ctx->sweep_stamps + (size_t)i * VMP_SWEEP_NSTAMP
+                                                 : nullptr);
             if (rc != VMP_OK) return rc;
             ctx->sweep_mid_launches += 1;
         } else {
@@ -1410,6 +1425,25 @@ int32_t vmp_pca_sweep_mid_count(vmp_ctx *ctx, int64_t *launches)
     return VMP_OK;
 }
 
+int32_t vmp_pca_sweep_stamps(vmp_ctx *ctx, uint64_t *out, int32_t max_rows, int32_t *rows,
+                             int32_t *allocated)
+{
+    VMP_REQUIRE(ctx, ctx && rows && max_rows >= 0 && (out || max_rows == 0), VMP_ERR_INVALID,
+                "null argument");
+    if (allocated) *allocated = ctx->sweep_stamps ? 1 : 0;
+    *rows = 0;
+    if (!ctx->sweep_stamps) return VMP_OK;
+    const int n = ctx->sweep_stamp_rows < max_rows ? ctx->sweep_stamp_rows : max_rows;
+    if (n > 0) {
+        VMP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        VMP_HIP_CHECK(ctx, hipMemcpy(out, ctx->sweep_stamps,
+                                     (size_t)n * VMP_SWEEP_NSTAMP * sizeof(unsigned long long),
+                                     hipMemcpyDeviceToHost));
+    }
+    *rows = n;
+    return VMP_OK;
+}
+
 int32_t vmp_pca_gram_stats_form(vmp_ctx *ctx, int32_t D, int32_t K, double *state, void *workspace,
                                 int32_t form)
 {
@@ -1419,7 +1453,8 @@ int32_t vmp_pca_gram_stats_form(vmp_ctx *ctx, int32_t D, int32_t K, double *stat
     VMP_REQUIRE(ctx, rc == VMP_OK, rc, "unsupported dims D=%d K=%d", D, K);
     double *P = reinterpret_cast<double *>(workspace);
     if (form == 0) return run_gram_stats(ctx, L, D, K, state, P, ctx->stream, nullptr, false);
-    return vmp_pca_launch_gram_fast(ctx, D, K, state, P);
+    VMP_REQUIRE(ctx, form == 1 || form == 2, VMP_ERR_INVALID, "form %d (0, 1 or 2)", form);
+    return vmp_pca_launch_gram_fast(ctx, D, K, state, P, form == 2);
 }
 
 int32_t vmp_pca_last_pass_ms(vmp_ctx *ctx, double *ms_pass, double *ms_reduce)

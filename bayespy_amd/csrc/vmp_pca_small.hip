@@ -113,8 +113,16 @@ __device__ void gj_inverse(double *M, int n, double *logdet, int *bad)
 // W / X-prepare kernel per inverse when it runs alone, and 70+ us each beside the streaming grid of
 // the plate pass, whose wavefronts keep the CU's LDS pipeline busy (measured with wall_clock64
 // stamps at N = 1.25e6, the shard one of 8 ranks holds at the headline size).
-template <int KP>
-__device__ __forceinline__ void sweep_inverse(double *M, int n, double *logdet, int *bad)
+// `side` is what wavefronts 1 .. 3 do meanwhile, between the two barriers.  Only pca_head_wide passes
+// one.  The default, no_side, is empty, so that instantiation -- the one pca_head_body, the tails and
+// every kernel that runs beside the pass use -- is the code from before the parameter existed (its
+// kernels' register and LDS figures are unchanged).
+struct no_side {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <int KP, class SIDE = no_side>
+__device__ __forceinline__ void sweep_inverse(double *M, int n, double *logdet, int *bad,
+                                              const SIDE &side = SIDE())
 {
     static_assert(KP == 16 || KP == 32, "one 32 x 32 register tile set");
     constexpr int LDM = KP + 1;
@@ -150,9 +158,32 @@ __device__ __forceinline__ void sweep_inverse(double *M, int n, double *logdet, 
             *logdet = vmp_sweep::sweep_logdet(prod, ld);
             if (isbad) *bad = 1;
         }
+    } else {
+        side();
     }
     __syncthreads();
 }
+
+// wall_clock64 stamps of the one-launch sweep (tune key "pca_sweep_stamps", tools/sweep_stamps.py):
+// thread 0 keeps them in LDS and the workgroup that runs phase B copies them out at its end.  The
+// default kernels are instantiated with stamps_off, which is empty.
+enum { SP_ENTRY = 0, SP_LDS_FILLED, SP_SYX, SP_PXX, SP_TICKET, SP_ACQUIRE,
+       SP_T_PARTIALS, SP_T_LOADS, SP_T_BLOCKSUMS, SP_T_TAU_ALPHA, SP_T_BOUND, SP_T_RING,
+       SP_H_LAMBDA, SP_H_INV1, SP_H_W, SP_H_SWW, SP_H_INV2, SP_H_A, SP_COUNT };
+static_assert(SP_COUNT <= VMP_SWEEP_NSTAMP, "stamp row length");
+struct stamps_off {
+    __device__ __forceinline__ void operator()(int) const {}
+    __device__ __forceinline__ void drain() const {}
+};
+struct stamps_on {
+    unsigned long long *t;      // LDS, VMP_SWEEP_NSTAMP words
+    __device__ __forceinline__ void operator()(int i) const
+    {
+        if (threadIdx.x == 0) t[i] = wall_clock64();
+    }
+    // before a stamp that stands for "stored": the thread's stores have left
+    __device__ __forceinline__ void drain() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+};
 
 template <int KP, int NTQ>
 struct small_lds {
@@ -525,9 +556,9 @@ __device__ __forceinline__ v4f64 wave_tile_mma_acc(v4f64 acc, const double *As, 
 // The body is shared with pca_sweep_mid_kernel below, where the tail of the previous sweep has just
 // run in the same workgroup: HANDOFF = what that tail holds in LDS -- Cov_X in M, sum <x><x>^T in T,
 // <alpha> in alm and <tau> in tau_in, the very values it stored to the state -- is not loaded again.
-template <int KP, bool HANDOFF>
+template <int KP, bool HANDOFF, class STAMP = stamps_off>
 __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, double *Mh, double *Th,
-                                              double *almh, double tau_in)
+                                              double *almh, double tau_in, const STAMP &stamp = STAMP())
 {
     constexpr int LDM = KP + 1, E = KP * KP / NTF, RB = 32;
     constexpr int OWN = HANDOFF ? 1 : KP * LDM;
@@ -593,9 +624,11 @@ __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, d
             M[(e / KP) * LDM + (e % KP)] = lam[m];
         }
     }
+    stamp(SP_H_LAMBDA);
     asm volatile("" : "+v"(tid));     // nothing derived from the thread index stays live across the sweep
     sweep_inverse<KP>(M, K, &logdet, &bad);
     asm volatile("" : "+v"(tid));
+    stamp(SP_H_INV1);
 #pragma unroll
     for (int m = 0; m < E; ++m) {
         const int e = tid + m * NTF;
@@ -677,6 +710,7 @@ __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, d
         }
     }
     __syncthreads();
+    stamp(SP_H_SWW);     // (W and Sww share the row-block loop of this body: no stamp between them)
     // ---- X, replicated half: Lambda_X = x_prec I + <tau> Sww ; A = <tau> Cov_X W^T --------
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -692,6 +726,7 @@ __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, d
     asm volatile("" : "+v"(tid));
     sweep_inverse<KP>(M, K, &logdet, &bad);
     asm volatile("" : "+v"(tid));
+    stamp(SP_H_INV2);
     w = tid >> 6, l15 = tid & 15, l4 = (tid & 63) >> 4;
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -741,6 +776,8 @@ __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, d
         st[L.off_scal + 1] = logdet;
         if (bad) st[L.off_scal + 3] = (double)VMP_ERR_NOT_POSDEF;
     }
+    stamp.drain();
+    stamp(SP_H_A);
 }
 
 template <int KP>
@@ -778,10 +815,16 @@ struct alignas(16) tail_lds {
 };
 // (a multiple of 16 bytes: the dynamic LDS behind it is accessed 16 bytes at a time)
 static_assert(sizeof(tail_lds<16>) % 16 == 0 && sizeof(tail_lds<32>) % 16 == 0, "tail_lds size");
-template <int KP, int MODE>
+// WIDE (pca_sweep_mid_kernel only, where no plate pass shares the CU and the register budget of the
+// placement does not bind): every load of the tail is issued before the partial blocks are added, and
+// the rows of sum y<x>^T go on to the next head in SW (FAST_D x (KP+1) doubles of LDS, columns >= K and
+// rows >= D zero) instead of being loaded a second time there.  Same expressions, same order of sums.
+template <int KP, int MODE, bool WIDE = false, class STAMP = stamps_off>
 __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, const vmp_sweep_tail *sw,
-                                              tail_lds<KP> &s)
+                                              tail_lds<KP> &s, double *SW = nullptr,
+                                              const STAMP &stamp = STAMP())
 {
+    static_assert(!WIDE || MODE == TAIL_SWEEP, "the wide tail is a sweep tail");
     constexpr bool GRAM = (MODE == TAIL_GRAM);
     constexpr int LDM = KP + 1, E = KP * KP / NTF;
     extern __shared__ __align__(16) double gl[];          // GRAM: A (KP x (DP+1)) | G batch (GB x (DP+1)) | S batch (GB x LDM)
@@ -802,7 +845,56 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
     double sxx[E];
 #pragma unroll
     for (int m = 0; m < E; ++m) sxx[m] = 0.0;
-    if constexpr (MODE == TAIL_SWEEP) {
+    // WIDE: <W>, sum y<x>^T, Sww and Cov_X are requested here, ahead of the partial blocks
+    constexpr int NW = WIDE ? FAST_D * KP / NTF : 1;
+    double ww[NW], wy[NW], es0[WIDE ? E : 1], es1[WIDE ? E : 1];
+    if constexpr (WIDE) {
+        const int n = D * KP;
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            const int e = tid + j * NTF;
+            ww[j] = e < n ? st[L.off_W + e] : 0.0;
+            wy[j] = e < n ? st[L.off_S + e] : 0.0;
+        }
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            const int e = tid + m * NTF;
+            const int i = e / KP, j = e % KP;
+            const bool in = (i < K && j < K);
+            es0[m] = in ? st[L.off_Sww + i * KP + j] : 0.0;
+            es1[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
+        }
+    }
+    if constexpr (WIDE) {
+        // sum <x><x>^T = sum_b P[b]: the adds of the loop below in the same order, from ONE batch of
+        // loads (nb <= FAST_D / 8) -- that loop waits for four loads at a time, nb / 4 round trips
+        // in a row for each of the E elements of a thread
+        constexpr int NBM = FAST_D / 8;
+        const int nb = sw->nb, nb4 = nb & ~3;
+        double pv[E][NBM];
+#pragma unroll
+        for (int m = 0; m < E; ++m)
+#pragma unroll
+            for (int b = 0; b < NBM; ++b)
+                pv[m][b] = b < nb ? sw->P[tid + m * NTF + b * (KP * KP)] : 0.0;
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+#pragma unroll
+            for (int b = 0; b < NBM; b += 4)
+                if (b < nb4) {
+                    s0 += pv[m][b];
+                    s1 += pv[m][b + 1];
+                    s2 += pv[m][b + 2];
+                    s3 += pv[m][b + 3];
+                }
+#pragma unroll
+            for (int b = 0; b < NBM; ++b)
+                if (b >= nb4 && b < nb) s0 += pv[m][b];
+            sxx[m] = (s0 + s1) + (s2 + s3);
+            st[L.off_S + L.DP * KP + tid + m * NTF] = sxx[m];
+        }
+    } else if constexpr (MODE == TAIL_SWEEP) {
         // sum <x><x>^T = sum_b P[b] in the order of reduce_partials_kernel (vmp_pca.hip): the same bits
         const int nb = sw->nb;
 #pragma unroll
@@ -822,6 +914,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             st[L.off_S + L.DP * KP + e] = sxx[m];
         }
     }
+    stamp(SP_T_PARTIALS);
     if constexpr (GRAM) {
         const int DP = L.DP, LA = DP + 1;
         double *As = gl, *Gs = As + KP * LA, *Ss = Gs + GB * LA;
@@ -881,8 +974,13 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             const int e = tid + m * NTF;
             const int i = e / KP, j = e % KP;
             const bool in = (i < K && j < K);
-            v0[m] = in ? st[L.off_Sww + i * KP + j] : 0.0;
-            v1[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
+            if constexpr (WIDE) {
+                v0[m] = es0[m];
+                v1[m] = es1[m];
+            } else {
+                v0[m] = in ? st[L.off_Sww + i * KP + j] : 0.0;
+                v1[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
+            }
             if constexpr (MODE != TAIL_PLAIN) v2[m] = in ? sxx[m] : 0.0;
             else v2[m] = in ? st[L.off_S + (L.DP + i) * KP + j] : 0.0;
         }
@@ -901,7 +999,18 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
         }
     }
     // sum(W o Syx): padded entries of W are zero, so the D x KP blocks are walked linearly
-    if constexpr (!GRAM) {
+    if constexpr (WIDE) {
+        // the same products in the same order as the loop below, which runs whole passes of 8 per
+        // thread; the rows go to SW as the head would have loaded them (zero beyond D and K)
+        const int n = D * KP, jn = (n + 8 * NTF - 1) / (8 * NTF) * 8;
+        const int nsw = (D + 31) / 32 * 32 * KP;       // whole 32-row blocks, at most DP rows
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            const int e = tid + j * NTF;
+            if (j < jn) t1 += ww[j] * wy[j];
+            if (e < nsw) SW[(e / KP) * LDM + (e % KP)] = (e < n && e % KP < K) ? wy[j] : 0.0;
+        }
+    } else if constexpr (!GRAM) {
         const int n = D * KP;
 #pragma unroll 1
         for (int e0 = 0; e0 < n; e0 += 8 * NTF) {
@@ -916,7 +1025,9 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             for (int m = 0; m < 8; ++m) t1 += w[m] * y[m];
         }
     }
+    (void)ww; (void)wy; (void)es0; (void)es1;
     __syncthreads();
+    stamp(SP_T_LOADS);
     double t2 = 0.0, trx = 0.0;
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -929,6 +1040,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
     t1 = block_sum<NTF>(t1, red);
     t2 = block_sum<NTF>(t2, red);
     trx = block_sum<NTF>(trx, red);
+    stamp(SP_T_BLOCKSUMS);
     // (dot.py:355 E1 and dot.py:403 E2 collapsed to traces)
     const double resid = sc[4] - 2.0 * t1 + t2;
     // ---- tau (gamma.py:116-148 with the message gaussian.py:2363-2369), alpha -------------
@@ -974,6 +1086,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
     sla = block_sum<NTF>(sla, red);
     saw = block_sum<NTF>(saw, red);
     lal = block_sum<NTF>(lal, red);
+    stamp(SP_T_TAU_ALPHA);
     if (tid == 0) {
         const double tau = sc[2], logtau = sc[3];
         const double Dd = (double)D, Kd = (double)K;
@@ -989,6 +1102,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
         st[L.off_L + 3] = Lt;
         st[L.off_L + 4] = lal;
         st[L.off_L + 5] = LY + LX + LW + Lt + lal;
+        stamp(SP_T_BOUND);
         if constexpr (MODE == TAIL_SWEEP) {
             const double status = sc[7];
             double *slot = sw->slot;
@@ -1015,6 +1129,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             sw->ctl[VMP_SWEEP_L] = Lb;
             sw->ctl[VMP_SWEEP_EXECUTED] += 1.0;
         }
+        stamp(SP_T_RING);
     }
 }
 
@@ -1051,9 +1166,10 @@ __host__ __device__ inline size_t gram_phase_a_lds(int KP, int DP)
     return ((size_t)KP * (DP + 1) + (size_t)GRA * DP + (size_t)GRA * (KP + 1)) * sizeof(double);
 }
 
-template <int KP>
+template <int KP, class STAMP = stamps_off>
 __device__ __forceinline__ void gram_phase_a(const vmp_pca_layout &L, int D, int K, double *st,
-                                             double *P, double *lds, int blk)
+                                             double *P, double *lds, int blk,
+                                             const STAMP &stamp = STAMP())
 {
     constexpr int LDS_S = KP + 1, H = KP / 2, E = KP * KP / NTF;
     const int DP = (int)L.DP, LA = DP + 1;
@@ -1076,6 +1192,7 @@ __device__ __forceinline__ void gram_phase_a(const vmp_pca_layout &L, int D, int
     for (int e = tid; e < GRA * DP2; e += NTF)
         *reinterpret_cast<v2f64 *>(Gs + 2 * e) = *reinterpret_cast<const v2f64 *>(G + 2 * e);
     __syncthreads();
+    stamp(SP_LDS_FILLED);
     // Syx[r][k] = sum_d G[r][d] A[k][d]: rows (ra, ra + 4) x columns (k0, k0 + H) per thread
     if (tid < 4 * H) {
         const int k0 = tid % H, ra = tid / H;
@@ -1105,6 +1222,7 @@ __device__ __forceinline__ void gram_phase_a(const vmp_pca_layout &L, int D, int
         }
     }
     __syncthreads();
+    stamp(SP_SYX);
     // Pxx_b[k][k'] = sum_{r in group} A[k][r] Syx[r][k']  (added up in fixed order by the tail)
     double *Pb = P + (int64_t)blk * KP * KP;
 #pragma unroll
@@ -1129,6 +1247,99 @@ pca_gram_fast_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
     gram_phase_a<KP>(L, D, K, st, P, gl, blockIdx.x);
 }
 
+// Phase A as the one-launch sweep runs it when "pca_sweep_wide" is on: the same outputs by the same
+// chains, scheduled for a launch that has the GPU to itself.  Every load of A and G is requested
+// before the first LDS write (gram_phase_a waits for memory twice at KP = 32, DP = 128); the rows of A
+// are DP + 2 doubles apart, so that they take 16-byte LDS writes; and every thread of the 8 x KP
+// block of Syx owns one output, not 4 H threads a 2 x 2 block each.  The 32 lanes of a half
+// wavefront are 16 columns x 2 rows: 16 rows of A, 4 banks apart, and two broadcast rows of G.
+__host__ __device__ inline size_t gram_phase_a_wide_lds(int KP, int DP)
+{
+    return ((size_t)KP * (DP + 2) + (size_t)GRA * DP + (size_t)GRA * (KP + 1)) * sizeof(double);
+}
+
+template <int KP, class STAMP = stamps_off>
+__device__ __forceinline__ void gram_phase_a_wide(const vmp_pca_layout &L, int D, int K, double *st,
+                                                  double *P, double *lds, int blk,
+                                                  const STAMP &stamp = STAMP())
+{
+    constexpr int LDS_S = KP + 1, KT = KP / 16, E = KP * KP / NTF;
+    constexpr int NA = KP * (FAST_D / 2) / NTF, NG = GRA * (FAST_D / 2) / NTF;
+    const int DP = (int)L.DP, LA = DP + 2;
+    const int DP2 = DP >> 1, sh = __builtin_ctz(DP2);       // DP = 32, 64 or 128
+    double *As = lds;                    // KP x LA (rows >= K zero)
+    double *Gs = As + KP * LA;           // GRA x DP
+    double *Ss = Gs + GRA * DP;          // GRA x LDS_S
+    const int tid = threadIdx.x;
+    const int r0 = blk * GRA;
+    const double *A = st + L.off_A;
+    const double *G = st + L.off_G + (int64_t)r0 * DP;
+    // (every load is unconditional, from a clamped address, and masked afterwards: behind a branch
+    // each would be waited for before the next is requested)
+    v2f64 av[NA], gv[NG];
+#pragma unroll
+    for (int m = 0; m < NA; ++m) {
+        const int e = tid + m * NTF;                         // (beyond KP DP2 at DP < 128: row K - 1)
+        const int k = e >> sh, c = (e & (DP2 - 1)) * 2;
+        av[m] = *reinterpret_cast<const v2f64 *>(A + (k < K ? k : K - 1) * DP + c);
+    }
+#pragma unroll
+    for (int m = 0; m < NG; ++m) {
+        const int e = tid + m * NTF;
+        gv[m] = *reinterpret_cast<const v2f64 *>(G + 2 * (e < GRA * DP2 ? e : GRA * DP2 - 1));
+    }
+#pragma unroll
+    for (int m = 0; m < NA; ++m) {
+        const int e = tid + m * NTF;
+        const int k = e >> sh, c = (e & (DP2 - 1)) * 2;
+        if (e < KP * DP2) *reinterpret_cast<v2f64 *>(As + k * LA + c) = k < K ? av[m] : v2f64{0.0, 0.0};
+    }
+#pragma unroll
+    for (int m = 0; m < NG; ++m) {
+        const int e = tid + m * NTF;
+        if (e < GRA * DP2) *reinterpret_cast<v2f64 *>(Gs + 2 * e) = gv[m];
+    }
+    __syncthreads();
+    stamp(SP_LDS_FILLED);
+    // Syx[r][k] = sum_d G[r][d] A[k][d]: one output per thread
+    {
+        const int w = tid >> 6, l = tid & 63;
+        if (w < 2 * KT) {
+            const int k = (l & 15) + 16 * (w % KT), r = (l >> 4) + 4 * (w / KT);
+            const double *g = Gs + r * DP, *ar = As + k * LA;
+            double s = 0.0;
+#pragma unroll 16
+            for (int d = 0; d < D; ++d) s = __builtin_fma(g[d], ar[d], s);
+            Ss[r * LDS_S + k] = s;
+            if (r0 + r < D && k < K) st[L.off_S + (r0 + r) * KP + k] = s;
+        }
+    }
+    __syncthreads();
+    stamp(SP_SYX);
+    // Pxx_b[k][k'] = sum_{r in group} A[k][r] Syx[r][k']  (added up in fixed order by the tail)
+    double *Pb = P + (int64_t)blk * KP * KP;
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int e = tid + m * NTF;
+        const int k = e / KP, k2 = e % KP;
+        double s = 0.0;
+        if (k < K && k2 < K) {
+#pragma unroll
+            for (int r = 0; r < GRA; ++r) s = __builtin_fma(As[k * LA + r0 + r], Ss[r * LDS_S + k2], s);
+        }
+        Pb[e] = s;
+    }
+}
+
+// that phase A alone (tests: bitwise against pca_gram_stats_kernel)
+template <int KP>
+__global__ void __launch_bounds__(NTF)
+pca_gram_wide_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
+{
+    extern __shared__ __align__(16) double gl[];
+    gram_phase_a_wide<KP>(L, D, K, st, P, gl, blockIdx.x);
+}
+
 // Phase B, the workgroup that draws the last ticket: the tail of this sweep and, unless that tail
 // stops the loop, the head of the next one.  The ticket is the counter form of the in-launch
 // reduction: every workgroup drains its stores, lane 0 releases at agent scope and draws; the one
@@ -1138,9 +1349,153 @@ pca_gram_fast_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
 // `ticket` is this sweep's own word, zero at the launch (one memset per chunk, vmp_pca_sweeps).
 // This kernel never runs beside a latent pass (no pass is in flight during held sweeps), so the
 // placement budget of pca_head_fast_kernel does not bind it.
-template <int KP>
-__global__ void __launch_bounds__(NTF)
-pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, unsigned int *ticket)
+// The head of the next sweep as phase B runs it when "pca_sweep_wide" is on: pca_head_body without
+// the placement budget.  The D x K operand -- the rows of sum y<x>^T the wide tail left in SW, then
+// the rows of <W> -- stays in LDS whole (whole 32-row blocks of it, as many as pca_head_body walks),
+// so W = tau Syx Cov_W, Sww and A = tau Cov_X W^T are one barrier-delimited phase each and nothing is
+// loaded from global memory.  Per output the MFMA sequence is the one of pca_head_body: over q for a
+// tile of W and A, over the rows in ascending order for a tile of Sww.  Stores are the same.
+template <int KP, class STAMP>
+__device__ __forceinline__ void pca_head_wide(const small_args &a, double *st, double *M, double *T,
+                                              const double *alm, double tau, double *SW,
+                                              const STAMP &stamp)
+{
+    constexpr int LDM = KP + 1, E = KP * KP / NTF, KT = KP / 16;
+    constexpr int WT = FAST_D / 16 * KT / 4;      // 16 x 16 tiles of the D x K operand per wavefront
+    constexpr int ST = (KT * KT + 3) / 4;         // tiles of Sww per wavefront
+    __shared__ double logdet;
+    __shared__ int bad;
+    const lay32 L(a.L);
+    const int tid = threadIdx.x, D = a.D, K = a.K, DP = (int)L.DP;
+    const int nr = (D + 31) / 32 * 32;            // rows of SW in use
+    const int nt = nr / 16 * KT;                  // ... and its tiles
+    const int w = tid >> 6, l15 = tid & 15, l4 = (tid & 63) >> 4;
+    if (tid == 0) bad = 0;
+    // ---- W: Lambda_W = diag<alpha> + <tau> Sxx ------------------------------------------
+    {
+        double lam[E];
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            const int e = tid + m * NTF;
+            const int i = e / KP, j = e % KP;
+            double x = (i == j) ? 1.0 : 0.0;
+            if (i < K && j < K) {
+                x = tau * (a.n_total * M[i * LDM + j] + 0.5 * (T[i * LDM + j] + T[j * LDM + i]));
+                if (i == j) x += alm[i];
+            }
+            lam[m] = x;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            const int e = tid + m * NTF;
+            M[(e / KP) * LDM + (e % KP)] = lam[m];
+        }
+    }
+    stamp(SP_H_LAMBDA);
+    sweep_inverse<KP>(M, K, &logdet, &bad);
+    stamp(SP_H_INV1);
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int e = tid + m * NTF;
+        const int i = e / KP, j = e % KP;
+        if (i < K && j < K) st[L.off_CW + i * KP + j] = M[i * LDM + j];
+    }
+    if (tid == 0) st[L.off_scal + 0] = logdet;
+    // <w_d> = <tau> Cov_W Syx[d]: every tile first, then the rows of <W> replace those of Syx
+    v4f64 wt[WT];
+#pragma unroll
+    for (int t = 0; t < WT; ++t) {
+        const int tile = w + 4 * t;
+        if (tile < nt)
+            wt[t] = wave_tile_mma(SW + (tile / KT) * 16 * LDM, LDM, 1, M + (tile % KT) * 16, LDM, 1, KP);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < WT; ++t) {
+        const int tile = w + 4 * t;
+        if (tile < nt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = (tile / KT) * 16 + l4 + 4 * r, k = (tile % KT) * 16 + l15;
+                const double x = tau * wt[t][r];
+                SW[row * LDM + k] = x;
+                if (row < D && k < K) st[L.off_W + row * KP + k] = x;
+            }
+        }
+    }
+    __syncthreads();
+    stamp(SP_H_W);
+    // Sww = D Cov_W + W^T W: one chain over the rows per tile
+#pragma unroll
+    for (int t = 0; t < ST; ++t) {
+        const int tile = w + 4 * t;
+        if (tile < KT * KT) {
+            const v4f64 sacc = wave_tile_mma_acc(v4f64{0.0, 0.0, 0.0, 0.0}, SW + (tile / KT) * 16, 1, LDM,
+                                                 SW + (tile % KT) * 16, LDM, 1, nr);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = (tile / KT) * 16 + l4 + 4 * r, j = (tile % KT) * 16 + l15;
+                const double sww = (double)D * M[i * LDM + j] + sacc[r];
+                T[i * LDM + j] = sww;
+                if (i < K && j < K) st[L.off_Sww + i * KP + j] = sww;
+            }
+        }
+    }
+    __syncthreads();
+    stamp(SP_H_SWW);
+    // ---- X, replicated half: Lambda_X = x_prec I + <tau> Sww ; A = <tau> Cov_X W^T --------
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int e = tid + m * NTF;
+        const int i = e / KP, j = e % KP;
+        double x = (i == j) ? 1.0 : 0.0;
+        if (i < K && j < K) {
+            x = tau * 0.5 * (T[i * LDM + j] + T[j * LDM + i]);
+            if (i == j) x += a.x_prec;
+        }
+        M[i * LDM + j] = x;
+    }
+    // pca_head_body multiplies by the rows of <W> it loads back from the state, which are exactly
+    // zero beyond D and K: wavefronts 1 .. 3 make SW so while wavefront 0 inverts
+    const auto pad = [&]() {
+        if (D == nr && K == KP) return;
+        for (int e = tid - 64; e < nr * KP; e += NTF - 64)
+            if (e / KP >= D || e % KP >= K) SW[(e / KP) * LDM + (e % KP)] = 0.0;
+    };
+    sweep_inverse<KP>(M, K, &logdet, &bad, pad);
+    stamp(SP_H_INV2);
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int e = tid + m * NTF;
+        const int i = e / KP, j = e % KP;
+        if (i < K && j < K) st[L.off_CX + i * KP + j] = M[i * LDM + j];
+    }
+#pragma unroll
+    for (int t = 0; t < WT; ++t) {
+        const int tile = w + 4 * t;
+        if (tile < nt) {
+            const int tk = tile % KT, td = tile / KT;
+            const v4f64 acc = wave_tile_mma(M + tk * 16 * LDM, LDM, 1, SW + td * 16 * LDM, 1, LDM, KP);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = tk * 16 + l4 + 4 * r, d = td * 16 + l15;
+                if (k < K && d < D) st[L.off_A + k * DP + d] = tau * acc[r];
+            }
+        }
+    }
+    if (tid == 0) {
+        st[L.off_scal + 1] = logdet;
+        if (bad) st[L.off_scal + 3] = (double)VMP_ERR_NOT_POSDEF;
+    }
+    stamp.drain();
+    stamp(SP_H_A);
+}
+
+template <int KP, bool WIDE, class STAMP>
+__device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *st, double *P,
+                                                   const vmp_sweep_tail &sw, unsigned int *ticket,
+                                                   const STAMP &stamp)
 {
     extern __shared__ __align__(16) double gl[];
     __shared__ tail_lds<KP> ts;
@@ -1153,9 +1508,14 @@ pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, uns
         }
         return;
     }
-    gram_phase_a<KP>(a.L, a.D, a.K, st, P, gl, blockIdx.x);
+    stamp(SP_ENTRY);
+    if constexpr (WIDE)
+        gram_phase_a_wide<KP>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
+    else
+        gram_phase_a<KP>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    stamp(SP_PXX);
     unsigned int *word = reinterpret_cast<unsigned int *>(gl);     // (phase A's LDS is free now)
     if (tid == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -1164,17 +1524,49 @@ pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, uns
     }
     __syncthreads();
     if (*word != gridDim.x - 1) return;
+    stamp(SP_TICKET);
     if (tid == 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
-    pca_tail_body<KP, TAIL_SWEEP>(a, st, &sw, ts);
+    stamp(SP_ACQUIRE);
+    // (every thread has read the ticket word: the dynamic region is free for SW)
+    pca_tail_body<KP, TAIL_SWEEP, WIDE>(a, st, &sw, ts, gl, stamp);
     __syncthreads();
     if (ts.stop != 0.0) return;
-    // Cov_X, sum <x><x>^T, <alpha> and <tau> go over in LDS; the Syx rows the head loads were
-    // written by phase A (acquired above), the rows of <W> it reads back are its own
-    pca_head_body<KP, true>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2]);
+    // Cov_X, sum <x><x>^T, <alpha> and <tau> go over in LDS.  WIDE: so do the Syx rows (in gl);
+    // otherwise the head loads them -- phase A wrote them, acquired above -- and reads back its own <W>
+    if constexpr (WIDE)
+        pca_head_wide<KP>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], gl, stamp);
+    else
+        pca_head_body<KP, true>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], stamp);
+}
+
+// WIDE: phase B runs the wide tail and head ("pca_sweep_wide", default); false: pca_tail_body and
+// pca_head_body as the three-launch sweep runs them
+template <int KP, bool WIDE>
+__global__ void __launch_bounds__(NTF)
+pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, unsigned int *ticket)
+{
+    pca_sweep_mid_body<KP, WIDE>(a, st, P, sw, ticket, stamps_off());
+}
+
+// the same with wall_clock64 stamps ("pca_sweep_stamps"): `out` is this launch's row of
+// VMP_SWEEP_NSTAMP words, written by the workgroup that ran phase B
+template <int KP, bool WIDE>
+__global__ void __launch_bounds__(NTF)
+pca_sweep_mid_stamped_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw,
+                             unsigned int *ticket, unsigned long long *out)
+{
+    __shared__ unsigned long long stl[VMP_SWEEP_NSTAMP];
+    if (threadIdx.x < VMP_SWEEP_NSTAMP) stl[threadIdx.x] = 0;
+    __syncthreads();
+    const stamps_on stamp{stl};
+    pca_sweep_mid_body<KP, WIDE>(a, st, P, sw, ticket, stamp);
+    // (a workgroup that did not run phase B leaves no tail stamp)
+    if (threadIdx.x == 0 && stl[SP_T_PARTIALS] != 0)
+        for (int i = 0; i < VMP_SWEEP_NSTAMP; ++i) out[i] = stl[i];
 }
 
 bool fast_small_enabled()
@@ -1378,7 +1770,8 @@ static int32_t raise_lds_once(vmp_ctx *ctx, F *k16, F *k32, bool *raised)
     return VMP_OK;
 }
 
-int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P)
+int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P,
+                                 int32_t wide)
 {
     vmp_pca_layout L;
     const int32_t rc = vmp_pca_get_layout(D, K, &L);
@@ -1386,10 +1779,24 @@ int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *sta
     VMP_REQUIRE(ctx, L.KP <= 32 && D <= FAST_D, VMP_ERR_UNSUPPORTED,
                 "the fast Gram statistics cover K <= 32, D <= %d", FAST_D);
     VMP_REQUIRE(ctx, ((uintptr_t)state % 16) == 0, VMP_ERR_INVALID, "state must be 16-byte aligned");
-    static bool raised[64] = {false};
-    const int32_t rr = raise_lds_once(ctx, pca_gram_fast_kernel<16>, pca_gram_fast_kernel<32>, raised);
+    static bool raised[2][64] = {{false}};
+    const int32_t rr = wide ? raise_lds_once(ctx, pca_gram_wide_kernel<16>, pca_gram_wide_kernel<32>,
+                                             raised[1])
+                            : raise_lds_once(ctx, pca_gram_fast_kernel<16>, pca_gram_fast_kernel<32>,
+                                             raised[0]);
     if (rr != VMP_OK) return rr;
     const int nb = (int)(L.DP / GRA);
+    if (wide) {
+        const size_t ldw = gram_phase_a_wide_lds((int)L.KP, (int)L.DP);
+        if (L.KP == 16)
+            hipLaunchKernelGGL(pca_gram_wide_kernel<16>, dim3(nb), dim3(NTF), ldw, ctx->stream, L, D, K,
+                               state, P);
+        else
+            hipLaunchKernelGGL(pca_gram_wide_kernel<32>, dim3(nb), dim3(NTF), ldw, ctx->stream, L, D, K,
+                               state, P);
+        VMP_HIP_CHECK(ctx, hipGetLastError());
+        return VMP_OK;
+    }
     const size_t lds = gram_phase_a_lds((int)L.KP, (int)L.DP);
     if (L.KP == 16)
         hipLaunchKernelGGL(pca_gram_fast_kernel<16>, dim3(nb), dim3(NTF), lds, ctx->stream, L, D, K,
@@ -1401,26 +1808,47 @@ int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *sta
     return VMP_OK;
 }
 
+// one instantiation of the one-launch sweep; `stamps` (null: the default kernel) is the launch's row
+template <int KP, bool WIDE>
+static int32_t launch_mid(vmp_ctx *ctx, const small_args &a, double *state, double *P,
+                          const vmp_sweep_tail &t, unsigned int *ticket, unsigned long long *stamps)
+{
+    static bool raised[2][64] = {{false}};
+    const int dev = ctx->device & 63, s = stamps ? 1 : 0;
+    if (!raised[s][dev]) {
+        const void *f = stamps ? (const void *)pca_sweep_mid_stamped_kernel<KP, WIDE>
+                               : (const void *)pca_sweep_mid_kernel<KP, WIDE>;
+        VMP_HIP_CHECK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               96 * 1024));
+        raised[s][dev] = true;
+    }
+    // (the rows of SW the wide bodies keep fit in phase A's region: DP (KP + 1) doubles at most)
+    const size_t lds = WIDE ? gram_phase_a_wide_lds((int)a.L.KP, (int)a.L.DP)
+                            : gram_phase_a_lds((int)a.L.KP, (int)a.L.DP);
+    const dim3 nb((unsigned)(a.L.DP / GRA));
+    if (stamps)
+        hipLaunchKernelGGL((pca_sweep_mid_stamped_kernel<KP, WIDE>), nb, dim3(NTF), lds, ctx->stream, a,
+                           state, P, t, ticket, stamps);
+    else
+        hipLaunchKernelGGL((pca_sweep_mid_kernel<KP, WIDE>), nb, dim3(NTF), lds, ctx->stream, a, state,
+                           P, t, ticket);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
 int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                                  double a0t, double b0t, double a0a, double b0a, double *state,
-                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket)
+                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket, int32_t wide,
+                                 unsigned long long *stamps)
 {
     small_args a;
     const int32_t rc = fill_small_args(ctx, a, D, K, n_total, x_prec, a0t, b0t, a0a, b0a);
     if (rc != VMP_OK) return rc;
-    static bool raised[64] = {false};
-    const int32_t rr = raise_lds_once(ctx, pca_sweep_mid_kernel<16>, pca_sweep_mid_kernel<32>, raised);
-    if (rr != VMP_OK) return rr;
-    const int nb = (int)(a.L.DP / GRA);
-    const size_t lds = gram_phase_a_lds((int)a.L.KP, (int)a.L.DP);
     if (a.L.KP == 16)
-        hipLaunchKernelGGL(pca_sweep_mid_kernel<16>, dim3(nb), dim3(NTF), lds, ctx->stream, a, state,
-                           P, t, ticket);
-    else
-        hipLaunchKernelGGL(pca_sweep_mid_kernel<32>, dim3(nb), dim3(NTF), lds, ctx->stream, a, state,
-                           P, t, ticket);
-    VMP_HIP_CHECK(ctx, hipGetLastError());
-    return VMP_OK;
+        return wide ? launch_mid<16, true>(ctx, a, state, P, t, ticket, stamps)
+                    : launch_mid<16, false>(ctx, a, state, P, t, ticket, stamps);
+    return wide ? launch_mid<32, true>(ctx, a, state, P, t, ticket, stamps)
+                : launch_mid<32, false>(ctx, a, state, P, t, ticket, stamps);
 }
 
 extern "C" {

@@ -150,6 +150,15 @@ class HIPKernels:
         self.rt.check(self.lib.vmp_pca_sweep_mid_count(self.ctx, ctypes.byref(a)))
         return a.value
 
+    def sweep_stamps(self, max_rows=4096):
+        """(rows x 24 array of wall_clock64 stamps of the latest batch's one-launch sweeps, whether
+        the context owns a stamp buffer at all): vmp_pca_sweep_stamps, tune key "pca_sweep_stamps"."""
+        out = np.zeros((max_rows, 24), dtype=np.uint64)
+        rows, allocated = ctypes.c_int32(), ctypes.c_int32()
+        self.rt.check(self.lib.vmp_pca_sweep_stamps(self.ctx, out.ctypes.data, max_rows,
+                                                    ctypes.byref(rows), ctypes.byref(allocated)))
+        return out[:rows.value], bool(allocated.value)
+
     def ensure_gram(self):
         """The Gram-form messages to W are formed lazily by the library (vmp_pca_ensure_gram):
         before the state block is read directly."""

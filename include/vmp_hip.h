@@ -255,10 +255,25 @@ int32_t vmp_pca_sweep_counts(vmp_ctx *ctx, int64_t *enqueued, int64_t *executed,
  * error: this count is where that shows.  Launches of that kernel on this context since it was
  * created (no device read). */
 int32_t vmp_pca_sweep_mid_count(vmp_ctx *ctx, int64_t *launches);
+/* Phase B of that launch runs wide forms of the tail and the head -- every load of the tail in one
+ * batch, the D x K operand of the head whole in LDS, built for a workgroup that has the GPU to
+ * itself -- unless tune key "pca_sweep_wide" / VMP_PCA_SWEEP_WIDE (default 1) is 0, which selects the
+ * bodies of the three-launch sweep inside the launch.  The two agree bitwise.
+ *
+ * Measurement: while tune key "pca_sweep_stamps" is 1, vmp_pca_sweeps launches a stamped build of that
+ * kernel, in which one lane records wall_clock64() (a constant 100 MHz counter) at the boundaries of
+ * its phases: VMP_PCA_SWEEP_NSTAMP words per launch of the latest batch, 0 where a boundary was not
+ * passed (order: csrc/vmp_pca_small.hip, enum SP_*).  This call waits for the stream and copies up to
+ * max_rows rows out.  The buffer belongs to the context and exists only once the key has been on:
+ * *allocated (may be null) says whether it does. */
+#define VMP_PCA_SWEEP_NSTAMP 24
+int32_t vmp_pca_sweep_stamps(vmp_ctx *ctx, uint64_t *out, int32_t max_rows, int32_t *rows,
+                             int32_t *allocated);
 /* The Gram statistics of one sweep alone, from the A and G of the state block: rows of sum y<x>^T
  * into the state, the DP / 8 partial blocks of sum <x><x>^T into the workspace (not added up).
- * form 0: the kernel every other path uses; form 1: the body of the one-launch sweep (K <= 32,
- * D <= 128, 16-byte aligned state).  The two agree bitwise. */
+ * form 0: the kernel every other path uses; form 1: the body of the one-launch sweep with
+ * "pca_sweep_wide" = 0, form 2: its body with "pca_sweep_wide" = 1 (both K <= 32, D <= 128, 16-byte
+ * aligned state).  The three agree bitwise. */
 int32_t vmp_pca_gram_stats_form(vmp_ctx *ctx, int32_t D, int32_t K, double *state, void *workspace,
                                 int32_t form);
 /* Gram form: the messages to W of the latest latent pass, S = [G A^T ; A G A^T] in the state block

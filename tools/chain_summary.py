@@ -3,7 +3,10 @@
 calls / mean / min of the replicated-node chain over the timed region, launches per sweep, and the
 gap from one sweep's end to the next one's start.
 
-    python tools/chain_summary.py <results.db> <steps>
+    python tools/chain_summary.py <results.db> <steps> [<below_us>]
+
+With <below_us> (the other build's shortest one-launch sweep) the distribution of the one-launch sweeps
+is printed as well: deciles and how many launches are shorter than that.
 """
 import re
 import sqlite3
@@ -22,7 +25,7 @@ ENDERS = ('pca_tail_sweep_kernel', 'pca_sweep_mid_kernel')      # the kernel tha
 PASSES = ('pca_xpass', 'pca_pass')
 
 
-def main(db, steps):
+def main(db, steps, below=None):
     """The window is the timed region of `bench.py --steps <steps>`: every pca_* launch that starts
     after the end of the last sweep BEFORE the final `steps` sweeps (the last warm-up sweep), so
     set-up and warm-up launches are left out and parent and change are cut the same way."""
@@ -46,6 +49,14 @@ def main(db, steps):
     print('%-52s %6s %10s %10s %10s' % ('kernel', 'calls', 'mean_us', 'min_us', 'max_us'))
     for k, v in sorted(agg.items(), key=lambda kv: -sum(kv[1])):
         print('%-52s %6d %10.2f %10.2f %10.2f' % (k, len(v), sum(v) / len(v), min(v), max(v)))
+    mid = sorted(d for k, v in agg.items() if k.startswith('pca_sweep_mid_kernel') for d in v)
+    if mid:
+        q = lambda f: mid[min(len(mid) - 1, int(f * len(mid)))]
+        print('pca_sweep_mid_kernel durations: p10 %.2f median %.2f p90 %.2f us'
+              % (q(0.1), q(0.5), q(0.9)))
+        if below is not None:
+            print('pca_sweep_mid_kernel launches shorter than %.2f us: %d of %d'
+                  % (below, sum(1 for d in mid if d < below), len(mid)))
     small = [r for r in win if not r[0].startswith(PASSES)]
     # gap: the end of a sweep to the start of the next small kernel; period: sweep end to sweep end
     gaps, periods, prev_end = [], [], t_begin
@@ -68,4 +79,5 @@ def main(db, steps):
 
 
 if __name__ == '__main__':
-    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 200)
+    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 200,
+         float(sys.argv[3]) if len(sys.argv) > 3 else None)
