@@ -41,20 +41,6 @@ struct BinmArgs {
     double *r_out;             // N x K or null
 };
 
-__device__ __forceinline__ double group16_max(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 16));
-    return v;
-}
-
-__device__ __forceinline__ double group16_sum(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
-    return v;
-}
-
 template <int KT>
 __global__ void __launch_bounds__(NT) binm_pass_kernel(BinmArgs a)
 {
@@ -345,10 +331,7 @@ binm_dots_kernel(int n, const double *__restrict__ S, const double *__restrict__
     }
     bs[tid] = t + te;
     __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (tid < off) bs[tid] += bs[tid + off];
-        __syncthreads();
-    }
+    block_halve_sum<NT>(bs, tid);
     if (tid == 0) out[0] = bs[0];
 }
 
@@ -393,27 +376,6 @@ binm_tables_kernel(int D, int K, int form, const double *__restrict__ elog_p,
     }
 }
 
-__device__ __forceinline__ void binm_pack_value(double v, int64_t tn, bool seen, uint16_t *xo,
-                                                uint16_t *no, int *bad)
-{
-    vmp_binm_pack_f64(v, tn, seen, xo, no, bad);
-}
-__device__ __forceinline__ void binm_pack_value(int64_t v, int64_t tn, bool seen, uint16_t *xo,
-                                                uint16_t *no, int *bad)
-{
-    vmp_binm_pack_i64(v, tn, seen, xo, no, bad);
-}
-__device__ __forceinline__ void binm_pack_value(int32_t v, int64_t tn, bool seen, uint16_t *xo,
-                                                uint16_t *no, int *bad)
-{
-    vmp_binm_pack_i64((int64_t)v, tn, seen, xo, no, bad);
-}
-__device__ __forceinline__ void binm_pack_value(uint8_t v, int64_t tn, bool seen, uint16_t *xo,
-                                                uint16_t *no, int *bad)
-{
-    vmp_binm_pack_i64((int64_t)v, tn, seen, xo, no, bad);
-}
-
 // block b: the elements [b span, (b + 1) span); its sum of coefficients, its number of hidden entries
 // and whether any of its trials differs from row 0's of the column go to the three arrays of ws
 template <typename T>
@@ -438,7 +400,7 @@ binm_pack_kernel(int64_t n, int D, int64_t span, const T *__restrict__ x,
         var |= tn != trials[d * ts_d] ? 1 : 0;
         const bool seen = mask ? mask[e] != 0 : true;
         uint16_t xo, no;
-        binm_pack_value(x[e], tn, seen, &xo, &no, &bad);
+        vmp_binm_pack(x[e], tn, seen, &xo, &no, &bad);
         xp[e] = xo;
         np[e] = no;
         vmp_pmm_sum_add(&lc, &lce, vmp_binm_lchoose(xo, no));

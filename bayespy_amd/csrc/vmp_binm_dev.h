@@ -128,6 +128,21 @@ __host__ __device__ inline void vmp_binm_pack_i64(int64_t v, int64_t tn, bool se
     *no = (seen && ok) ? (uint16_t)tn : (uint16_t)VMP_BINM_HIDDEN;
 }
 
+// an entry of any dtype the pack takes: a double by vmp_binm_pack_f64, every integer by
+// vmp_binm_pack_i64
+__host__ __device__ inline void vmp_binm_pack(double v, int64_t tn, bool seen, uint16_t *xo,
+                                              uint16_t *no, int *bad)
+{
+    vmp_binm_pack_f64(v, tn, seen, xo, no, bad);
+}
+
+template <typename T>
+__host__ __device__ inline void vmp_binm_pack(T v, int64_t tn, bool seen, uint16_t *xo,
+                                              uint16_t *no, int *bad)
+{
+    vmp_binm_pack_i64((int64_t)v, tn, seen, xo, no, bad);
+}
+
 __host__ __device__ inline bool vmp_binm_observed(uint16_t np) { return np != VMP_BINM_HIDDEN; }
 
 // lgamma(p + 1) as a sum hi + lo; exactly zero for 0 and 1.  Up to 20 the factorial is an exact

@@ -62,20 +62,6 @@ struct BmmMaskedArgs : BmmArgs {   // xw: N x 2 W, part: chunks x vmp_bmm_partia
 template <bool MASKED> struct BmmArgsOf { using type = BmmArgs; };
 template <> struct BmmArgsOf<true> { using type = BmmMaskedArgs; };
 
-__device__ __forceinline__ double group16_max(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 16));
-    return v;
-}
-
-__device__ __forceinline__ double group16_sum(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
-    return v;
-}
-
 template <int KT, bool MASKED>
 __global__ void __launch_bounds__(BMM_NT) bmm_pass_kernel(typename BmmArgsOf<MASKED>::type a)
 {

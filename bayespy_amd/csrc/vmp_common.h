@@ -417,4 +417,46 @@ __device__ inline double block_sum(double v, double *red)
     for (int i = 0; i < NT / 64; ++i) s += red[i];
     return s;
 }
+
+// Maximum and sum over a group of 16 lanes (the columns of one row in the plate passes of the
+// mixture blocks): a butterfly, so every lane of the group has the result.
+__device__ __forceinline__ double group16_max(double v)
+{
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 16));
+    return v;
+}
+
+__device__ __forceinline__ double group16_sum(double v)
+{
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
+    return v;
+}
+
+// The NT sums of a workgroup (LDS, one per thread, a barrier behind the last store) are halved
+// until v[0] holds their total: 256 sums eight times.  Ends on a barrier.
+template <int NT>
+__device__ __forceinline__ void block_halve_sum(double *v, int tid)
+{
+    for (int off = NT / 2; off > 0; off >>= 1) {
+        if (tid < off) v[tid] += v[tid + off];
+        __syncthreads();
+    }
+}
+
+// vmp_pmm.hip: the plate pass of the Poisson block, which the multinomial block runs as well
+// (nothing hidden, words for columns).  Leaves one partial per chunk in `part`.
+struct PmmArgs {
+    int64_t N, chunk;
+    int D, K;
+    const uint16_t *x;         // N x D, packed
+    const int32_t *labels;     // fixed classes (r = one-hot, lse = 0) or null
+    const double *l, *lb;      // D x K; lb is read with hidden entries only
+    const double *c;           // K
+    double *part;              // chunks x vmp_pmm_partial_doubles
+    double *r_out;             // N x K or null
+};
+
+void vmp_pmm_launch_pass(vmp_ctx *ctx, int64_t nc, bool hidden, const PmmArgs &a);
 #endif

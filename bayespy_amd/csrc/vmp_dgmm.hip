@@ -49,20 +49,6 @@ struct DgmmArgs {
     double *r_out;             // N x K or null
 };
 
-__device__ __forceinline__ double group16_max(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 16));
-    return v;
-}
-
-__device__ __forceinline__ double group16_sum(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
-    return v;
-}
-
 // place of element (row t, column j) of the y tile in LDS: the column is XORed with a function of
 // the row (below 32, so it stays inside the row of 64), which spreads both the A reads (16 rows,
 // one column per lane quarter) and the B reads (16 columns, one row per lane quarter) over the banks
@@ -365,10 +351,7 @@ dgmm_update_kernel(int D, int K, int which, const double *__restrict__ prior_a,
     }
     bs[tid] = t;
     __syncthreads();
-    for (int off = DGMM_NT / 2; off > 0; off >>= 1) {
-        if (tid < off) bs[tid] += bs[tid + off];
-        __syncthreads();
-    }
+    block_halve_sum<DGMM_NT>(bs, tid);
     if (tid == 0) bound[0] = bs[0];
 }
 

@@ -56,20 +56,6 @@ struct MaskedArgs {
     double *r_out;             // N x K or null
 };
 
-__device__ __forceinline__ double group16_max(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 16));
-    return v;
-}
-
-__device__ __forceinline__ double group16_sum(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
-    return v;
-}
-
 __device__ __forceinline__ int y_at(int t, int j)
 {
     return t * DBM + (j ^ (((t & 15) << 1) ^ ((t & 1) << 4)));
@@ -386,10 +372,7 @@ dgmm_masked_update_kernel(int D, int K, int which, const double *__restrict__ pr
     }
     bs[tid] = t;
     __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (tid < off) bs[tid] += bs[tid + off];
-        __syncthreads();
-    }
+    block_halve_sum<NT>(bs, tid);
     if (tid == 0) bound[0] = bs[0];
 }
 

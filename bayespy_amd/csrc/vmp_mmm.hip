@@ -12,263 +12,22 @@
 //                         N_k += sum r, sum lse
 //                         S += r^T X                                (K x M, a row per cluster)
 //
-// Both products run on v_mfma_f64_16x16x4_f64 (operand layout: vmp_dgmm.hip).  x is 16 bits per
-// entry (the fragment loads, the softmax and the compensated sums are those of vmp_pmm_dev.h); the
-// tile of a word block is staged in LDS as it is and becomes a double when an operand is formed.
-// The pass reads no other array of size N M.
+// THE PASS KERNEL IS THE POISSON BLOCK'S: vmp_mmm_pass launches pmm_pass_kernel<KT, false>
+// (vmp_pmm.hip, through vmp_pmm_launch_pass of vmp_common.h) with the M words for its D columns and
+// L for its l; nothing is hidden, so its lb is never read.  The 16-bit x, the word blocks of 128
+// that hold M = 1024, the staged tile, the softmax and the chunk's partial (S as K x M, N_k, sum
+// lse: vmp_mmm_partial_doubles(M, K) = vmp_pmm_partial_doubles(M, K, 0)) are described there.  A
+// profile of a multinomial model therefore lists pmm_pass_kernel.
 //
-// M is walked in WORD BLOCKS of 128: 32 accumulator tiles of 16 x 16 at K = 64, eight per
-// wavefront, held twice (the sums of the present tile of 64 rows and the chunk's running sums): 128
-// registers.  With one block its x tile stays in LDS between the two products and the running sums
-// live in registers through the chunk.  Above, the logits walk the blocks first, the second product
-// walks them again (from L2) and each block's running sums are carried through the chunk's partial
-// in memory; that holds M = 1024.
-//
-// A row of the staged tile is 128 + 2 halfwords: 65 dwords, so the 16 rows of an A read and the 4
-// rows of a B read fall on different banks.
-//
-// No floating-point atomics: a workgroup owns a chunk of consecutive rows and leaves one partial;
-// mmm_combine_kernel adds the partials in chunk order.
+// What follows the pass is this block's own and defines the bits of its outputs: mmm_combine_kernel
+// adds the partials in chunk order and leaves S as K x M (a row per cluster, where the Poisson
+// block writes D x K); mmm_dots_kernel forms scal[1] and scal[2] in the order of vmp_mmm_dev.h.
 #include "vmp_common.h"
 #include "vmp_mmm_dev.h"
 
 namespace {
 
 constexpr int NT = VMP_MMM_NT;
-
-struct MmmArgs {
-    int64_t N, chunk;
-    int M, K;
-    const uint16_t *x;         // N x M, packed
-    const int32_t *labels;     // fixed classes (r = one-hot, lse = 0) or null
-    const double *L;           // M x K, word-major
-    const double *c;           // K
-    double *part;              // chunks x vmp_mmm_partial_doubles
-    double *r_out;             // N x K or null
-};
-
-__device__ __forceinline__ double group16_max(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 16));
-    return v;
-}
-
-__device__ __forceinline__ double group16_sum(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
-    return v;
-}
-
-template <int KT>
-__global__ void __launch_bounds__(NT) mmm_pass_kernel(MmmArgs a)
-{
-    constexpr int KP = KT * 16;
-    constexpr int MB = VMP_MMM_MBLOCK;
-    constexpr int STR = MB + 2;                      // halfwords of a staged row
-    constexpr int NH = KT * (MB / 16) / 4;           // (word, k) tiles per wavefront
-    __shared__ __attribute__((aligned(8))) uint16_t x_s[VMP_MMM_TILE * STR];
-    __shared__ double r_s[VMP_MMM_TILE * KP];        // responsibilities of the tile, row-major
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
-    const int M = a.M, K = a.K;
-    const int64_t r0 = (int64_t)blockIdx.x * a.chunk;
-    const int64_t r1 = (r0 + a.chunk < a.N) ? r0 + a.chunk : a.N;
-    double *part = a.part + (int64_t)blockIdx.x * vmp_mmm_partial_doubles(M, K);
-    const int64_t MK = (int64_t)M * K;
-    const int nblk = (M + MB - 1) / MB;
-    const bool soft = a.labels == nullptr;
-    const bool x8 = ((uintptr_t)a.x & 7) == 0;
-
-    double cval[KT], nk[KT];
-#pragma unroll
-    for (int kb = 0; kb < KT; ++kb) {
-        const int k = kb * 16 + l15;
-        cval[kb] = k < K ? a.c[k] : -INFINITY;
-        nk[kb] = 0.0;
-    }
-    double lsum = 0.0;
-    v4f64 acc[NH];                                   // the chunk's running sums
-#pragma unroll
-    for (int j = 0; j < NH; ++j) acc[j] = v4f64{0.0, 0.0, 0.0, 0.0};
-
-    // rows row0 .. of words m0 .. m0 + MB - 1 into x_s, four halfwords per thread and step; zero
-    // beyond the chunk and beyond M
-    auto load_x = [&](int64_t row0, int m0) {
-        for (int i = tid; i < VMP_MMM_TILE * (MB / 4); i += NT) {
-            const int t = i / (MB / 4), j = 4 * (i % (MB / 4));
-            const int64_t row = row0 + t;
-            const int m = m0 + j;
-            const int64_t e = row * M + m;
-            uint32_t lo, hi;
-            if (row < r1 && m + 3 < M && x8 && (e & 3) == 0) {
-                const uint64_t v = *(const uint64_t *)(a.x + e);
-                lo = (uint32_t)v;
-                hi = (uint32_t)(v >> 32);
-            } else {
-                uint32_t h[4];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) h[b] = (row < r1 && m + b < M) ? a.x[e + b] : 0u;
-                lo = h[0] | (h[1] << 16);
-                hi = h[2] | (h[3] << 16);
-            }
-            uint32_t *dst = (uint32_t *)(x_s + t * STR + j);
-            dst[0] = lo;
-            dst[1] = hi;
-        }
-    };
-
-    for (int64_t row0 = r0; row0 < r1; row0 += VMP_MMM_TILE) {
-        // -- logits of this wavefront's 16 rows, block after block
-        v4f64 lg[KT];
-#pragma unroll
-        for (int kb = 0; kb < KT; ++kb) lg[kb] = v4f64{0.0, 0.0, 0.0, 0.0};
-        if (soft || nblk == 1) {
-            for (int blk = 0; blk < nblk; ++blk) {
-                const int m0 = blk * MB;
-                if (blk > 0) __syncthreads();        // the block before has been read
-                load_x(row0, m0);
-                __syncthreads();
-                if (!soft) continue;
-                const int cols = (M - m0 < MB) ? M - m0 : MB;
-                const int steps = (cols + 3) >> 2;
-                for (int s = 0; s < steps; ++s) {
-                    const int j = 4 * s + l4, m = m0 + j;
-                    const double av = vmp_pmm_count(x_s[(wave * 16 + l15) * STR + j]);
-#pragma unroll
-                    for (int kb = 0; kb < KT; ++kb) {
-                        const int k = kb * 16 + l15;
-                        const double bl = (m < M && k < K) ? a.L[(int64_t)m * K + k] : 0.0;
-                        lg[kb] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bl, lg[kb], 0, 0, 0);
-                    }
-                }
-            }
-        }
-        // the constant of the column comes last, as one addition (-inf for the padding)
-#pragma unroll
-        for (int kb = 0; kb < KT; ++kb)
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq)
-                lg[kb][qq] = vmp_dgmm_logit_finish(lg[kb][qq], cval[kb]);
-        // -- softmax over the row: lane (l4, qq) holds columns l15, l15 + 16, ... of row l4 + 4 qq
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-            const int t = wave * 16 + l4 + 4 * qq;
-            const int64_t row = row0 + t;
-            const bool valid = row < r1;
-            double lse = 0.0, s = 1.0, ex[KT];
-            int lab = -1;
-            if (soft) {
-                double mx = lg[0][qq];
-#pragma unroll
-                for (int kb = 1; kb < KT; ++kb) mx = fmax(mx, lg[kb][qq]);
-                mx = group16_max(mx);
-                s = 0.0;
-#pragma unroll
-                for (int kb = 0; kb < KT; ++kb) {
-                    ex[kb] = vmp_dgmm_shifted_exp(lg[kb][qq], mx);
-                    s += ex[kb];
-                }
-                s = group16_sum(s);
-                lse = vmp_dgmm_lse(mx, s);
-            } else if (valid) {
-                lab = a.labels[row];
-            }
-#pragma unroll
-            for (int kb = 0; kb < KT; ++kb) {
-                const int k = kb * 16 + l15;
-                double rv = 0.0;
-                if (valid) rv = soft ? vmp_pmm_resp(ex[kb], s) : (k == lab ? 1.0 : 0.0);
-                r_s[t * KP + k] = rv;
-                nk[kb] += rv;
-                if (a.r_out && valid && k < K) a.r_out[row * K + k] = rv;
-            }
-            if (valid) lsum += lse;
-        }
-        __syncthreads();
-
-        // -- S += r^T X, block after block.  Tile tl of a block is (word tile, cluster tile) =
-        // (tl / KT, tl % KT), dealt out to the wavefronts; the sums of the tile of rows start at
-        // zero and are added to the chunk's running sums once per tile (vmp_mmm_dev.h).
-        for (int blk = 0; blk < nblk; ++blk) {
-            const int m0 = blk * MB;
-            if (nblk > 1) {
-                __syncthreads();                     // what x_s held has been read
-                load_x(row0, m0);
-                __syncthreads();
-            }
-            const int cols = (M - m0 < MB) ? M - m0 : MB;
-            const int ntile = KT * ((cols + 15) >> 4);
-            v4f64 tacc[NH];
-#pragma unroll
-            for (int j = 0; j < NH; ++j) tacc[j] = v4f64{0.0, 0.0, 0.0, 0.0};
-            if (nblk > 1) {
-#pragma unroll
-                for (int j = 0; j < NH; ++j) {
-                    const int tl = wave + 4 * j;
-                    if (tl >= ntile) continue;
-                    const int kb = tl % KT;
-                    const int m = m0 + (tl / KT) * 16 + l15;
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) {
-                        const int k = kb * 16 + l4 + 4 * qq;
-                        acc[j][qq] = (row0 > r0 && k < K && m < M) ? part[(int64_t)k * M + m] : 0.0;
-                    }
-                }
-            }
-            for (int s = 0; s < 16; ++s) {
-                const int t = 4 * s + l4;
-                const double *rrow = r_s + t * KP;
-#pragma unroll
-                for (int j = 0; j < NH; ++j) {
-                    const int tl = wave + 4 * j;
-                    if (tl >= ntile) continue;
-                    const int kb = tl % KT;
-                    const int jc = (tl / KT) * 16 + l15;
-                    const double av = rrow[kb * 16 + l15];
-                    const double bv = vmp_pmm_count(x_s[t * STR + jc]);
-                    tacc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, tacc[j], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < NH; ++j)
-#pragma unroll
-                for (int qq = 0; qq < 4; ++qq) acc[j][qq] += tacc[j][qq];
-            if (nblk > 1 || row0 + VMP_MMM_TILE >= r1) {
-#pragma unroll
-                for (int j = 0; j < NH; ++j) {
-                    const int tl = wave + 4 * j;
-                    if (tl >= ntile) continue;
-                    const int kb = tl % KT;
-                    const int m = m0 + (tl / KT) * 16 + l15;
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) {
-                        const int k = kb * 16 + l4 + 4 * qq;
-                        if (k < K && m < M) part[(int64_t)k * M + m] = acc[j][qq];
-                    }
-                }
-            }
-        }
-        __syncthreads();                 // r_s and x_s are free for the next tile
-    }
-
-    // -- N_k and sum lse: the 16 slots in slot order (they stand in r_s, which is free now) ------
-    double *nk_s = r_s, *lse_s = r_s + 16 * KP;
-#pragma unroll
-    for (int kb = 0; kb < KT; ++kb) nk_s[(wave * 4 + l4) * KP + kb * 16 + l15] = nk[kb];
-    if (l15 == 0) lse_s[wave * 4 + l4] = lsum;
-    __syncthreads();
-    if (tid < K) {
-        double t = 0.0;
-        for (int s = 0; s < 16; ++s) t += nk_s[s * KP + tid];
-        part[MK + tid] = t;
-    }
-    if (tid == 0) {
-        double t = 0.0;
-        for (int s = 0; s < 16; ++s) t += lse_s[s];
-        part[MK + K] = t;
-    }
-}
 
 // one thread per (k, m): the partials in chunk order
 __global__ void __launch_bounds__(NT)
@@ -309,10 +68,7 @@ mmm_dots_kernel(int M, int K, const double *__restrict__ S, const double *__rest
     }
     ds[tid] = t;
     __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (tid < off) ds[tid] += ds[tid + off];
-        __syncthreads();
-    }
+    block_halve_sum<NT>(ds, tid);
     if (tid == 0) {
         double n = 0.0;
         for (int k = 0; k < K; ++k) n = vmp_pmm_mac(n, Nk[k], c[k]);
@@ -340,21 +96,10 @@ mmm_tables_kernel(int M, int K, const double *__restrict__ elog_p,
     }
 }
 
-__device__ __forceinline__ uint16_t mmm_pack_value(double v, int *bad)
+template <typename T>
+__device__ __forceinline__ uint16_t mmm_pack_value(T v, int *bad)
 {
-    return vmp_mmm_entry(vmp_pmm_pack_f64(v, true, bad));
-}
-__device__ __forceinline__ uint16_t mmm_pack_value(int64_t v, int *bad)
-{
-    return vmp_mmm_entry(vmp_pmm_pack_i64(v, true, bad));
-}
-__device__ __forceinline__ uint16_t mmm_pack_value(int32_t v, int *bad)
-{
-    return vmp_mmm_entry(vmp_pmm_pack_i64((int64_t)v, true, bad));
-}
-__device__ __forceinline__ uint16_t mmm_pack_value(uint8_t v, int *bad)
-{
-    return vmp_mmm_entry(vmp_pmm_pack_i64((int64_t)v, true, bad));
+    return vmp_mmm_entry(vmp_pmm_pack(v, true, bad));
 }
 
 // block b: the rows [b span, (b + 1) span); its sum of the multinomial coefficients goes to
@@ -392,10 +137,7 @@ mmm_pack_kernel(int64_t N, int M, int64_t span, const T *__restrict__ x,
     if (bad & VMP_MMM_BAD_SUM) flags[3] = 1;
     ls[tid] = lg + lge;
     __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (tid < off) ls[tid] += ls[tid + off];
-        __syncthreads();
-    }
+    block_halve_sum<NT>(ls, tid);
     if (tid == 0) lg_part[blockIdx.x] = ls[0];
 }
 
@@ -496,21 +238,9 @@ int32_t vmp_mmm_pass(vmp_ctx *ctx, int64_t N, int32_t M, int32_t K, const uint16
     VMP_FLUSH_SMALL(ctx);
     const int64_t nc = vmp_mmm_chunks(N, M, K);
     if (nc > 0) {
-        MmmArgs a = {N, vmp_mmm_chunk_rows(N, M, K), M, K, x_packed, labels, L, c, ws, r_out};
-        switch (vmp_pmm_kpad(K) / 16) {
-        case 1:
-            hipLaunchKernelGGL(mmm_pass_kernel<1>, dim3((unsigned)nc), dim3(NT), 0, ctx->stream, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL(mmm_pass_kernel<2>, dim3((unsigned)nc), dim3(NT), 0, ctx->stream, a);
-            break;
-        case 3:
-            hipLaunchKernelGGL(mmm_pass_kernel<3>, dim3((unsigned)nc), dim3(NT), 0, ctx->stream, a);
-            break;
-        default:
-            hipLaunchKernelGGL(mmm_pass_kernel<4>, dim3((unsigned)nc), dim3(NT), 0, ctx->stream, a);
-            break;
-        }
+        // the Poisson pass, nothing hidden: words for columns, L for l; lb is not read
+        PmmArgs a = {N, vmp_mmm_chunk_rows(N, M, K), M, K, x_packed, labels, L, L, c, ws, r_out};
+        vmp_pmm_launch_pass(ctx, nc, false, a);
         VMP_HIP_CHECK(ctx, hipGetLastError());
     }
     hipLaunchKernelGGL(mmm_combine_kernel, dim3((unsigned)((M * K + NT - 1) / NT)), dim3(NT), 0,

@@ -36,31 +36,7 @@ namespace {
 
 constexpr int NT = VMP_PMM_NT;
 
-struct PmmArgs {
-    int64_t N, chunk;
-    int D, K;
-    const uint16_t *x;         // N x D, packed
-    const int32_t *labels;     // fixed classes (r = one-hot, lse = 0) or null
-    const double *l, *lb;      // D x K
-    const double *c;           // K
-    double *part;              // chunks x vmp_pmm_partial_doubles
-    double *r_out;             // N x K or null
-};
-
-__device__ __forceinline__ double group16_max(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 16));
-    return v;
-}
-
-__device__ __forceinline__ double group16_sum(double v)
-{
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
-    return v;
-}
-
+// PmmArgs: vmp_common.h
 template <int KT, bool HIDDEN>
 __global__ void __launch_bounds__(NT) pmm_pass_kernel(PmmArgs a)
 {
@@ -367,23 +343,6 @@ pmm_tables_kernel(int D, int K, int form, const double *__restrict__ lam_mom,
     }
 }
 
-__device__ __forceinline__ uint16_t pmm_pack_value(double v, bool seen, int *bad)
-{
-    return vmp_pmm_pack_f64(v, seen, bad);
-}
-__device__ __forceinline__ uint16_t pmm_pack_value(int64_t v, bool seen, int *bad)
-{
-    return vmp_pmm_pack_i64(v, seen, bad);
-}
-__device__ __forceinline__ uint16_t pmm_pack_value(int32_t v, bool seen, int *bad)
-{
-    return vmp_pmm_pack_i64((int64_t)v, seen, bad);
-}
-__device__ __forceinline__ uint16_t pmm_pack_value(uint8_t v, bool seen, int *bad)
-{
-    return vmp_pmm_pack_i64((int64_t)v, seen, bad);
-}
-
 // block b: the elements [b span, (b + 1) span); its sum of lgamma(x + 1) and its number of hidden
 // entries go to lg_part[b] and hid_part[b]
 template <typename T>
@@ -402,7 +361,7 @@ pmm_pack_kernel(int64_t n, int64_t span, const T *__restrict__ x, const uint8_t 
         const int64_t e = e0 + i;
         if (e >= n) break;
         const bool seen = mask ? mask[e] != 0 : true;
-        const uint16_t p = pmm_pack_value(x[e], seen, &bad);
+        const uint16_t p = vmp_pmm_pack(x[e], seen, &bad);
         xp[e] = p;
         vmp_pmm_sum_add(&lg, &lge, vmp_pmm_lgamma1(p));
         hid += vmp_pmm_observed(p) ? 0 : 1;
@@ -462,10 +421,7 @@ pmm_update_kernel(int D, int K, int per_element, const double *__restrict__ prio
     }
     bs[tid] = t;
     __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (tid < off) bs[tid] += bs[tid + off];
-        __syncthreads();
-    }
+    block_halve_sum<NT>(bs, tid);
     if (tid == 0) bound[0] = bs[0];
 }
 
@@ -490,6 +446,17 @@ void launch_pack(vmp_ctx *ctx, int64_t n, const void *x, const uint8_t *mask, ui
 }
 
 }  // namespace
+
+// the pass kernel for a.K, on nc chunks (vmp_common.h; vmp_mmm.hip calls it as well)
+void vmp_pmm_launch_pass(vmp_ctx *ctx, int64_t nc, bool hidden, const PmmArgs &a)
+{
+    switch (vmp_pmm_kpad(a.K) / 16) {
+    case 1: launch_pass<1>(ctx, nc, hidden, a); break;
+    case 2: launch_pass<2>(ctx, nc, hidden, a); break;
+    case 3: launch_pass<3>(ctx, nc, hidden, a); break;
+    default: launch_pass<4>(ctx, nc, hidden, a); break;
+    }
+}
 
 #define PMM_SHAPE(ctx, D, K)                                                                      \
     VMP_REQUIRE(ctx, K <= VMP_PMM_MAX_K && D <= VMP_PMM_MAX_D, VMP_ERR_UNSUPPORTED,               \
@@ -574,12 +541,7 @@ int32_t vmp_pmm_pass(vmp_ctx *ctx, int64_t N, int32_t D, int32_t K, int32_t hidd
     const int64_t nc = vmp_pmm_chunks(N, D, K);
     if (nc > 0) {
         PmmArgs a = {N, vmp_pmm_chunk_rows(N, D, K), D, K, x_packed, labels, l, lb, c, ws, r_out};
-        switch (vmp_pmm_kpad(K) / 16) {
-        case 1: launch_pass<1>(ctx, nc, hidden != 0, a); break;
-        case 2: launch_pass<2>(ctx, nc, hidden != 0, a); break;
-        case 3: launch_pass<3>(ctx, nc, hidden != 0, a); break;
-        default: launch_pass<4>(ctx, nc, hidden != 0, a); break;
-        }
+        vmp_pmm_launch_pass(ctx, nc, hidden != 0, a);
     }
     hipLaunchKernelGGL(pmm_combine_kernel, dim3((unsigned)((D * K + NT - 1) / NT)), dim3(NT), 0,
                        ctx->stream, nc, D, K, ws, S, hidden ? M : nullptr, Nk, scal);

@@ -178,6 +178,32 @@ __host__ __device__ inline uint16_t vmp_pmm_pack_i64(int64_t v, bool seen, int *
     return (seen && ok) ? (uint16_t)v : (uint16_t)VMP_PMM_HIDDEN;
 }
 
+// an entry of any dtype the pack takes: a double by vmp_pmm_pack_f64, every integer by
+// vmp_pmm_pack_i64
+__host__ __device__ inline uint16_t vmp_pmm_pack(double v, bool seen, int *bad)
+{
+    return vmp_pmm_pack_f64(v, seen, bad);
+}
+
+template <typename T>
+__host__ __device__ inline uint16_t vmp_pmm_pack(T v, bool seen, int *bad)
+{
+    return vmp_pmm_pack_i64((int64_t)v, seen, bad);
+}
+
+// entry e of an array by the dtype code of the pack entry points (0 double, 1 int64, 2 uint8,
+// otherwise int32)
+__host__ __device__ inline uint16_t vmp_pmm_pack_at(int dtype, const void *x, int64_t e, bool seen,
+                                                    int *bad)
+{
+    switch (dtype) {
+    case 0: return vmp_pmm_pack(((const double *)x)[e], seen, bad);
+    case 1: return vmp_pmm_pack(((const int64_t *)x)[e], seen, bad);
+    case 2: return vmp_pmm_pack(((const uint8_t *)x)[e], seen, bad);
+    default: return vmp_pmm_pack(((const int32_t *)x)[e], seen, bad);
+    }
+}
+
 // lgamma(x + 1) of a packed count; exactly zero for 0, 1 and a hidden entry.  Up to 20 the
 // factorial is an exact integer and its logarithm is rounded once; above, vmp_lgamma_dd.
 __host__ __device__ inline double vmp_pmm_lgamma1(uint16_t p)

@@ -25,16 +25,6 @@ int64_t pmm_workspace_doubles(int64_t N, int D, int K) { return vmp_pmm_workspac
 int64_t pmm_pack_span(int64_t n) { return vmp_pmm_pack_span(n); }
 int64_t pmm_pack_blocks(int64_t n) { return vmp_pmm_pack_blocks(n); }
 
-static uint16_t pack_one(int dtype, const void *x, int64_t e, bool seen, int *bad)
-{
-    switch (dtype) {
-    case 0: return vmp_pmm_pack_f64(((const double *)x)[e], seen, bad);
-    case 1: return vmp_pmm_pack_i64(((const int64_t *)x)[e], seen, bad);
-    case 2: return vmp_pmm_pack_i64((int64_t)((const uint8_t *)x)[e], seen, bad);
-    default: return vmp_pmm_pack_i64((int64_t)((const int32_t *)x)[e], seen, bad);
-    }
-}
-
 // xp (N x D), flags (3), counts (2), lgam (1)
 void pmm_pack(int64_t N, int D, int dtype, const void *x, const uint8_t *mask, uint16_t *xp,
               int32_t *flags, int64_t *counts, double *lgam)
@@ -50,7 +40,7 @@ void pmm_pack(int64_t N, int D, int dtype, const void *x, const uint8_t *mask, u
             for (int64_t i = t; i < span; i += VMP_PMM_NT) {
                 const int64_t e = b * span + i;
                 if (e >= n) break;
-                const uint16_t p = pack_one(dtype, x, e, mask ? mask[e] != 0 : true, &bad);
+                const uint16_t p = vmp_pmm_pack_at(dtype, x, e, mask ? mask[e] != 0 : true, &bad);
                 xp[e] = p;
                 vmp_pmm_sum_add(&lg, &lge, vmp_pmm_lgamma1(p));
                 hidden += vmp_pmm_observed(p) ? 0 : 1;
@@ -91,19 +81,21 @@ void pmm_tables(int D, int K, int form, const double *lam_mom, const double *elo
     for (int k = 0; k < K; ++k) c[k] = cs[k] - m;
 }
 
-// S, M (D x K; M only with hidden), Nk (K), scal[0] = sum lse; r_out (N x K) or null
-void pmm_pass(int64_t N, int D, int K, int hidden, const uint16_t *x, const int32_t *labels,
-              const double *l, const double *lb, const double *c, double *S, double *M, double *Nk,
-              double *scal, double *r_out)
+// what pmm_pass_kernel leaves: a partial per chunk, vmp_pmm_partial_doubles(D, K, hidden) apart --
+// S (K x D), with hidden entries M (K x D), N_k (K), sum lse; r_out (N x K) or null.  The pass of
+// tests/host/mmm_host.cpp starts here as well, as vmp_mmm_pass starts with that kernel.
+static std::vector<double> pmm_pass_partials(int64_t N, int D, int K, int hidden, const uint16_t *x,
+                                             const int32_t *labels, const double *l,
+                                             const double *lb, const double *c, double *r_out)
 {
-    const int KP = vmp_pmm_kpad(K);
+    const int KP = vmp_pmm_kpad(K), ns = hidden ? 2 : 1;
     const int64_t chunk = vmp_pmm_chunk_rows(N, D, K), nc = vmp_pmm_chunks(N, D, K);
-    const int64_t per = vmp_pmm_partial_doubles(D, K, 1), DK = (int64_t)D * K;
+    const int64_t per = vmp_pmm_partial_doubles(D, K, hidden), DK = (int64_t)D * K;
     std::vector<double> part((size_t)(nc * per), 0.0);
     double logit[VMP_PMM_MAX_K], ex[VMP_PMM_MAX_K], r[VMP_PMM_MAX_K], v[16];
     for (int64_t ch = 0; ch < nc; ++ch) {
         const int64_t r0 = ch * chunk, r1 = r0 + chunk < N ? r0 + chunk : N;
-        double *p1 = part.data() + ch * per, *p2 = p1 + DK;             // [k][d]
+        double *p1 = part.data() + ch * per, *p2 = p1 + DK;             // [k][d]; p2 with hidden
         std::vector<double> nk(16 * K, 0.0), t1((size_t)DK), t2((size_t)DK);
         double ls[16] = {0};
         for (int64_t row = r0; row < r1; ++row) {
@@ -164,34 +156,46 @@ void pmm_pass(int64_t N, int D, int K, int hidden, const uint16_t *x, const int3
             if ((row - r0) % VMP_PMM_TILE == VMP_PMM_TILE - 1 || row == r1 - 1)
                 for (int64_t i = 0; i < DK; ++i) {            // the tile's sums, in tile order
                     p1[i] += t1[i];
-                    p2[i] += t2[i];
+                    if (hidden) p2[i] += t2[i];
                 }
         }
         for (int k = 0; k < K; ++k) {
             double t = 0.0;
             for (int s = 0; s < 16; ++s) t += nk[s * K + k];
-            p1[2 * DK + k] = t;
+            p1[ns * DK + k] = t;
         }
         double t = 0.0;
         for (int s = 0; s < 16; ++s) t += ls[s];
-        p1[2 * DK + K] = t;
+        p1[ns * DK + K] = t;
     }
+    return part;
+}
+
+// S, M (D x K; M only with hidden), Nk (K), scal[0] = sum lse; r_out (N x K) or null
+void pmm_pass(int64_t N, int D, int K, int hidden, const uint16_t *x, const int32_t *labels,
+              const double *l, const double *lb, const double *c, double *S, double *M, double *Nk,
+              double *scal, double *r_out)
+{
+    const std::vector<double> part = pmm_pass_partials(N, D, K, hidden, x, labels, l, lb, c, r_out);
+    const int ns = hidden ? 2 : 1;
+    const int64_t nc = vmp_pmm_chunks(N, D, K);
+    const int64_t per = vmp_pmm_partial_doubles(D, K, hidden), DK = (int64_t)D * K;
     for (int k = 0; k < K; ++k) {
         double n = 0.0;
-        for (int64_t ch = 0; ch < nc; ++ch) n += part[ch * per + 2 * DK + k];
+        for (int64_t ch = 0; ch < nc; ++ch) n += part[ch * per + ns * DK + k];
         Nk[k] = n;
         for (int d = 0; d < D; ++d) {
             double s = 0.0, m = 0.0;
             for (int64_t ch = 0; ch < nc; ++ch) {
                 s += part[ch * per + k * D + d];
-                m += part[ch * per + DK + k * D + d];
+                if (hidden) m += part[ch * per + DK + k * D + d];
             }
             S[d * K + k] = s;
             if (hidden) M[d * K + k] = m;
         }
     }
     double t = 0.0;
-    for (int64_t ch = 0; ch < nc; ++ch) t += part[ch * per + 2 * DK + K];
+    for (int64_t ch = 0; ch < nc; ++ch) t += part[ch * per + ns * DK + K];
     scal[0] = t;
 }
 

@@ -20,8 +20,9 @@ from dgmm_host import _special, tolerances, error            # noqa: F401
 DTYPES = {'float64': 0, 'int64': 1, 'uint8': 2, 'int32': 3}
 MAX_COUNT = 65534
 PASS_QUANTITIES = ('r', 'Nk', 'S', 'sum_lse', 'Nk_c', 'S_L')
-HEADERS = ['bayespy_amd/csrc/vmp_mmm_dev.h', 'bayespy_amd/csrc/vmp_pmm_dev.h',
-           'bayespy_amd/csrc/vmp_dgmm_masked_dev.h', 'bayespy_amd/csrc/vmp_dgmm_dev.h']
+HEADERS = ['tests/host/pmm_host.cpp', 'bayespy_amd/csrc/vmp_mmm_dev.h',
+           'bayespy_amd/csrc/vmp_pmm_dev.h', 'bayespy_amd/csrc/vmp_dgmm_masked_dev.h',
+           'bayespy_amd/csrc/vmp_dgmm_dev.h']
 
 
 @functools.lru_cache(None)

@@ -157,6 +157,38 @@ def test_bit_identity(N, M, K):
         np.testing.assert_array_equal(a[key], n[key], err_msg=key)
 
 
+@pytest.mark.parametrize('fixed', [False, True], ids=['soft', 'labels'])
+@pytest.mark.parametrize('N,M,K', [(65, 65, 17), (257, 129, 16), (763, 257, 64), (0, 70, 5)])
+def test_the_pass_is_the_poisson_pass(N, M, K, fixed):
+    """vmp_mmm_pass runs the Poisson block's pass kernel: on the same packed x, L and c,
+    vmp_pmm_pass(hidden = 0, l = L, lb = zeros) gives the same bits of N_k, sum lse, r_out and S
+    (its D x K transposed).  scal[1] and scal[2] are added in another order there and are left out.
+    The shapes: a ragged second tile with K padded into a second lane group; a second chunk and a
+    second word block (the carry through the partial, and fixed labels skipping the logit walk);
+    KT = 4 with three blocks and three chunks; no rows (the combine alone)."""
+    from bayespy_amd.inference.plans.pmm import PMMKernels
+    from mmm_host import pass_inputs, host_tables
+    inp = pass_inputs(N, M, K)
+    L, c = host_tables(M, K, inp['elog_p'], inp['elog_pi'])
+    labels = inp['labels'] if fixed else None
+    pk = _device_pack(N, M, inp['x'], inp['trials'])
+    got = _device_pass(N, M, K, pk['dev'], L, c, labels=labels, want_r=True)
+    rt, _ = _kernels()
+    k = PMMKernels(rt)
+    S, Nk, scal = rt.empty(M, K), rt.empty(K), rt.zeros(8)
+    ws = rt.empty(int(k.plan(N, M, K)[1]))
+    r = rt.empty(N, K) if N else None
+    lab = None if labels is None else _up(rt, labels.astype(np.int32))
+    k.pass_(N, M, K, 0, pk['dev'], lab, _up(rt, L), rt.zeros(M, K), _up(rt, c), ws, S, None, Nk,
+            scal, r)
+    rt.synchronize()
+    np.testing.assert_array_equal(got['Nk'], Nk.cpu().numpy())
+    np.testing.assert_array_equal(got['sum_lse'], scal.cpu().numpy()[0])
+    np.testing.assert_array_equal(got['S'], S.cpu().numpy().T)
+    if N:
+        np.testing.assert_array_equal(got['r'], r.cpu().numpy())
+
+
 def test_pack_flags_and_the_cap():
     from mmm_host import pass_inputs
     N, M, K = MID
