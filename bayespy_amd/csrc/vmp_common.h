@@ -56,8 +56,8 @@ struct vmp_ctx {
     double *sweep_ctl;
     int64_t sweeps_enqueued;
     // ... and the ticket words of the one-launch sweeps (pca_sweep_mid_kernel): one 32-bit word per
-    // sweep of a chunk, cleared ahead of the chunk's first launch, never reused within a chunk;
-    // launches of that kernel so far
+    // sweep of a chunk, cleared when they are allocated and put back to zero by every launch that
+    // draws from them, never reused within a chunk; launches of that kernel so far
     unsigned int *sweep_tickets;
     int64_t sweep_mid_launches;
     // wall_clock64 stamps of those launches, VMP_SWEEP_NSTAMP words per sweep of the latest chunk:
@@ -116,12 +116,17 @@ int32_t vmp_pca_launch_sweep_tail(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_
                                   const vmp_sweep_tail &t);
 
 // sweeps 1 .. n-1 of a chunk: Gram statistics, tail and the next sweep's head in ONE launch of DP / 8
-// workgroups (pca_sweep_mid_kernel, vmp_pca_small.hip); `ticket` is the sweep's own zeroed word,
-// `wide` selects the wide tail and head of phase B, `stamps` (null: none) the stamped build and its row
+// workgroups (pca_sweep_mid_kernel, vmp_pca_small.hip); `ticket` is the sweep's own zeroed word, which
+// the launch leaves zero again; `wide` = 1 selects the wide tail and head of phase B, 2 those and sum
+// <x><x>^T formed by the tail ("pca_sweep_local_pxx"); `stamps` (null: none) the stamped build and its row
 int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                                  double a0t, double b0t, double a0a, double b0a, double *state,
                                  double *P, const vmp_sweep_tail &t, unsigned int *ticket, int32_t wide,
                                  unsigned long long *stamps);
+// the first head of a chunk by the wide head body, for a GPU with no latent pass in flight
+int32_t vmp_pca_launch_sweep_head_wide(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total,
+                                       double x_prec, double a0t, double b0t, double a0a, double b0a,
+                                       double *state);
 // the Gram statistics of that kernel alone: Syx rows into the state, DP / 8 partial blocks into P
 int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P,
                                  int32_t wide);

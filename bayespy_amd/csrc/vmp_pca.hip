@@ -1347,7 +1347,12 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
     // the stamped build of the mid kernel, a measurement (tools/sweep_stamps.py).
     const bool ticket = n > 1 && ((uintptr_t)state % 16) == 0 &&
                         vmp_tune_get("pca_sweep_ticket", env_int("VMP_PCA_SWEEP_TICKET", 1, 0, 1));
-    const int wide = vmp_tune_get("pca_sweep_wide", env_int("VMP_PCA_SWEEP_WIDE", 1, 0, 1));
+    // "pca_sweep_local_pxx" = 0 (VMP_PCA_SWEEP_LOCAL_PXX=0), with the wide bodies: phase A stores its
+    // partial block of sum <x><x>^T and the tail adds the blocks, instead of the tail forming the sum
+    // from the A and the Syx rows it holds in LDS (the same bits).
+    int wide = vmp_tune_get("pca_sweep_wide", env_int("VMP_PCA_SWEEP_WIDE", 1, 0, 1)) ? 1 : 0;
+    if (wide && vmp_tune_get("pca_sweep_local_pxx", env_int("VMP_PCA_SWEEP_LOCAL_PXX", 1, 0, 1)))
+        wide = 2;
     const bool stamps = ticket && vmp_tune_get("pca_sweep_stamps", 0);
     if (stamps) {
         const size_t bytes = (size_t)VMP_PCA_MAX_SWEEPS * VMP_SWEEP_NSTAMP * sizeof(unsigned long long);
@@ -1358,18 +1363,34 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
         ctx->sweep_stamp_rows = n - 1;
     }
     if (ticket) {
-        if (!ctx->sweep_tickets)
+        // cleared once, here: every launch that draws from a word leaves it zero for the next one on
+        // this stream (pca_sweep_mid_body), so a chunk needs no memset of its own
+        if (!ctx->sweep_tickets) {
             VMP_HIP_CHECK(ctx, hipMalloc(&ctx->sweep_tickets,
                                          VMP_PCA_MAX_SWEEPS * sizeof(unsigned int)));
-        VMP_HIP_CHECK(ctx, hipMemsetAsync(ctx->sweep_tickets, 0, (size_t)(n - 1) * sizeof(unsigned int),
-                                          ctx->stream));
+            VMP_HIP_CHECK(ctx, hipMemsetAsync(ctx->sweep_tickets, 0,
+                                              VMP_PCA_MAX_SWEEPS * sizeof(unsigned int), ctx->stream));
+        }
+    }
+    // The first head of the chunk runs before the chunk's pass is described.  With no latent pass of
+    // an earlier call in flight either it has the GPU to itself and takes the wide body (its LDS
+    // would not be placed beside a running pass); otherwise pca_head_fast_kernel.
+    // (a held pass is a description, not a launch; both heads leave the same bits)
+    bool head_wide = ticket && wide;
+    if (head_wide && ctx->x_pending) {
+        head_wide = hipEventQuery(ctx->ev_xdone) == hipSuccess;
+        (void)hipGetLastError();        // ("not ready" is an answer, not an error of this call)
     }
     for (int i = 0; i < n; ++i) {
         // the first sweep of the batch reads no stop word: whatever an earlier batch left is stale
         const double *stop = i == 0 ? nullptr : ctx->sweep_ctl;
         const bool last = i + 1 == n;
         // the head of this sweep: its own launch, unless the mid launch of sweep i - 1 has run it
-        if (!ticket || i == 0) {
+        if (i == 0 && head_wide) {
+            rc = vmp_pca_launch_sweep_head_wide(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
+                                                b0_alpha, state);
+            if (rc != VMP_OK) return rc;
+        } else if (!ticket || i == 0) {
             rc = vmp_pca_launch_sweep_head(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
                                            b0_alpha, state, stop);
             if (rc != VMP_OK) return rc;

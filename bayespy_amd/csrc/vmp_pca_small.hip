@@ -168,7 +168,7 @@ __device__ __forceinline__ void sweep_inverse(double *M, int n, double *logdet, 
 // thread 0 keeps them in LDS and the workgroup that runs phase B copies them out at its end.  The
 // default kernels are instantiated with stamps_off, which is empty.
 enum { SP_ENTRY = 0, SP_LDS_FILLED, SP_SYX, SP_PXX, SP_TICKET, SP_ACQUIRE,
-       SP_T_PARTIALS, SP_T_LOADS, SP_T_BLOCKSUMS, SP_T_TAU_ALPHA, SP_T_BOUND, SP_T_RING,
+       SP_T_PARTIALS, SP_T_LOADS, SP_T_PXX, SP_T_BLOCKSUMS, SP_T_TAU_ALPHA, SP_T_BOUND, SP_T_RING,
        SP_H_LAMBDA, SP_H_INV1, SP_H_W, SP_H_SWW, SP_H_INV2, SP_H_A, SP_COUNT };
 static_assert(SP_COUNT <= VMP_SWEEP_NSTAMP, "stamp row length");
 struct stamps_off {
@@ -801,6 +801,7 @@ pca_head_fast_kernel(small_args a, double *st, const double *stop)
 // that kernel); and after the bound it writes the sweep's ring slot, evaluates the loop's stop
 // rule (vmp_stop_rule.h) and leaves the stop word and the bound for the next sweep.
 constexpr int GB = 32;            // rows of G per batch
+constexpr int GRA = 8;            // rows of G per workgroup of the Gram statistics (one partial block)
 constexpr int TAIL_PLAIN = 0, TAIL_GRAM = 1, TAIL_SWEEP = 2;
 // LDS of the tail (a struct: pca_sweep_mid_kernel hands Cx, Sx, al and sc on to the next head)
 template <int KP>
@@ -819,19 +820,25 @@ static_assert(sizeof(tail_lds<16>) % 16 == 0 && sizeof(tail_lds<32>) % 16 == 0, 
 // placement does not bind): every load of the tail is issued before the partial blocks are added, and
 // the rows of sum y<x>^T go on to the next head in SW (FAST_D x (KP+1) doubles of LDS, columns >= K and
 // rows >= D zero) instead of being loaded a second time there.  Same expressions, same order of sums.
-template <int KP, int MODE, bool WIDE = false, class STAMP = stamps_off>
+// LOCAL ("pca_sweep_local_pxx", a wide tail): no partial blocks were stored.  sum <x><x>^T is formed
+// here from the rows of sum y<x>^T in SW and from the A that phase A of this workgroup left in LDS
+// (AL, KP rows DP + 2 doubles apart) -- every group's partial by the chain of gram_phase_a_wide, the
+// partials added in the order of the loop below.  The stop word is not read a second time: the
+// launch read it at entry, and no workgroup of a launch writes it before the tail of that launch.
+template <int KP, int MODE, bool WIDE = false, class STAMP = stamps_off, bool LOCAL = false>
 __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, const vmp_sweep_tail *sw,
                                               tail_lds<KP> &s, double *SW = nullptr,
-                                              const STAMP &stamp = STAMP())
+                                              const STAMP &stamp = STAMP(), const double *AL = nullptr)
 {
     static_assert(!WIDE || MODE == TAIL_SWEEP, "the wide tail is a sweep tail");
+    static_assert(!LOCAL || WIDE, "sum <x><x>^T is formed locally by the wide tail only");
     constexpr bool GRAM = (MODE == TAIL_GRAM);
     constexpr int LDM = KP + 1, E = KP * KP / NTF;
     extern __shared__ __align__(16) double gl[];          // GRAM: A (KP x (DP+1)) | G batch (GB x (DP+1)) | S batch (GB x LDM)
     double *Sw = s.Sw, *Cx = s.Cx, *Sx = s.Sx, *al = s.al, *sc = s.sc, *red = s.red;
     const lay32 L(a.L);
     const int tid = threadIdx.x, D = a.D, K = a.K;
-    if constexpr (MODE == TAIL_SWEEP) {
+    if constexpr (MODE == TAIL_SWEEP && !LOCAL) {
         if (!sw->first && sw->ctl[VMP_SWEEP_STOP] != 0.0) {
             if (tid == 0) {
                 sw->slot[7] = 0.0;                     // not executed
@@ -865,7 +872,9 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             es1[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
         }
     }
-    if constexpr (WIDE) {
+    if constexpr (LOCAL) {
+        // (formed below, once the rows of sum y<x>^T are in SW)
+    } else if constexpr (WIDE) {
         // sum <x><x>^T = sum_b P[b]: the adds of the loop below in the same order, from ONE batch of
         // loads (nb <= FAST_D / 8) -- that loop waits for four loads at a time, nb / 4 round trips
         // in a row for each of the E elements of a thread
@@ -914,7 +923,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             st[L.off_S + L.DP * KP + e] = sxx[m];
         }
     }
-    stamp(SP_T_PARTIALS);
+    if constexpr (!LOCAL) stamp(SP_T_PARTIALS);
     if constexpr (GRAM) {
         const int DP = L.DP, LA = DP + 1;
         double *As = gl, *Gs = As + KP * LA, *Ss = Gs + GB * LA;
@@ -995,7 +1004,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             const int i = e / KP, j = e % KP;
             Sw[i * LDM + j] = v0[m];
             Cx[i * LDM + j] = v1[m];
-            Sx[i * LDM + j] = v2[m];
+            if constexpr (!LOCAL) Sx[i * LDM + j] = v2[m];
         }
     }
     // sum(W o Syx): padded entries of W are zero, so the D x KP blocks are walked linearly
@@ -1003,7 +1012,8 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
         // the same products in the same order as the loop below, which runs whole passes of 8 per
         // thread; the rows go to SW as the head would have loaded them (zero beyond D and K)
         const int n = D * KP, jn = (n + 8 * NTF - 1) / (8 * NTF) * 8;
-        const int nsw = (D + 31) / 32 * 32 * KP;       // whole 32-row blocks, at most DP rows
+        // (LOCAL: all DP rows, which the sum over the DP / 8 groups below walks)
+        const int nsw = LOCAL ? L.DP * KP : (D + 31) / 32 * 32 * KP;   // whole 32-row blocks, at most DP rows
 #pragma unroll
         for (int j = 0; j < NW; ++j) {
             const int e = tid + j * NTF;
@@ -1028,6 +1038,83 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
     (void)ww; (void)wy; (void)es0; (void)es1;
     __syncthreads();
     stamp(SP_T_LOADS);
+    if constexpr (LOCAL) {
+        // sum <x><x>^T [k][k'] = sum_b Pxx_b[k][k'], Pxx_b[k][k'] = sum_{r in group b} A[k][r] Syx[r][k']:
+        // each partial its own chain of multiply-adds from zero over the 8 rows in ascending order
+        // (gram_phase_a_wide), the partials added four at a time as above (reduce_partials_kernel).
+        // A thread owns the outputs (ki + 16 i, ji + 16 j): at KP = 32 four multiply-adds share two
+        // 16-byte reads of A (4 rows per wavefront, 4 banks apart) and two reads of a row of SW.
+        constexpr int B = KP / 16;
+        const int LA = L.DP + 2;
+        const int ki = tid >> 4, ji = tid & 15;
+        const int nb = sw->nb, nb4 = nb & ~3;
+        const double *ar = AL + ki * LA, *sr = SW + ji;
+        double acc[4][B][B];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int i = 0; i < B; ++i)
+#pragma unroll
+                for (int j = 0; j < B; ++j) acc[q][i][j] = 0.0;
+        const auto group = [&](int b, double (&p)[B][B]) {
+#pragma unroll
+            for (int i = 0; i < B; ++i)
+#pragma unroll
+                for (int j = 0; j < B; ++j) p[i][j] = 0.0;
+#pragma unroll
+            for (int r = 0; r < GRA; r += 2) {
+                v2f64 x[B];
+                double y0[B], y1[B];
+#pragma unroll
+                for (int i = 0; i < B; ++i)
+                    x[i] = *reinterpret_cast<const v2f64 *>(ar + 16 * i * LA + b * GRA + r);
+#pragma unroll
+                for (int j = 0; j < B; ++j) {
+                    y0[j] = sr[(b * GRA + r) * LDM + 16 * j];
+                    y1[j] = sr[(b * GRA + r + 1) * LDM + 16 * j];
+                }
+#pragma unroll
+                for (int i = 0; i < B; ++i)
+#pragma unroll
+                    for (int j = 0; j < B; ++j) {
+                        p[i][j] = __builtin_fma(x[i][0], y0[j], p[i][j]);
+                        p[i][j] = __builtin_fma(x[i][1], y1[j], p[i][j]);
+                    }
+            }
+        };
+        double p[B][B];
+#pragma unroll 1
+        for (int b = 0; b < nb4; b += 4) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                group(b + q, p);
+#pragma unroll
+                for (int i = 0; i < B; ++i)
+#pragma unroll
+                    for (int j = 0; j < B; ++j) acc[q][i][j] += p[i][j];
+            }
+        }
+#pragma unroll 1
+        for (int b = nb4; b < nb; ++b) {
+            group(b, p);
+#pragma unroll
+            for (int i = 0; i < B; ++i)
+#pragma unroll
+                for (int j = 0; j < B; ++j) acc[0][i][j] += p[i][j];
+        }
+#pragma unroll
+        for (int i = 0; i < B; ++i)
+#pragma unroll
+            for (int j = 0; j < B; ++j) {
+                const int k = ki + 16 * i, k2 = ji + 16 * j;
+                const bool in = (k < K && k2 < K);
+                const double x = in ? (acc[0][i][j] + acc[1][i][j]) + (acc[2][i][j] + acc[3][i][j]) : 0.0;
+                st[L.off_S + (L.DP + k) * KP + k2] = x;
+                Sx[k * LDM + k2] = x;
+            }
+        __syncthreads();
+        stamp(SP_T_PXX);
+    }
     double t2 = 0.0, trx = 0.0;
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -1159,8 +1246,6 @@ pca_tail_sweep_kernel(small_args a, double *st, vmp_sweep_tail sw)
 // shifts instead of a division per element, and a thread owns a 2 x 2 block of (row, column)
 // outputs, so that four multiply-adds share four LDS reads instead of eight.
 // ---------------------------------------------------------------------------
-constexpr int GRA = 8;
-
 __host__ __device__ inline size_t gram_phase_a_lds(int KP, int DP)
 {
     return ((size_t)KP * (DP + 1) + (size_t)GRA * DP + (size_t)GRA * (KP + 1)) * sizeof(double);
@@ -1258,7 +1343,8 @@ __host__ __device__ inline size_t gram_phase_a_wide_lds(int KP, int DP)
     return ((size_t)KP * (DP + 2) + (size_t)GRA * DP + (size_t)GRA * (KP + 1)) * sizeof(double);
 }
 
-template <int KP, class STAMP = stamps_off>
+// PXX = false ("pca_sweep_local_pxx"): the phase ends with the Syx rows; A stays in LDS for the tail
+template <int KP, class STAMP = stamps_off, bool PXX = true>
 __device__ __forceinline__ void gram_phase_a_wide(const vmp_pca_layout &L, int D, int K, double *st,
                                                   double *P, double *lds, int blk,
                                                   const STAMP &stamp = STAMP())
@@ -1316,18 +1402,21 @@ __device__ __forceinline__ void gram_phase_a_wide(const vmp_pca_layout &L, int D
     }
     __syncthreads();
     stamp(SP_SYX);
-    // Pxx_b[k][k'] = sum_{r in group} A[k][r] Syx[r][k']  (added up in fixed order by the tail)
-    double *Pb = P + (int64_t)blk * KP * KP;
+    if constexpr (PXX) {
+        // Pxx_b[k][k'] = sum_{r in group} A[k][r] Syx[r][k']  (added up in fixed order by the tail)
+        double *Pb = P + (int64_t)blk * KP * KP;
 #pragma unroll
-    for (int m = 0; m < E; ++m) {
-        const int e = tid + m * NTF;
-        const int k = e / KP, k2 = e % KP;
-        double s = 0.0;
-        if (k < K && k2 < K) {
+        for (int m = 0; m < E; ++m) {
+            const int e = tid + m * NTF;
+            const int k = e / KP, k2 = e % KP;
+            double s = 0.0;
+            if (k < K && k2 < K) {
 #pragma unroll
-            for (int r = 0; r < GRA; ++r) s = __builtin_fma(As[k * LA + r0 + r], Ss[r * LDS_S + k2], s);
+                for (int r = 0; r < GRA; ++r)
+                    s = __builtin_fma(As[k * LA + r0 + r], Ss[r * LDS_S + k2], s);
+            }
+            Pb[e] = s;
         }
-        Pb[e] = s;
     }
 }
 
@@ -1346,7 +1435,12 @@ pca_gram_wide_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
 // that draws nb - 1 knows that every other workgroup's Syx rows and Pxx block are released, acquires
 // once and reads them with plain loads.  A ticket is drawn once and nobody waits for anybody: the
 // other workgroups return, so there is no order of dispatch in which the launch cannot finish.
-// `ticket` is this sweep's own word, zero at the launch (one memset per chunk, vmp_pca_sweeps).
+// `ticket` is this sweep's own word, zero at the launch: vmp_pca_sweeps clears the words once, when
+// it allocates them, and the workgroup that draws nb - 1 -- the only one of its launch that is still
+// running, after every other draw -- stores 0 again.  The next launch that draws from the word is a
+// later one on the same stream (the same sweep of a later chunk): launches of a stream run in
+// order and each sees the stores of those before it, so it finds 0.  A launch that returns at
+// entry because the loop has stopped draws nothing and leaves the 0 it found.
 // This kernel never runs beside a latent pass (no pass is in flight during held sweeps), so the
 // placement budget of pca_head_fast_kernel does not bind it.
 // The head of the next sweep as phase B runs it when "pca_sweep_wide" is on: pca_head_body without
@@ -1492,11 +1586,20 @@ __device__ __forceinline__ void pca_head_wide(const small_args &a, double *st, d
     stamp(SP_H_A);
 }
 
-template <int KP, bool WIDE, class STAMP>
+// the dynamic LDS of the one-launch sweep with LOCAL: A (phase A, kept for the tail) | the G rows and
+// the Syx block of phase A, then the DP rows of SW | the ticket word, which gets 16 bytes of its own
+// so that A survives the draw
+__host__ __device__ inline size_t sweep_local_lds(int KP, int DP)
+{
+    return ((size_t)KP * (DP + 2) + (size_t)DP * (KP + 1) + 2) * sizeof(double);
+}
+
+template <int KP, bool WIDE, bool LOCAL, class STAMP>
 __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *st, double *P,
                                                    const vmp_sweep_tail &sw, unsigned int *ticket,
                                                    const STAMP &stamp)
 {
+    static_assert(!LOCAL || WIDE, "sum <x><x>^T is formed locally beside the wide bodies only");
     extern __shared__ __align__(16) double gl[];
     __shared__ tail_lds<KP> ts;
     const int tid = threadIdx.x;
@@ -1510,14 +1613,17 @@ __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *
     }
     stamp(SP_ENTRY);
     if constexpr (WIDE)
-        gram_phase_a_wide<KP>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
+        gram_phase_a_wide<KP, STAMP, !LOCAL>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
     else
         gram_phase_a<KP>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     stamp(SP_PXX);
-    unsigned int *word = reinterpret_cast<unsigned int *>(gl);     // (phase A's LDS is free now)
-    if (tid == 0) {
+    // LOCAL: SW lies behind A, over the G rows and the Syx block of phase A, the ticket word behind SW
+    const int na = LOCAL ? KP * ((int)a.L.DP + 2) : 0;
+    double *SW = gl + na;
+    unsigned int *word = reinterpret_cast<unsigned int *>(LOCAL ? SW + (int)a.L.DP * (KP + 1) : gl);
+    if (tid == 0) {                                                // (phase A's LDS is free now)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         *word = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1528,33 +1634,37 @@ __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *
     if (tid == 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // every other workgroup of the launch has drawn: the word is this workgroup's alone, and it
+        // goes back to 0 for the next launch that uses it (see above; also when the tail stops the loop)
+        *ticket = 0u;
     }
     __syncthreads();
     stamp(SP_ACQUIRE);
     // (every thread has read the ticket word: the dynamic region is free for SW)
-    pca_tail_body<KP, TAIL_SWEEP, WIDE>(a, st, &sw, ts, gl, stamp);
+    pca_tail_body<KP, TAIL_SWEEP, WIDE, STAMP, LOCAL>(a, st, &sw, ts, SW, stamp, gl);
     __syncthreads();
     if (ts.stop != 0.0) return;
-    // Cov_X, sum <x><x>^T, <alpha> and <tau> go over in LDS.  WIDE: so do the Syx rows (in gl);
+    // Cov_X, sum <x><x>^T, <alpha> and <tau> go over in LDS.  WIDE: so do the Syx rows (in SW);
     // otherwise the head loads them -- phase A wrote them, acquired above -- and reads back its own <W>
     if constexpr (WIDE)
-        pca_head_wide<KP>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], gl, stamp);
+        pca_head_wide<KP>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], SW, stamp);
     else
         pca_head_body<KP, true>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], stamp);
 }
 
 // WIDE: phase B runs the wide tail and head ("pca_sweep_wide", default); false: pca_tail_body and
-// pca_head_body as the three-launch sweep runs them
-template <int KP, bool WIDE>
+// pca_head_body as the three-launch sweep runs them.  LOCAL ("pca_sweep_local_pxx", default, with
+// WIDE): no partial blocks of sum <x><x>^T are stored, the tail forms the sum from LDS.
+template <int KP, bool WIDE, bool LOCAL>
 __global__ void __launch_bounds__(NTF)
 pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, unsigned int *ticket)
 {
-    pca_sweep_mid_body<KP, WIDE>(a, st, P, sw, ticket, stamps_off());
+    pca_sweep_mid_body<KP, WIDE, LOCAL>(a, st, P, sw, ticket, stamps_off());
 }
 
 // the same with wall_clock64 stamps ("pca_sweep_stamps"): `out` is this launch's row of
 // VMP_SWEEP_NSTAMP words, written by the workgroup that ran phase B
-template <int KP, bool WIDE>
+template <int KP, bool WIDE, bool LOCAL>
 __global__ void __launch_bounds__(NTF)
 pca_sweep_mid_stamped_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw,
                              unsigned int *ticket, unsigned long long *out)
@@ -1563,10 +1673,54 @@ pca_sweep_mid_stamped_kernel(small_args a, double *st, double *P, vmp_sweep_tail
     if (threadIdx.x < VMP_SWEEP_NSTAMP) stl[threadIdx.x] = 0;
     __syncthreads();
     const stamps_on stamp{stl};
-    pca_sweep_mid_body<KP, WIDE>(a, st, P, sw, ticket, stamp);
+    pca_sweep_mid_body<KP, WIDE, LOCAL>(a, st, P, sw, ticket, stamp);
     // (a workgroup that did not run phase B leaves no tail stamp)
-    if (threadIdx.x == 0 && stl[SP_T_PARTIALS] != 0)
+    if (threadIdx.x == 0 && stl[SP_T_LOADS] != 0)
         for (int i = 0; i < VMP_SWEEP_NSTAMP; ++i) out[i] = stl[i];
+}
+
+// The first head of a chunk (vmp_pca_sweeps, "pca_sweep_wide" on, no latent pass in flight): the
+// wide head body in a launch of its own.  What the tail of a mid launch hands over in LDS -- Cov_X,
+// sum <x><x>^T, <alpha>, <tau> and the rows of sum y<x>^T -- is loaded from the state, masked as
+// pca_head_body masks its loads.
+template <int KP>
+__global__ void __launch_bounds__(NTF)
+pca_head_wide_kernel(small_args a, double *st)
+{
+    constexpr int LDM = KP + 1, E = KP * KP / NTF, NW = FAST_D * KP / NTF;
+    __shared__ __align__(16) double M[KP * LDM], T[KP * LDM], SW[FAST_D * LDM], alm[KP];
+    const lay32 L(a.L);
+    const int tid = threadIdx.x, D = a.D, K = a.K;
+    const int n = D * KP, nsw = (D + 31) / 32 * 32 * KP;
+    double cx[E], sx[E], wy[NW];
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int e = tid + m * NTF;
+        const int i = e / KP, j = e % KP;
+        const bool in = (i < K && j < K);
+        cx[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
+        sx[m] = in ? st[L.off_S + (L.DP + i) * KP + j] : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        const int e = tid + j * NTF;
+        wy[j] = (e < n && e % KP < K) ? st[L.off_S + e] : 0.0;
+    }
+    const double tau = st[L.off_tau + 2];
+    if (tid < KP) alm[tid] = tid < K ? st[L.off_alpha + 2 * KP + tid] : 0.0;
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int e = tid + m * NTF;
+        M[(e / KP) * LDM + (e % KP)] = cx[m];
+        T[(e / KP) * LDM + (e % KP)] = sx[m];
+    }
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        const int e = tid + j * NTF;
+        if (e < nsw) SW[(e / KP) * LDM + (e % KP)] = wy[j];
+    }
+    __syncthreads();
+    pca_head_wide<KP>(a, st, M, T, alm, tau, SW, stamps_off());
 }
 
 bool fast_small_enabled()
@@ -1809,28 +1963,30 @@ int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *sta
 }
 
 // one instantiation of the one-launch sweep; `stamps` (null: the default kernel) is the launch's row
-template <int KP, bool WIDE>
+template <int KP, bool WIDE, bool LOCAL>
 static int32_t launch_mid(vmp_ctx *ctx, const small_args &a, double *state, double *P,
                           const vmp_sweep_tail &t, unsigned int *ticket, unsigned long long *stamps)
 {
     static bool raised[2][64] = {{false}};
     const int dev = ctx->device & 63, s = stamps ? 1 : 0;
     if (!raised[s][dev]) {
-        const void *f = stamps ? (const void *)pca_sweep_mid_stamped_kernel<KP, WIDE>
-                               : (const void *)pca_sweep_mid_kernel<KP, WIDE>;
+        const void *f = stamps ? (const void *)pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL>
+                               : (const void *)pca_sweep_mid_kernel<KP, WIDE, LOCAL>;
         VMP_HIP_CHECK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                96 * 1024));
         raised[s][dev] = true;
     }
-    // (the rows of SW the wide bodies keep fit in phase A's region: DP (KP + 1) doubles at most)
-    const size_t lds = WIDE ? gram_phase_a_wide_lds((int)a.L.KP, (int)a.L.DP)
-                            : gram_phase_a_lds((int)a.L.KP, (int)a.L.DP);
+    // (the rows of SW the wide bodies keep fit in phase A's region: DP (KP + 1) doubles at most;
+    // LOCAL keeps A beside them, 67 KB at KP = 32, DP = 128)
+    const size_t lds = LOCAL ? sweep_local_lds((int)a.L.KP, (int)a.L.DP)
+                       : WIDE ? gram_phase_a_wide_lds((int)a.L.KP, (int)a.L.DP)
+                              : gram_phase_a_lds((int)a.L.KP, (int)a.L.DP);
     const dim3 nb((unsigned)(a.L.DP / GRA));
     if (stamps)
-        hipLaunchKernelGGL((pca_sweep_mid_stamped_kernel<KP, WIDE>), nb, dim3(NTF), lds, ctx->stream, a,
+        hipLaunchKernelGGL((pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL>), nb, dim3(NTF), lds, ctx->stream, a,
                            state, P, t, ticket, stamps);
     else
-        hipLaunchKernelGGL((pca_sweep_mid_kernel<KP, WIDE>), nb, dim3(NTF), lds, ctx->stream, a, state,
+        hipLaunchKernelGGL((pca_sweep_mid_kernel<KP, WIDE, LOCAL>), nb, dim3(NTF), lds, ctx->stream, a, state,
                            P, t, ticket);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
@@ -1845,10 +2001,27 @@ int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_t
     const int32_t rc = fill_small_args(ctx, a, D, K, n_total, x_prec, a0t, b0t, a0a, b0a);
     if (rc != VMP_OK) return rc;
     if (a.L.KP == 16)
-        return wide ? launch_mid<16, true>(ctx, a, state, P, t, ticket, stamps)
-                    : launch_mid<16, false>(ctx, a, state, P, t, ticket, stamps);
-    return wide ? launch_mid<32, true>(ctx, a, state, P, t, ticket, stamps)
-                : launch_mid<32, false>(ctx, a, state, P, t, ticket, stamps);
+        return wide == 2 ? launch_mid<16, true, true>(ctx, a, state, P, t, ticket, stamps)
+               : wide    ? launch_mid<16, true, false>(ctx, a, state, P, t, ticket, stamps)
+                         : launch_mid<16, false, false>(ctx, a, state, P, t, ticket, stamps);
+    return wide == 2 ? launch_mid<32, true, true>(ctx, a, state, P, t, ticket, stamps)
+           : wide    ? launch_mid<32, true, false>(ctx, a, state, P, t, ticket, stamps)
+                     : launch_mid<32, false, false>(ctx, a, state, P, t, ticket, stamps);
+}
+
+int32_t vmp_pca_launch_sweep_head_wide(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total,
+                                       double x_prec, double a0t, double b0t, double a0a, double b0a,
+                                       double *state)
+{
+    small_args a;
+    const int32_t rc = fill_small_args(ctx, a, D, K, n_total, x_prec, a0t, b0t, a0a, b0a);
+    if (rc != VMP_OK) return rc;
+    if (a.L.KP == 16)
+        hipLaunchKernelGGL(pca_head_wide_kernel<16>, dim3(1), dim3(NTF), 0, ctx->stream, a, state);
+    else
+        hipLaunchKernelGGL(pca_head_wide_kernel<32>, dim3(1), dim3(NTF), 0, ctx->stream, a, state);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
 }
 
 extern "C" {

@@ -258,7 +258,12 @@ int32_t vmp_pca_sweep_mid_count(vmp_ctx *ctx, int64_t *launches);
 /* Phase B of that launch runs wide forms of the tail and the head -- every load of the tail in one
  * batch, the D x K operand of the head whole in LDS, built for a workgroup that has the GPU to
  * itself -- unless tune key "pca_sweep_wide" / VMP_PCA_SWEEP_WIDE (default 1) is 0, which selects the
- * bodies of the three-launch sweep inside the launch.  The two agree bitwise.
+ * bodies of the three-launch sweep inside the launch.  The two agree bitwise.  With the wide bodies
+ * and tune key "pca_sweep_local_pxx" / VMP_PCA_SWEEP_LOCAL_PXX (default 1) the workgroups store no
+ * partial blocks of sum <x><x>^T: the workgroup that runs phase B forms the sum from the A and the rows
+ * of sum y<x>^T it holds in LDS, by the same chains added in the same order (bitwise the same; 0: the
+ * blocks travel through memory).  The first head of a batch runs the wide head too, in a launch of
+ * its own, unless a latent pass is still in flight.
  *
  * Measurement: while tune key "pca_sweep_stamps" is 1, vmp_pca_sweeps launches a stamped build of that
  * kernel, in which one lane records wall_clock64() (a constant 100 MHz counter) at the boundaries of

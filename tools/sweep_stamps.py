@@ -2,7 +2,7 @@
 """Where the time goes inside one launch of pca_sweep_mid_kernel: per-phase medians from the
 wall_clock64 stamps of the stamped build (tune key "pca_sweep_stamps").
 
-    python tools/sweep_stamps.py [--wide 0|1] [--D 128] [--K 32] [--N 4096] [--chunks 5]
+    python tools/sweep_stamps.py [--wide 0|1] [--local 0|1] [--D 128] [--K 32] [--N 4096] [--chunks 5]
 
 Runs chunks of 32 sweeps (31 mid launches each) of the PCA demo model at the headline's (D, K) with a
 small N, reads the stamps of each chunk and prints the median over all launches of every phase, in
@@ -11,6 +11,10 @@ few microseconds is resolved to a few per cent.  A stamp is one clock read and o
 one lane; that this costs well under a tick is assumed, not measured (the stamped kernel's own
 duration has not been set against the default kernel's).  --wide 0 selects the tail and head bodies of the three-launch sweep
 inside the launch ("pca_sweep_wide" = 0), which share one loop for W and Sww: that row reads 0.
+--local 0 ("pca_sweep_local_pxx" = 0) has the partial blocks of sum <x><x>^T stored by phase A and added
+by the tail ('tail: partials summed'); with --local 1 the tail forms the sum from LDS after its loads
+have landed ('tail: Pxx formed') and the other boundary is not passed.  A boundary that is not passed
+prints '-'.
 """
 import argparse
 import os
@@ -23,7 +27,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 TICK_US = 1.0 / 100.0            # 100 MHz
 # (name of the boundary, in the order of enum SP_* in csrc/vmp_pca_small.hip)
 NAMES = ['kernel entry', 'A: LDS filled', 'A: Syx done', 'A: Pxx stored', 'ticket drawn', 'acquire done',
-         'tail: partials summed', 'tail: loads landed', 'tail: block sums done', 'tail: tau/alpha done',
+         'tail: partials summed', 'tail: loads landed', 'tail: Pxx formed', 'tail: block sums done',
+         'tail: tau/alpha done',
          'tail: bound done', 'tail: ring written',
          'head: Lambda_W built', 'head: inverse 1 done', 'head: W done', 'head: Sww done',
          'head: inverse 2 done', 'head: A stored']
@@ -32,6 +37,7 @@ NAMES = ['kernel entry', 'A: LDS filled', 'A: Syx done', 'A: Pxx stored', 'ticke
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--wide', type=int, default=1)
+    ap.add_argument('--local', type=int, default=1)
     ap.add_argument('--D', type=int, default=128)
     ap.add_argument('--K', type=int, default=32)
     ap.add_argument('--N', type=int, default=4096)
@@ -42,6 +48,7 @@ def main():
     from bayespy_amd.inference import VB
     rt = get_runtime()
     rt.check(rt.lib.vmp_tune_set(b'pca_sweep_wide', a.wide))
+    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_local_pxx', a.local))
     rt.check(rt.lib.vmp_tune_set(b'pca_sweep_stamps', 1))
     rng = np.random.default_rng(0)
     y = rng.standard_normal((a.D, a.K)) @ rng.standard_normal((a.K, a.N)) \
@@ -66,11 +73,12 @@ def main():
         assert allocated and r.shape[0] == 31, r.shape
         rows.append(r[:, :len(NAMES)].astype(np.int64))
     t = np.concatenate(rows[1:])                       # (the first chunk warms up)
-    print('pca_sweep_mid_kernel stamps: D=%d K=%d N=%d, pca_sweep_wide=%d, %d launches'
-          % (a.D, a.K, a.N, a.wide, t.shape[0]))
+    print('pca_sweep_mid_kernel stamps: D=%d K=%d N=%d, pca_sweep_wide=%d, pca_sweep_local_pxx=%d, '
+          '%d launches' % (a.D, a.K, a.N, a.wide, a.local if a.wide else 0, t.shape[0]))
     print('wall_clock64 at a constant 100 MHz: 1 tick = 0.01 us; medians over the launches')
     print('%-28s %10s %12s' % ('boundary', 'phase_us', 'since_entry'))
     prev = t[:, 0]
+    ix = {name: i for i, name in enumerate(NAMES)}
     for i, name in enumerate(NAMES):
         have = t[:, i] != 0
         if not have.all():
@@ -81,7 +89,10 @@ def main():
         prev = t[:, i]
     print('phase A (entry -> ticket) %.2f | tail (acquire -> ring) %.2f | head (ring -> A stored) %.2f us'
           % tuple(np.median(x) * TICK_US for x in
-                  (t[:, 4] - t[:, 0], t[:, 11] - t[:, 5], t[:, 17] - t[:, 11])))
+                  (t[:, ix['ticket drawn']] - t[:, 0],
+                   t[:, ix['tail: ring written']] - t[:, ix['acquire done']],
+                   t[:, ix['head: A stored']] - t[:, ix['tail: ring written']])))
+    print('entry -> A stored %.2f us' % (np.median(t[:, ix['head: A stored']] - t[:, 0]) * TICK_US))
 
 
 if __name__ == '__main__':
