@@ -64,6 +64,12 @@ struct vmp_ctx {
     // allocated and written only while the tune key "pca_sweep_stamps" is on (vmp_pca_sweep_stamps)
     unsigned long long *sweep_stamps;
     int sweep_stamp_rows;
+    // values of the special functions that do not change from sweep to sweep (VMP_SWEEP_SF_*), read
+    // by the deferred side work of pca_sweep_mid_kernel ("pca_sweep_defer"), and the host copy of the
+    // inputs they were computed from: a0t, b0t, a0a, b0a, D, n_total, x_prec (sweep_sf_valid: any)
+    double *sweep_sf;
+    double sweep_sf_key[7];
+    int sweep_sf_valid;
     // streams / events of the pipelined plate pass of the missing-data PCA block (vmp_mpca.hip)
     hipStream_t ms[3];
     hipEvent_t me[VMP_NME];
@@ -90,6 +96,11 @@ enum { VMP_SWEEP_NSTAMP = VMP_PCA_SWEEP_NSTAMP };
 // control block of vmp_pca_sweeps (vmp_ctx::sweep_ctl), in doubles
 enum { VMP_SWEEP_STOP = 0, VMP_SWEEP_L = 1, VMP_SWEEP_EXECUTED = 2, VMP_SWEEP_SKIPPED = 3,
        VMP_SWEEP_CTL_LEN = 8 };
+
+// vmp_ctx::sweep_sf, in doubles: per Gamma node digamma(a), lgamma(a), lgamma(a0), log(b0) with the
+// shapes a = a0t + D n_total / 2 (tau) and a = a0a + D / 2 (alpha), then log(2 pi) and log(x_prec)
+enum { VMP_SWEEP_SF_TAU = 0, VMP_SWEEP_SF_ALPHA = 4, VMP_SWEEP_SF_LOG2PI = 8, VMP_SWEEP_SF_LOGXPREC = 9,
+       VMP_SWEEP_SF_LEN = 10 };
 
 // what the tail kernel of a batched sweep needs beyond the node updates (vmp_pca_small.hip)
 struct vmp_sweep_tail {
@@ -118,11 +129,17 @@ int32_t vmp_pca_launch_sweep_tail(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_
 // sweeps 1 .. n-1 of a chunk: Gram statistics, tail and the next sweep's head in ONE launch of DP / 8
 // workgroups (pca_sweep_mid_kernel, vmp_pca_small.hip); `ticket` is the sweep's own zeroed word, which
 // the launch leaves zero again; `wide` = 1 selects the wide tail and head of phase B, 2 those and sum
-// <x><x>^T formed by the tail ("pca_sweep_local_pxx"); `stamps` (null: none) the stamped build and its row
+// <x><x>^T formed by the tail ("pca_sweep_local_pxx"), 3 those and the bound deferred to the first
+// inverse of the head ("pca_sweep_defer"; vmp_pca_sweep_constants first); `stamps` (null: none) the
+// stamped build and its row, `stamp_level` the value of "pca_sweep_stamps"
 int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                                  double a0t, double b0t, double a0a, double b0a, double *state,
                                  double *P, const vmp_sweep_tail &t, unsigned int *ticket, int32_t wide,
-                                 unsigned long long *stamps);
+                                 unsigned long long *stamps, int32_t stamp_level);
+// makes vmp_ctx::sweep_sf hold the values for these arguments: a one-wavefront launch on the stream
+// when they differ from the ones it holds (the first call, another plan, changed priors or plates)
+int32_t vmp_pca_sweep_constants(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                                double a0t, double b0t, double a0a, double b0a);
 // the first head of a chunk by the wide head body, for a GPU with no latent pass in flight
 int32_t vmp_pca_launch_sweep_head_wide(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total,
                                        double x_prec, double a0t, double b0t, double a0a, double b0a,

@@ -101,6 +101,8 @@ int32_t vmp_ctx_create(int32_t device, void *stream, vmp_ctx **out)
     ctx->sweep_mid_launches = 0;
     ctx->sweep_stamps = nullptr;
     ctx->sweep_stamp_rows = 0;
+    ctx->sweep_sf = nullptr;
+    ctx->sweep_sf_valid = 0;
     for (int i = 0; i < 3; ++i) ctx->ms[i] = nullptr;
     for (int i = 0; i < VMP_NME; ++i) ctx->me[i] = nullptr;
     ctx->comm = nullptr;
@@ -137,6 +139,7 @@ int32_t vmp_ctx_destroy(vmp_ctx *ctx)
     if (ctx->sweep_ctl) (void)hipFree(ctx->sweep_ctl);       // (waits for the device itself)
     if (ctx->sweep_tickets) (void)hipFree(ctx->sweep_tickets);
     if (ctx->sweep_stamps) (void)hipFree(ctx->sweep_stamps);
+    if (ctx->sweep_sf) (void)hipFree(ctx->sweep_sf);
     if (ctx->ev_xfork) (void)hipEventDestroy(ctx->ev_xfork);
     if (ctx->ev_xdone) (void)hipEventDestroy(ctx->ev_xdone);
     for (int i = 0; i < 2; ++i)

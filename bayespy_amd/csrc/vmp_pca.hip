@@ -1353,7 +1353,19 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
     int wide = vmp_tune_get("pca_sweep_wide", env_int("VMP_PCA_SWEEP_WIDE", 1, 0, 1)) ? 1 : 0;
     if (wide && vmp_tune_get("pca_sweep_local_pxx", env_int("VMP_PCA_SWEEP_LOCAL_PXX", 1, 0, 1)))
         wide = 2;
-    const bool stamps = ticket && vmp_tune_get("pca_sweep_stamps", 0);
+    // "pca_sweep_defer" = 0 (VMP_PCA_SWEEP_DEFER=0), with both of the above: the tail computes <log tau>,
+    // <log alpha>, the bound, the ring slot and the stop rule before it hands over to the head, instead
+    // of one wavefront doing so beside the head's first inverse, and every special function anew each
+    // sweep instead of reading the sweep-invariant ones from ctx->sweep_sf (the same bits)
+    if (wide == 2 && vmp_tune_get("pca_sweep_defer", env_int("VMP_PCA_SWEEP_DEFER", 1, 0, 1)))
+        wide = 3;
+    if (ticket && wide == 3) {
+        rc = vmp_pca_sweep_constants(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha, b0_alpha);
+        if (rc != VMP_OK) return rc;
+    }
+    // "pca_sweep_stamps" = 2: the side wavefront of the deferred form stamps too
+    const int stamp_level = ticket ? vmp_tune_get("pca_sweep_stamps", 0) : 0;
+    const bool stamps = stamp_level != 0;
     if (stamps) {
         const size_t bytes = (size_t)VMP_PCA_MAX_SWEEPS * VMP_SWEEP_NSTAMP * sizeof(unsigned long long);
         if (!ctx->sweep_stamps) VMP_HIP_CHECK(ctx, hipMalloc(&ctx->sweep_stamps, bytes));
@@ -1410,7 +1422,7 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
             rc = vmp_pca_launch_sweep_mid(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
                                           b0_alpha, state, P, t, ctx->sweep_tickets + i, wide,
                                           stamps ? ctx->sweep_stamps + (size_t)i * VMP_SWEEP_NSTAMP
-                                                 : nullptr);
+                                                 : nullptr, stamp_level);
             if (rc != VMP_OK) return rc;
             ctx->sweep_mid_launches += 1;
         } else {

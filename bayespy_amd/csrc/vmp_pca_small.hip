@@ -17,6 +17,8 @@
 #include "vmp_stop_rule.h"
 
 #include <stdlib.h>
+#include <string.h>
+#include <type_traits>
 
 namespace {
 
@@ -169,17 +171,26 @@ __device__ __forceinline__ void sweep_inverse(double *M, int n, double *logdet, 
 // default kernels are instantiated with stamps_off, which is empty.
 enum { SP_ENTRY = 0, SP_LDS_FILLED, SP_SYX, SP_PXX, SP_TICKET, SP_ACQUIRE,
        SP_T_PARTIALS, SP_T_LOADS, SP_T_PXX, SP_T_BLOCKSUMS, SP_T_TAU_ALPHA, SP_T_BOUND, SP_T_RING,
-       SP_H_LAMBDA, SP_H_INV1, SP_H_W, SP_H_SWW, SP_H_INV2, SP_H_A, SP_COUNT };
-static_assert(SP_COUNT <= VMP_SWEEP_NSTAMP, "stamp row length");
+       SP_H_LAMBDA, SP_H_INV1, SP_H_W, SP_H_SWW, SP_H_INV2, SP_H_A, SP_COUNT,
+       // "pca_sweep_stamps" = 2, the deferred form: where the side wavefront stands (free words of the row)
+       SP_S_STATE = SP_COUNT, SP_S_RING, SP_COUNT2 };
+static_assert(SP_COUNT2 <= VMP_SWEEP_NSTAMP, "stamp row length");
 struct stamps_off {
     __device__ __forceinline__ void operator()(int) const {}
+    __device__ __forceinline__ void side(int) const {}
     __device__ __forceinline__ void drain() const {}
 };
 struct stamps_on {
     unsigned long long *t;      // LDS, VMP_SWEEP_NSTAMP words
+    int level;                  // the value of "pca_sweep_stamps"
     __device__ __forceinline__ void operator()(int i) const
     {
         if (threadIdx.x == 0) t[i] = wall_clock64();
+    }
+    // a stamp of the side wavefront (its first lane), recorded at level 2 only
+    __device__ __forceinline__ void side(int i) const
+    {
+        if (level >= 2 && threadIdx.x == 64) t[i] = wall_clock64();
     }
     // before a stamp that stands for "stored": the thread's stores have left
     __device__ __forceinline__ void drain() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -825,13 +836,19 @@ static_assert(sizeof(tail_lds<16>) % 16 == 0 && sizeof(tail_lds<32>) % 16 == 0, 
 // (AL, KP rows DP + 2 doubles apart) -- every group's partial by the chain of gram_phase_a_wide, the
 // partials added in the order of the loop below.  The stop word is not read a second time: the
 // launch read it at entry, and no workgroup of a launch writes it before the tail of that launch.
-template <int KP, int MODE, bool WIDE = false, class STAMP = stamps_off, bool LOCAL = false>
+// DEFER ("pca_sweep_defer", a local wide tail): the tail ends with what the next head reads -- resid,
+// tau's a, b and mean, the status condition on b, alpha's a, b and mean -- and leaves <log tau>,
+// <log alpha>, the bound, the ring slot and the stop rule to defer_side below, which one wavefront
+// runs beside the head's first inverse.  resid and trx wait in red[0] and red[1].
+template <int KP, int MODE, bool WIDE = false, class STAMP = stamps_off, bool LOCAL = false,
+          bool DEFER = false>
 __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, const vmp_sweep_tail *sw,
                                               tail_lds<KP> &s, double *SW = nullptr,
                                               const STAMP &stamp = STAMP(), const double *AL = nullptr)
 {
     static_assert(!WIDE || MODE == TAIL_SWEEP, "the wide tail is a sweep tail");
     static_assert(!LOCAL || WIDE, "sum <x><x>^T is formed locally by the wide tail only");
+    static_assert(!DEFER || LOCAL, "the bound is deferred behind the local wide tail only");
     constexpr bool GRAM = (MODE == TAIL_GRAM);
     constexpr int LDM = KP + 1, E = KP * KP / NTF;
     extern __shared__ __align__(16) double gl[];          // GRAM: A (KP x (DP+1)) | G batch (GB x (DP+1)) | S batch (GB x LDM)
@@ -1124,12 +1141,69 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
         t2 += Sw[i * LDM + j] * sxx;
         if (i == j) trx += sxx;
     }
-    t1 = block_sum<NTF>(t1, red);
-    t2 = block_sum<NTF>(t2, red);
-    trx = block_sum<NTF>(trx, red);
+    if constexpr (DEFER) {
+        // the three block_sums behind one barrier: the wave sums go to twelve words of their own (the
+        // <log alpha> quarter of al, which the deferred form does not use and nothing has touched
+        // since the barrier above) and every thread adds each four in the order of block_sum
+        double *r3 = al + 3 * KP;
+        static_assert(KP >= 3 * (NTF / 64), "twelve words");
+        t1 = wave_sum(t1);
+        t2 = wave_sum(t2);
+        trx = wave_sum(trx);
+        if ((tid & 63) == 0) {
+            r3[tid >> 6] = t1;
+            r3[NTF / 64 + (tid >> 6)] = t2;
+            r3[2 * (NTF / 64) + (tid >> 6)] = trx;
+        }
+        __syncthreads();
+        t1 = t2 = trx = 0.0;
+#pragma unroll
+        for (int i = 0; i < NTF / 64; ++i) {
+            t1 += r3[i];
+            t2 += r3[NTF / 64 + i];
+            trx += r3[2 * (NTF / 64) + i];
+        }
+    } else {
+        t1 = block_sum<NTF>(t1, red);
+        t2 = block_sum<NTF>(t2, red);
+        trx = block_sum<NTF>(trx, red);
+    }
     stamp(SP_T_BLOCKSUMS);
     // (dot.py:355 E1 and dot.py:403 E2 collapsed to traces)
     const double resid = sc[4] - 2.0 * t1 + t2;
+    if constexpr (DEFER) {
+        if (tid == 64) {
+            const double ta = a.a0t + 0.5 * (double)D * a.n_total;
+            const double tb = a.b0t + 0.5 * resid;
+            sc[0] = ta;
+            sc[1] = tb;
+            sc[2] = ta / tb;
+            red[0] = resid;
+            red[1] = trx;
+            st[L.off_tau + 0] = ta;
+            st[L.off_tau + 1] = tb;
+            st[L.off_tau + 2] = sc[2];
+            st[L.off_scal + 2] = resid;
+            if (!(tb > 0.0)) st[L.off_scal + 3] = (double)VMP_ERR_FLOATING;
+        }
+        if (tid < K) {
+            const double aa = a.a0a + 0.5 * (double)D;
+            const double ab = a.b0a + 0.5 * Sw[tid * LDM + tid];
+            const double am = aa / ab;
+            al[0 * KP + tid] = aa;
+            al[1 * KP + tid] = ab;
+            al[2 * KP + tid] = am;
+            st[L.off_alpha + 0 * KP + tid] = aa;
+            st[L.off_alpha + 1 * KP + tid] = ab;
+            st[L.off_alpha + 2 * KP + tid] = am;
+        }
+        // the critical path leaves the tail here: the three phases that follow it in the other
+        // forms are the side wavefront's now
+        stamp(SP_T_TAU_ALPHA);
+        stamp(SP_T_BOUND);
+        stamp(SP_T_RING);
+        return;
+    }
     // ---- tau (gamma.py:116-148 with the message gaussian.py:2363-2369), alpha -------------
     if (tid == 64) {
         const double ta = a.a0t + 0.5 * (double)D * a.n_total;
@@ -1449,11 +1523,110 @@ pca_gram_wide_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
 // so W = tau Syx Cov_W, Sww and A = tau Cov_X W^T are one barrier-delimited phase each and nothing is
 // loaded from global memory.  Per output the MFMA sequence is the one of pca_head_body: over q for a
 // tile of W and A, over the rows in ascending order for a tile of Sww.  Stores are the same.
+//
+// SIDE ("pca_sweep_defer", pca_sweep_mid_kernel only): what runs beside the FIRST inverse, and `stopw`,
+// the LDS word it leaves the stop decision in.  Every thread reads that word behind the inverse's
+// closing barrier and the workgroup returns on a stop before the head has stored anything: Lambda_W
+// and its inverse were computed for nothing, in LDS and registers only.
+//
+// defer_side is that work: the part of the deferred tail (pca_tail_body, DEFER) that no head reads.
+// Wavefront 1 runs it, wavefronts 2 and 3 idle.  Lanes < K take alpha's Gamma node k, the lanes from
+// K on tau's (lane 32 is the one whose values are used), through the same instructions: one sf_log
+// per lane, of b, which serves <log .> = digamma(a) - log b and the node's bound term.  Every other
+// special function has arguments that do not change from sweep to sweep and comes from `sf`
+// (vmp_ctx::sweep_sf, filled by pca_sweep_sf_kernel with the same sf_* functions): values only, the
+// expressions around them are those of the tail and of gamma_elbo.  sla, saw and lal are non-zero in
+// the lanes < K of one wavefront, so block_sum's result is 0.0 + that wavefront's wave_sum: the same
+// butterfly on the same lane layout, and the same -0 + 0.
+// It reads Sww's diagonal (ts.Sw), sc[0..2] and sc[4..6], alpha's a, b and mean (ts.al), resid and
+// trx (red[0..1]): LDS the head does not write before the closing barrier (Lambda_W is built in
+// ts.Cx from ts.Sx and the means).  It writes al[0..4], alpha's a, which nothing reads after it.
 template <int KP, class STAMP>
+struct defer_side {
+    const small_args &a;
+    double *st;
+    const vmp_sweep_tail &sw;
+    tail_lds<KP> &s;
+    const double *sf;
+    const STAMP &stamp;
+    __device__ __forceinline__ void operator()() const
+    {
+        constexpr int LDM = KP + 1;
+        if (threadIdx.x >= 128) return;
+        const lay32 L(a.L);
+        const int l = threadIdx.x - 64, D = a.D, K = a.K;
+        const bool isa = l < K;
+        const int k = isa ? l : 0;
+        const double a0 = isa ? a.a0a : a.a0t, b0 = isa ? a.b0a : a.b0t;
+        const double av = isa ? s.al[0 * KP + k] : s.sc[0];
+        const double bv = isa ? s.al[1 * KP + k] : s.sc[1];
+        const double mean = isa ? s.al[2 * KP + k] : s.sc[2];
+        const double *c = sf + (isa ? VMP_SWEEP_SF_ALPHA : VMP_SWEEP_SF_TAU);
+        const double dg = c[0], lga = c[1], lga0 = c[2], logb0 = c[3];
+        const double logb = sf_log(bv);
+        const double logx = dg - logb;
+        // gamma_elbo with the values of its special functions
+        const double g_p = a0 * logb0 - lga0;
+        const double g_q = av * logb - lga;
+        const double g = g_p - g_q + (bv - b0) * mean + (a0 - av) * logx;
+        if (isa) st[L.off_alpha + 3 * KP + k] = logx;
+        if (l == 32) st[L.off_tau + 3] = logx;
+        stamp.side(SP_S_STATE);
+        const double sla = 0.0 + wave_sum(isa ? logx : 0.0);
+        const double saw = 0.0 + wave_sum(isa ? mean * s.Sw[k * LDM + k] : 0.0);
+        const double lal = 0.0 + wave_sum(isa ? g : 0.0);
+        const double logtau = __shfl(logx, 32, 64), Lt = __shfl(g, 32, 64);
+        if (l == 0) {
+            const double tau = s.sc[2], resid = s.red[0], trx = s.red[1];
+            const double Dd = (double)D, Kd = (double)K;
+            const double LY = Dd * a.n_total * (-0.5 * sf[VMP_SWEEP_SF_LOG2PI] + 0.5 * logtau)
+                              - 0.5 * tau * resid;
+            const double LX = -0.5 * a.x_prec * trx
+                              + a.n_total * (0.5 * Kd * sf[VMP_SWEEP_SF_LOGXPREC] - 0.5 * s.sc[6] + 0.5 * Kd);
+            const double LW = 0.5 * Dd * sla - 0.5 * saw + Dd * (-0.5 * s.sc[5] + 0.5 * Kd);
+            st[L.off_L + 0] = LY;
+            st[L.off_L + 1] = LX;
+            st[L.off_L + 2] = LW;
+            st[L.off_L + 3] = Lt;
+            st[L.off_L + 4] = lal;
+            st[L.off_L + 5] = LY + LX + LW + Lt + lal;
+            // the status word as the host would read it after the tail
+            const double status = !(s.sc[1] > 0.0) ? (double)VMP_ERR_FLOATING : st[L.off_scal + 3];
+            double *slot = sw.slot;
+            slot[0] = LY;
+            slot[1] = LX;
+            slot[2] = LW;
+            slot[3] = Lt;
+            slot[4] = lal;
+            slot[5] = LY + LX + LW + Lt + lal;
+            slot[6] = status;
+            slot[7] = 1.0;                             // executed
+            double *al = s.al;
+            al[0] = LY;
+            al[1] = LX;
+            al[2] = LW;
+            al[3] = Lt;
+            al[4] = lal;
+            const double Lb = vmp_bound_sum(al, sw.order, sw.norder);
+            const double L0 = sw.first ? sw.l0 : sw.ctl[VMP_SWEEP_L];
+            int stop = status != 0.0;
+            if (sw.compare && vmp_stop_rule(Lb, L0, sw.tol)) stop = 1;
+            sw.ctl[VMP_SWEEP_STOP] = stop ? 1.0 : 0.0;
+            s.stop = stop ? 1.0 : 0.0;
+            sw.ctl[VMP_SWEEP_L] = Lb;
+            sw.ctl[VMP_SWEEP_EXECUTED] += 1.0;
+        }
+        stamp.side(SP_S_RING);
+    }
+};
+
+template <int KP, class STAMP, class SIDE = no_side>
 __device__ __forceinline__ void pca_head_wide(const small_args &a, double *st, double *M, double *T,
                                               const double *alm, double tau, double *SW,
-                                              const STAMP &stamp)
+                                              const STAMP &stamp, const SIDE &side = SIDE(),
+                                              const double *stopw = nullptr)
 {
+    constexpr bool DEFER = !std::is_same<SIDE, no_side>::value;
     constexpr int LDM = KP + 1, E = KP * KP / NTF, KT = KP / 16;
     constexpr int WT = FAST_D / 16 * KT / 4;      // 16 x 16 tiles of the D x K operand per wavefront
     constexpr int ST = (KT * KT + 3) / 4;         // tiles of Sww per wavefront
@@ -1487,7 +1660,13 @@ __device__ __forceinline__ void pca_head_wide(const small_args &a, double *st, d
         }
     }
     stamp(SP_H_LAMBDA);
-    sweep_inverse<KP>(M, K, &logdet, &bad);
+    if constexpr (DEFER) {
+        sweep_inverse<KP>(M, K, &logdet, &bad, side);
+        // the side work has evaluated the stop rule: nothing of this head is in the state yet
+        if (*stopw != 0.0) return;
+    } else {
+        sweep_inverse<KP>(M, K, &logdet, &bad);
+    }
     stamp(SP_H_INV1);
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -1594,12 +1773,13 @@ __host__ __device__ inline size_t sweep_local_lds(int KP, int DP)
     return ((size_t)KP * (DP + 2) + (size_t)DP * (KP + 1) + 2) * sizeof(double);
 }
 
-template <int KP, bool WIDE, bool LOCAL, class STAMP>
+template <int KP, bool WIDE, bool LOCAL, bool DEFER, class STAMP>
 __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *st, double *P,
                                                    const vmp_sweep_tail &sw, unsigned int *ticket,
-                                                   const STAMP &stamp)
+                                                   const double *sf, const STAMP &stamp)
 {
     static_assert(!LOCAL || WIDE, "sum <x><x>^T is formed locally beside the wide bodies only");
+    static_assert(!DEFER || LOCAL, "the bound is deferred behind the local wide tail only");
     extern __shared__ __align__(16) double gl[];
     __shared__ tail_lds<KP> ts;
     const int tid = threadIdx.x;
@@ -1641,8 +1821,15 @@ __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *
     __syncthreads();
     stamp(SP_ACQUIRE);
     // (every thread has read the ticket word: the dynamic region is free for SW)
-    pca_tail_body<KP, TAIL_SWEEP, WIDE, STAMP, LOCAL>(a, st, &sw, ts, SW, stamp, gl);
+    pca_tail_body<KP, TAIL_SWEEP, WIDE, STAMP, LOCAL, DEFER>(a, st, &sw, ts, SW, stamp, gl);
     __syncthreads();
+    if constexpr (DEFER) {
+        // the rest of the tail, the stop rule included, runs beside the head's first inverse; the
+        // head reads ts.stop behind it, before its first store
+        const defer_side<KP, STAMP> side{a, st, sw, ts, sf, stamp};
+        pca_head_wide<KP>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], SW, stamp, side, &ts.stop);
+        return;
+    }
     if (ts.stop != 0.0) return;
     // Cov_X, sum <x><x>^T, <alpha> and <tau> go over in LDS.  WIDE: so do the Syx rows (in SW);
     // otherwise the head loads them -- phase A wrote them, acquired above -- and reads back its own <W>
@@ -1654,26 +1841,31 @@ __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *
 
 // WIDE: phase B runs the wide tail and head ("pca_sweep_wide", default); false: pca_tail_body and
 // pca_head_body as the three-launch sweep runs them.  LOCAL ("pca_sweep_local_pxx", default, with
-// WIDE): no partial blocks of sum <x><x>^T are stored, the tail forms the sum from LDS.
-template <int KP, bool WIDE, bool LOCAL>
+// WIDE): no partial blocks of sum <x><x>^T are stored, the tail forms the sum from LDS.  DEFER
+// ("pca_sweep_defer", default, with LOCAL): the tail hands over as soon as the head's inputs are
+// ready and the bound, the ring slot and the stop rule run beside the head's first inverse, with the
+// sweep-invariant special functions read from `sf` (vmp_ctx::sweep_sf; not read otherwise).
+template <int KP, bool WIDE, bool LOCAL, bool DEFER = false>
 __global__ void __launch_bounds__(NTF)
-pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, unsigned int *ticket)
+pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, unsigned int *ticket,
+                     const double *sf)
 {
-    pca_sweep_mid_body<KP, WIDE, LOCAL>(a, st, P, sw, ticket, stamps_off());
+    pca_sweep_mid_body<KP, WIDE, LOCAL, DEFER>(a, st, P, sw, ticket, sf, stamps_off());
 }
 
 // the same with wall_clock64 stamps ("pca_sweep_stamps"): `out` is this launch's row of
-// VMP_SWEEP_NSTAMP words, written by the workgroup that ran phase B
-template <int KP, bool WIDE, bool LOCAL>
+// VMP_SWEEP_NSTAMP words, written by the workgroup that ran phase B; `level` the key's value (2: the
+// side wavefront of the deferred form stamps too)
+template <int KP, bool WIDE, bool LOCAL, bool DEFER = false>
 __global__ void __launch_bounds__(NTF)
 pca_sweep_mid_stamped_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw,
-                             unsigned int *ticket, unsigned long long *out)
+                             unsigned int *ticket, const double *sf, unsigned long long *out, int level)
 {
     __shared__ unsigned long long stl[VMP_SWEEP_NSTAMP];
     if (threadIdx.x < VMP_SWEEP_NSTAMP) stl[threadIdx.x] = 0;
     __syncthreads();
-    const stamps_on stamp{stl};
-    pca_sweep_mid_body<KP, WIDE, LOCAL>(a, st, P, sw, ticket, stamp);
+    const stamps_on stamp{stl, level};
+    pca_sweep_mid_body<KP, WIDE, LOCAL, DEFER>(a, st, P, sw, ticket, sf, stamp);
     // (a workgroup that did not run phase B leaves no tail stamp)
     if (threadIdx.x == 0 && stl[SP_T_LOADS] != 0)
         for (int i = 0; i < VMP_SWEEP_NSTAMP; ++i) out[i] = stl[i];
@@ -1721,6 +1913,32 @@ pca_head_wide_kernel(small_args a, double *st)
     }
     __syncthreads();
     pca_head_wide<KP>(a, st, M, T, alm, tau, SW, stamps_off());
+}
+
+// The special functions of the held sweeps whose arguments stay the same from sweep to sweep
+// (vmp_ctx::sweep_sf, VMP_SWEEP_SF_*): one wavefront, a lane per value, through the sf_* functions the
+// tails call -- the same code, so the bits a tail computes.
+__global__ void __launch_bounds__(64)
+pca_sweep_sf_kernel(small_args a, double *sf)
+{
+    const int l = threadIdx.x;
+    if (l >= VMP_SWEEP_SF_LEN) return;
+    const double ta = a.a0t + 0.5 * (double)a.D * a.n_total;
+    const double aa = a.a0a + 0.5 * (double)a.D;
+    double v;
+    switch (l) {
+    case VMP_SWEEP_SF_TAU + 0: v = sf_digamma(ta); break;
+    case VMP_SWEEP_SF_TAU + 1: v = sf_lgamma(ta); break;
+    case VMP_SWEEP_SF_TAU + 2: v = sf_lgamma(a.a0t); break;
+    case VMP_SWEEP_SF_TAU + 3: v = sf_log(a.b0t); break;
+    case VMP_SWEEP_SF_ALPHA + 0: v = sf_digamma(aa); break;
+    case VMP_SWEEP_SF_ALPHA + 1: v = sf_lgamma(aa); break;
+    case VMP_SWEEP_SF_ALPHA + 2: v = sf_lgamma(a.a0a); break;
+    case VMP_SWEEP_SF_ALPHA + 3: v = sf_log(a.b0a); break;
+    case VMP_SWEEP_SF_LOG2PI: v = sf_log(2.0 * M_PI); break;
+    default: v = sf_log(a.x_prec); break;
+    }
+    sf[l] = v;
 }
 
 bool fast_small_enabled()
@@ -1963,15 +2181,18 @@ int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *sta
 }
 
 // one instantiation of the one-launch sweep; `stamps` (null: the default kernel) is the launch's row
-template <int KP, bool WIDE, bool LOCAL>
+template <int KP, bool WIDE, bool LOCAL, bool DEFER = false>
 static int32_t launch_mid(vmp_ctx *ctx, const small_args &a, double *state, double *P,
-                          const vmp_sweep_tail &t, unsigned int *ticket, unsigned long long *stamps)
+                          const vmp_sweep_tail &t, unsigned int *ticket, unsigned long long *stamps,
+                          int stamp_level)
 {
+    VMP_REQUIRE(ctx, !DEFER || ctx->sweep_sf, VMP_ERR_INVALID,
+                "the deferred sweep needs vmp_pca_sweep_constants first");
     static bool raised[2][64] = {{false}};
     const int dev = ctx->device & 63, s = stamps ? 1 : 0;
     if (!raised[s][dev]) {
-        const void *f = stamps ? (const void *)pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL>
-                               : (const void *)pca_sweep_mid_kernel<KP, WIDE, LOCAL>;
+        const void *f = stamps ? (const void *)pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL, DEFER>
+                               : (const void *)pca_sweep_mid_kernel<KP, WIDE, LOCAL, DEFER>;
         VMP_HIP_CHECK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                96 * 1024));
         raised[s][dev] = true;
@@ -1983,11 +2204,12 @@ static int32_t launch_mid(vmp_ctx *ctx, const small_args &a, double *state, doub
                               : gram_phase_a_lds((int)a.L.KP, (int)a.L.DP);
     const dim3 nb((unsigned)(a.L.DP / GRA));
     if (stamps)
-        hipLaunchKernelGGL((pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL>), nb, dim3(NTF), lds, ctx->stream, a,
-                           state, P, t, ticket, stamps);
+        hipLaunchKernelGGL((pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL, DEFER>), nb, dim3(NTF), lds,
+                           ctx->stream, a, state, P, t, ticket, (const double *)ctx->sweep_sf, stamps,
+                           stamp_level);
     else
-        hipLaunchKernelGGL((pca_sweep_mid_kernel<KP, WIDE, LOCAL>), nb, dim3(NTF), lds, ctx->stream, a, state,
-                           P, t, ticket);
+        hipLaunchKernelGGL((pca_sweep_mid_kernel<KP, WIDE, LOCAL, DEFER>), nb, dim3(NTF), lds, ctx->stream, a,
+                           state, P, t, ticket, (const double *)ctx->sweep_sf);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }
@@ -1995,18 +2217,40 @@ static int32_t launch_mid(vmp_ctx *ctx, const small_args &a, double *state, doub
 int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                                  double a0t, double b0t, double a0a, double b0a, double *state,
                                  double *P, const vmp_sweep_tail &t, unsigned int *ticket, int32_t wide,
-                                 unsigned long long *stamps)
+                                 unsigned long long *stamps, int32_t stamp_level)
 {
     small_args a;
     const int32_t rc = fill_small_args(ctx, a, D, K, n_total, x_prec, a0t, b0t, a0a, b0a);
     if (rc != VMP_OK) return rc;
+    const int sl = stamp_level;
     if (a.L.KP == 16)
-        return wide == 2 ? launch_mid<16, true, true>(ctx, a, state, P, t, ticket, stamps)
-               : wide    ? launch_mid<16, true, false>(ctx, a, state, P, t, ticket, stamps)
-                         : launch_mid<16, false, false>(ctx, a, state, P, t, ticket, stamps);
-    return wide == 2 ? launch_mid<32, true, true>(ctx, a, state, P, t, ticket, stamps)
-           : wide    ? launch_mid<32, true, false>(ctx, a, state, P, t, ticket, stamps)
-                     : launch_mid<32, false, false>(ctx, a, state, P, t, ticket, stamps);
+        return wide == 3 ? launch_mid<16, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
+               : wide == 2 ? launch_mid<16, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
+               : wide      ? launch_mid<16, true, false>(ctx, a, state, P, t, ticket, stamps, sl)
+                           : launch_mid<16, false, false>(ctx, a, state, P, t, ticket, stamps, sl);
+    return wide == 3 ? launch_mid<32, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
+           : wide == 2 ? launch_mid<32, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
+           : wide      ? launch_mid<32, true, false>(ctx, a, state, P, t, ticket, stamps, sl)
+                       : launch_mid<32, false, false>(ctx, a, state, P, t, ticket, stamps, sl);
+}
+
+int32_t vmp_pca_sweep_constants(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
+                                double a0t, double b0t, double a0a, double b0a)
+{
+    small_args a;
+    const int32_t rc = fill_small_args(ctx, a, D, K, n_total, x_prec, a0t, b0t, a0a, b0a);
+    if (rc != VMP_OK) return rc;
+    const double key[7] = {a0t, b0t, a0a, b0a, (double)D, (double)n_total, x_prec};
+    if (ctx->sweep_sf && ctx->sweep_sf_valid && memcmp(key, ctx->sweep_sf_key, sizeof(key)) == 0)
+        return VMP_OK;
+    if (!ctx->sweep_sf) VMP_HIP_CHECK(ctx, hipMalloc(&ctx->sweep_sf, VMP_SWEEP_SF_LEN * sizeof(double)));
+    // on the stream, ahead of the chunk that reads the values and behind every launch that read the old ones
+    ctx->sweep_sf_valid = 0;
+    hipLaunchKernelGGL(pca_sweep_sf_kernel, dim3(1), dim3(64), 0, ctx->stream, a, ctx->sweep_sf);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    memcpy(ctx->sweep_sf_key, key, sizeof(key));
+    ctx->sweep_sf_valid = 1;
+    return VMP_OK;
 }
 
 int32_t vmp_pca_launch_sweep_head_wide(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total,

@@ -264,11 +264,22 @@ int32_t vmp_pca_sweep_mid_count(vmp_ctx *ctx, int64_t *launches);
  * of sum y<x>^T it holds in LDS, by the same chains added in the same order (bitwise the same; 0: the
  * blocks travel through memory).  The first head of a batch runs the wide head too, in a launch of
  * its own, unless a latent pass is still in flight.
+ * With both of these and tune key "pca_sweep_defer" / VMP_PCA_SWEEP_DEFER (default 1) the tail hands
+ * over to the head as soon as <tau>, <alpha>, Cov_X and sum <x><x>^T are ready.  <log tau>, <log alpha>,
+ * the bound, the ring slot and the stop rule are formed by one wavefront beside the head's first
+ * inverse; a stop is read behind that inverse, before the head's first store, so a stopped loop leaves
+ * what it left before.  The special functions whose arguments do not change from sweep to sweep
+ * (digamma and lgamma of the two Gamma shapes, lgamma(a0), log(b0), log(2 pi), log(x_prec)) are
+ * computed by one small launch when the priors, D, the plate size or x_prec differ from those of the
+ * previous call on the context, and read from a buffer of the context (not the state block) after
+ * that.  Bitwise the same as 0, where the tail computes all of it each sweep.
  *
  * Measurement: while tune key "pca_sweep_stamps" is 1, vmp_pca_sweeps launches a stamped build of that
  * kernel, in which one lane records wall_clock64() (a constant 100 MHz counter) at the boundaries of
  * its phases: VMP_PCA_SWEEP_NSTAMP words per launch of the latest batch, 0 where a boundary was not
- * passed (order: csrc/vmp_pca_small.hip, enum SP_*).  This call waits for the stream and copies up to
+ * passed (order: csrc/vmp_pca_small.hip, enum SP_*).  At 2 the deferred form also records, in words 19
+ * and 20, where its side wavefront has stored the tau / alpha state and where it has written the ring
+ * slot and the stop word.  This call waits for the stream and copies up to
  * max_rows rows out.  The buffer belongs to the context and exists only once the key has been on:
  * *allocated (may be null) says whether it does. */
 #define VMP_PCA_SWEEP_NSTAMP 24

@@ -2,7 +2,8 @@
 """Where the time goes inside one launch of pca_sweep_mid_kernel: per-phase medians from the
 wall_clock64 stamps of the stamped build (tune key "pca_sweep_stamps").
 
-    python tools/sweep_stamps.py [--wide 0|1] [--local 0|1] [--D 128] [--K 32] [--N 4096] [--chunks 5]
+    python tools/sweep_stamps.py [--wide 0|1] [--local 0|1] [--defer 0|1] [--D 128] [--K 32] [--N 4096]
+                                 [--chunks 5]
 
 Runs chunks of 32 sweeps (31 mid launches each) of the PCA demo model at the headline's (D, K) with a
 small N, reads the stamps of each chunk and prints the median over all launches of every phase, in
@@ -15,6 +16,11 @@ inside the launch ("pca_sweep_wide" = 0), which share one loop for W and Sww: th
 by the tail ('tail: partials summed'); with --local 1 the tail forms the sum from LDS after its loads
 have landed ('tail: Pxx formed') and the other boundary is not passed.  A boundary that is not passed
 prints '-'.
+--defer 1 ("pca_sweep_defer" = 1, with --wide 1 --local 1) hands over to the head once the means of tau
+and alpha are ready: the three boundaries behind 'tail: block sums done' are stamped together there, and
+the stamped build runs at "pca_sweep_stamps" = 2, where the side wavefront -- which forms the bound, the
+ring slot and the stop word beside the head's first inverse -- stamps too.  Its two boundaries are
+printed since kernel entry, with whether the side work ends before 'head: inverse 1 done'.
 """
 import argparse
 import os
@@ -32,12 +38,14 @@ NAMES = ['kernel entry', 'A: LDS filled', 'A: Syx done', 'A: Pxx stored', 'ticke
          'tail: bound done', 'tail: ring written',
          'head: Lambda_W built', 'head: inverse 1 done', 'head: W done', 'head: Sww done',
          'head: inverse 2 done', 'head: A stored']
+SIDE = ['side: tau/alpha state stored', 'side: ring and stop written']      # words 19 and 20 of a row
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--wide', type=int, default=1)
     ap.add_argument('--local', type=int, default=1)
+    ap.add_argument('--defer', type=int, default=1)
     ap.add_argument('--D', type=int, default=128)
     ap.add_argument('--K', type=int, default=32)
     ap.add_argument('--N', type=int, default=4096)
@@ -49,7 +57,9 @@ def main():
     rt = get_runtime()
     rt.check(rt.lib.vmp_tune_set(b'pca_sweep_wide', a.wide))
     rt.check(rt.lib.vmp_tune_set(b'pca_sweep_local_pxx', a.local))
-    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_stamps', 1))
+    defer = 1 if (a.wide and a.local and a.defer) else 0
+    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_defer', defer))
+    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_stamps', 2 if defer else 1))
     rng = np.random.default_rng(0)
     y = rng.standard_normal((a.D, a.K)) @ rng.standard_normal((a.K, a.N)) \
         + 0.1 * rng.standard_normal((a.D, a.N))
@@ -71,10 +81,11 @@ def main():
         Q.update(repeat=32, verbose=False)
         r, allocated = plan.kernels.sweep_stamps()
         assert allocated and r.shape[0] == 31, r.shape
-        rows.append(r[:, :len(NAMES)].astype(np.int64))
+        rows.append(r[:, :len(NAMES) + len(SIDE)].astype(np.int64))
     t = np.concatenate(rows[1:])                       # (the first chunk warms up)
     print('pca_sweep_mid_kernel stamps: D=%d K=%d N=%d, pca_sweep_wide=%d, pca_sweep_local_pxx=%d, '
-          '%d launches' % (a.D, a.K, a.N, a.wide, a.local if a.wide else 0, t.shape[0]))
+          'pca_sweep_defer=%d, %d launches' % (a.D, a.K, a.N, a.wide, a.local if a.wide else 0, defer,
+                                               t.shape[0]))
     print('wall_clock64 at a constant 100 MHz: 1 tick = 0.01 us; medians over the launches')
     print('%-28s %10s %12s' % ('boundary', 'phase_us', 'since_entry'))
     prev = t[:, 0]
@@ -93,6 +104,14 @@ def main():
                    t[:, ix['tail: ring written']] - t[:, ix['acquire done']],
                    t[:, ix['head: A stored']] - t[:, ix['tail: ring written']])))
     print('entry -> A stored %.2f us' % (np.median(t[:, ix['head: A stored']] - t[:, 0]) * TICK_US))
+    if defer:
+        inv1 = t[:, ix['head: inverse 1 done']]
+        for i, name in enumerate(SIDE):
+            print('%-28s %10s %12.2f' % (name, '', np.median(t[:, len(NAMES) + i] - t[:, 0]) * TICK_US))
+        slack = inv1 - t[:, len(NAMES) + 1]
+        print("side work ends before 'head: inverse 1 done' in %d of %d launches; slack median %.2f, "
+              'min %.2f us' % (int((slack >= 0).sum()), slack.size, np.median(slack) * TICK_US,
+                               slack.min() * TICK_US))
 
 
 if __name__ == '__main__':
