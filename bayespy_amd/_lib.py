@@ -192,6 +192,9 @@ SIGNATURES = {
     'vmp_gmm_natural_init': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     'vmp_gmm_natural_step': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_vp, c_vp]),
     'vmp_gmm_lower_bound': (c_i32, [c_vp, c_i32, c_i32, c_vp]),
+    'vmp_gmm_prepare_z_annealed': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f64, c_vp]),
+    'vmp_gmm_update_annealed': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f64, c_vp]),
+    'vmp_gmm_lower_bound_annealed': (c_i32, [c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_vp]),
     'vmp_sum_multiply': (c_i32, [c_vp, c_i32, P(c_i64), c_i32, P(c_vp), P(c_i64), P(c_i64),
                                  ctypes.c_uint32, c_f64, c_vp, c_vp, c_sz]),
     'vmp_sum_multiply_workspace_bytes': (c_sz, []),
@@ -247,6 +250,8 @@ SIGNATURES = {
     'vmp_dgmm_tables': (c_i32, [c_vp, c_i32, c_i32] + [c_vp] * 7),
     'vmp_dgmm_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32] + [c_vp] * 11),
     'vmp_dgmm_update': (c_i32, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 9),
+    'vmp_dgmm_tables_annealed': (c_i32, [c_vp, c_i32, c_i32, c_f64] + [c_vp] * 7),
+    'vmp_dgmm_update_annealed': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f64] + [c_vp] * 9),
     'vmp_dgmm_limits_masked': (c_i32, [P(c_i32), P(c_i32)]),
     'vmp_dgmm_plan_masked': (c_i32, [c_i64, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_dgmm_pack_masked': (c_i32, [c_vp, c_i64, c_i32] + [c_vp] * 4),

@@ -291,18 +291,27 @@ __global__ void dgmm_add2_kernel(const double *__restrict__ two, double *__restr
 
 // h = <tau><mu>, q = -1/2 <tau>; gsum[k] = sum_d g[d, k] in ascending d; c = gsum + <log pi> less
 // its largest element.  mu_mom, tau_mom: (D K, 2) or null (no observation term)
+// ANN (deterministic annealing): h, q and gsum + <log pi> times `ab` before the maximum is taken
+// out; gsum itself is not scaled (it feeds L_Y).  The plain instance ignores `ab`.
+template <bool ANN>
 __global__ void __launch_bounds__(DGMM_NT)
 dgmm_tables_kernel(int D, int K, const double *__restrict__ mu_mom,
                    const double *__restrict__ tau_mom, const double *__restrict__ elog_pi,
                    double *__restrict__ h, double *__restrict__ q, double *__restrict__ c,
-                   double *__restrict__ gsum)
+                   double *__restrict__ gsum, double ab)
 {
     __shared__ double cs[VMP_DGMM_MAX_K];
     const int idx = blockIdx.x * DGMM_NT + threadIdx.x;
     const bool have = mu_mom && tau_mom;
     if (idx < D * K) {
-        h[idx] = have ? vmp_dgmm_h(tau_mom[2 * (int64_t)idx], mu_mom[2 * (int64_t)idx]) : 0.0;
-        q[idx] = have ? vmp_dgmm_q(tau_mom[2 * (int64_t)idx]) : 0.0;
+        double hv = have ? vmp_dgmm_h(tau_mom[2 * (int64_t)idx], mu_mom[2 * (int64_t)idx]) : 0.0;
+        double qv = have ? vmp_dgmm_q(tau_mom[2 * (int64_t)idx]) : 0.0;
+        if constexpr (ANN) {
+            hv = vmp_dgmm_anneal(ab, hv);
+            qv = vmp_dgmm_anneal(ab, qv);
+        }
+        h[idx] = hv;
+        q[idx] = qv;
     }
     if (blockIdx.x == 0) {
         if (idx < K) {
@@ -314,6 +323,7 @@ dgmm_tables_kernel(int D, int K, const double *__restrict__ mu_mom,
                 }
             if (gsum) gsum[idx] = t;
             cs[idx] = t + elog_pi[idx];
+            if constexpr (ANN) cs[idx] = vmp_dgmm_anneal(ab, cs[idx]);
         }
         __syncthreads();
         if (idx < K) {
@@ -355,6 +365,54 @@ dgmm_update_kernel(int D, int K, int which, const double *__restrict__ prior_a,
     if (tid == 0) bound[0] = bs[0];
 }
 
+// The annealed update (which 0: mu, 1: tau) and, which 2 / 3, the parts alone of the q that par and
+// mom hold: ab[0] = A, ab[1] = B, each the sum over the D K elements in the order of the plain
+// bound term (element e to thread e % 256, the 256 sums halved eight times).
+__global__ void __launch_bounds__(DGMM_NT)
+dgmm_update_annealed_kernel(int D, int K, int which, double beta, const double *__restrict__ prior_a,
+                            const double *__restrict__ prior_b, const double *__restrict__ S1,
+                            const double *__restrict__ S2, const double *__restrict__ Nk,
+                            const double *__restrict__ other, double *__restrict__ par,
+                            double *__restrict__ mom, double *__restrict__ ab)
+{
+    __shared__ double as[DGMM_NT];
+    __shared__ double bs[DGMM_NT];
+    const int tid = threadIdx.x;
+    const bool stats = S1 && S2 && Nk && other;
+    double ta = 0.0, tb = 0.0;
+    for (int e = tid; e < D * K; e += DGMM_NT) {
+        const int k = e % K;
+        double A, B;
+        if (which >= 2) {
+            if (which == 2) vmp_dgmm_parts_mu(prior_a[e], prior_b[e], par + 2 * (int64_t)e, &A, &B);
+            else vmp_dgmm_parts_tau(prior_a[e], prior_b[e], par + 2 * (int64_t)e,
+                                    mom + 2 * (int64_t)e, &A, &B);
+        } else {
+            const double nk = stats ? Nk[k] : 0.0, s1 = stats ? S1[e] : 0.0;
+            const double s2 = stats ? S2[e] : 0.0;
+            const double o0 = stats ? other[2 * (int64_t)e] : 0.0;
+            const double o1 = stats ? other[2 * (int64_t)e + 1] : 0.0;
+            if (which == 0)
+                vmp_dgmm_update_mu_annealed(beta, prior_a[e], prior_b[e], o0, nk, s1,
+                                            par + 2 * (int64_t)e, mom + 2 * (int64_t)e, &A, &B);
+            else
+                vmp_dgmm_update_tau_annealed(beta, prior_a[e], prior_b[e], o0, o1, nk, s1, s2,
+                                             par + 2 * (int64_t)e, mom + 2 * (int64_t)e, &A, &B);
+        }
+        ta += A;
+        tb += B;
+    }
+    as[tid] = ta;
+    bs[tid] = tb;
+    __syncthreads();
+    block_halve_sum<DGMM_NT>(as, tid);
+    block_halve_sum<DGMM_NT>(bs, tid);
+    if (tid == 0) {
+        ab[0] = as[0];
+        ab[1] = bs[0];
+    }
+}
+
 template <int KT>
 void launch_pass(vmp_ctx *ctx, int64_t nc, const DgmmArgs &a)
 {
@@ -394,8 +452,27 @@ int32_t vmp_dgmm_tables(vmp_ctx *ctx, int32_t D, int32_t K, const double *mu_mom
     VMP_REQUIRE(ctx, K <= VMP_DGMM_MAX_K && D <= VMP_DGMM_MAX_D, VMP_ERR_UNSUPPORTED,
                 "D = %d, K = %d exceed the limits (%d, %d)", D, K, VMP_DGMM_MAX_D, VMP_DGMM_MAX_K);
     VMP_REQUIRE(ctx, elog_pi && h && q && c, VMP_ERR_INVALID, "null argument");
-    hipLaunchKernelGGL(dgmm_tables_kernel, dim3((unsigned)((D * K + DGMM_NT - 1) / DGMM_NT)),
-                       dim3(DGMM_NT), 0, ctx->stream, D, K, mu_mom, tau_mom, elog_pi, h, q, c, gsum);
+    hipLaunchKernelGGL(dgmm_tables_kernel<false>, dim3((unsigned)((D * K + DGMM_NT - 1) / DGMM_NT)),
+                       dim3(DGMM_NT), 0, ctx->stream, D, K, mu_mom, tau_mom, elog_pi, h, q, c, gsum,
+                       1.0);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+int32_t vmp_dgmm_tables_annealed(vmp_ctx *ctx, int32_t D, int32_t K, double annealing,
+                                 const double *mu_mom, const double *tau_mom, const double *elog_pi,
+                                 double *h, double *q, double *c, double *gsum)
+{
+    VMP_FLUSH_SMALL(ctx);
+    VMP_REQUIRE(ctx, ctx && D >= 1 && K >= 1, VMP_ERR_INVALID, "bad arguments");
+    VMP_REQUIRE(ctx, K <= VMP_DGMM_MAX_K && D <= VMP_DGMM_MAX_D, VMP_ERR_UNSUPPORTED,
+                "D = %d, K = %d exceed the limits (%d, %d)", D, K, VMP_DGMM_MAX_D, VMP_DGMM_MAX_K);
+    VMP_REQUIRE(ctx, elog_pi && h && q && c, VMP_ERR_INVALID, "null argument");
+    VMP_REQUIRE(ctx, annealing > 0.0 && annealing <= 1.0, VMP_ERR_INVALID,
+                "annealing must be in (0, 1], got %g", annealing);
+    hipLaunchKernelGGL(dgmm_tables_kernel<true>, dim3((unsigned)((D * K + DGMM_NT - 1) / DGMM_NT)),
+                       dim3(DGMM_NT), 0, ctx->stream, D, K, mu_mom, tau_mom, elog_pi, h, q, c, gsum,
+                       annealing);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }
@@ -448,6 +525,25 @@ int32_t vmp_dgmm_update(vmp_ctx *ctx, int32_t D, int32_t K, int32_t which, const
     VMP_REQUIRE(ctx, prior_a && prior_b && par && mom && bound, VMP_ERR_INVALID, "null argument");
     hipLaunchKernelGGL(dgmm_update_kernel, dim3(1), dim3(DGMM_NT), 0, ctx->stream, D, K, which,
                        prior_a, prior_b, S1, S2, Nk, other_mom, par, mom, bound);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+int32_t vmp_dgmm_update_annealed(vmp_ctx *ctx, int32_t D, int32_t K, int32_t which,
+                                 double annealing, const double *prior_a, const double *prior_b,
+                                 const double *S1, const double *S2, const double *Nk,
+                                 const double *other_mom, double *par, double *mom, double *ab)
+{
+    VMP_FLUSH_SMALL(ctx);
+    VMP_REQUIRE(ctx, ctx && D >= 1 && K >= 1 && which >= 0 && which <= 3, VMP_ERR_INVALID,
+                "bad arguments");
+    VMP_REQUIRE(ctx, K <= VMP_DGMM_MAX_K && D <= VMP_DGMM_MAX_D, VMP_ERR_UNSUPPORTED,
+                "D = %d, K = %d exceed the limits (%d, %d)", D, K, VMP_DGMM_MAX_D, VMP_DGMM_MAX_K);
+    VMP_REQUIRE(ctx, prior_a && prior_b && par && mom && ab, VMP_ERR_INVALID, "null argument");
+    VMP_REQUIRE(ctx, annealing > 0.0 && annealing <= 1.0, VMP_ERR_INVALID,
+                "annealing must be in (0, 1], got %g", annealing);
+    hipLaunchKernelGGL(dgmm_update_annealed_kernel, dim3(1), dim3(DGMM_NT), 0, ctx->stream, D, K,
+                       which, annealing, prior_a, prior_b, S1, S2, Nk, other_mom, par, mom, ab);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }

@@ -148,6 +148,63 @@ __host__ __device__ inline double vmp_dgmm_update_tau(double a0, double b0, doub
     return -a0 * log1p(add / b0) - vmp_lgamma(a0) + vmp_lgamma(a) + (a0 - a) * psi + add * tau;
 }
 
+// -- deterministic annealing (expfamily.py:343-350, :400-480) ------------------------------------------
+// A node with the coefficient ab in (0, 1] updates to ab times its natural parameters; its bound term
+// is A - T B with T = 1 / ab AT THE REQUEST, A = cgf from the parents + phi_p . u and B = phi_q . u +
+// g_q (the base measure cancels as at T = 1).  ab = 1 gives the bits of the plain forms: par and mom
+// are formed by the same expressions from ab * (the plain parameters).
+__host__ __device__ inline double vmp_dgmm_anneal(double ab, double x) { return ab * x; }
+
+// A and B of q(mu_dk) = N(m, 1 / lambda) under the prior N(m0, 1 / beta0):
+//   A = 1/2 log beta0 - 1/2 beta0 ((m - m0)^2 + 1 / lambda),   B = 1/2 log lambda - 1/2
+__host__ __device__ inline void vmp_dgmm_parts_mu(double m0, double beta0, const double *par,
+                                                  double *A, double *B)
+{
+    const double dm = par[0] - m0, lambda = par[1];
+    *A = 0.5 * log(beta0) - 0.5 * beta0 * (dm * dm + 1.0 / lambda);
+    *B = 0.5 * log(lambda) - 0.5;
+}
+
+// A and B of q(tau_dk) = Gamma(a, b) under the prior Gamma(a0, b0), mom = (<tau>, <log tau>):
+//   A = a0 log b0 - lgamma(a0) - b0 <tau> + a0 <log tau>,   B = a psi(a) - a - lgamma(a)
+__host__ __device__ inline void vmp_dgmm_parts_tau(double a0, double b0, const double *par,
+                                                   const double *mom, double *A, double *B)
+{
+    // psi(a) itself, not <log tau> + log b, which carries the rounding of both of its terms times a
+    const double a = par[0], psi = vmp_digamma(a);
+    *A = a0 * log(b0) - vmp_lgamma(a0) - b0 * mom[0] + a0 * mom[1];
+    *B = a * (psi - 1.0) - vmp_lgamma(a);
+}
+
+// mu with the coefficient ab: precision ab (beta0 + N_k <tau>), the mean as at ab = 1
+__host__ __device__ inline void vmp_dgmm_update_mu_annealed(double ab, double m0, double beta0,
+                                                            double tau, double nk, double s1,
+                                                            double *par, double *mom, double *A,
+                                                            double *B)
+{
+    vmp_dgmm_update_mu(m0, beta0, tau, nk, s1, par, mom);
+    const double m = par[0], lambda = vmp_dgmm_anneal(ab, par[1]);
+    par[1] = lambda;
+    mom[1] = m * m + 1.0 / lambda;
+    vmp_dgmm_parts_mu(m0, beta0, par, A, B);
+}
+
+// tau with the coefficient ab: a = ab (a0 + N_k / 2), b = ab (b0 + ...)
+__host__ __device__ inline void vmp_dgmm_update_tau_annealed(double ab, double a0, double b0,
+                                                             double mu1, double mu2, double nk,
+                                                             double s1, double s2, double *par,
+                                                             double *mom, double *A, double *B)
+{
+    vmp_dgmm_update_tau(a0, b0, mu1, mu2, nk, s1, s2, par, mom);
+    const double a = vmp_dgmm_anneal(ab, par[0]), b = vmp_dgmm_anneal(ab, par[1]);
+    const double psi = vmp_digamma(a), tau = a / b;
+    par[0] = a;
+    par[1] = b;
+    mom[0] = tau;
+    mom[1] = psi - log(b);
+    vmp_dgmm_parts_tau(a0, b0, par, mom, A, B);
+}
+
 #ifndef __HIPCC__
 // the butterfly of a 16-lane group over v[0 .. 15]; every element ends with the result
 inline void vmp_dgmm_group_sum_host(double *v)

@@ -570,9 +570,14 @@ gmm_init_state_kernel(vmp_gmm_layout L, int D, int K, double beta0, double n0, d
 
 // mu.update(): Lambda_mu = beta0 I + R_k <Lambda_k>, Cov, mean = Cov <Lambda_k> S1_k
 // (gaussian.py:649-706 with the messages gaussian.py:2451-2454 weighted by r, mixture.py:126-158)
-template <int WPC>
+// ANN (deterministic annealing, expfamily.py:343-350): every natural parameter times `ab`, i.e. the
+// precision ab (beta0 I + R_k <Lambda_k>) and h = ab <Lambda_k> S1_k -- the mean stays, the
+// covariance is divided by ab.  ab = 1 multiplies by one: the same bits as the plain form.
+// (The ANN = false instances of this and the following kernels never read `ab` or the
+// temperatures: the plain entry points pass 1.0 only to fill the argument list.)
+template <int WPC, bool ANN = false>
 __global__ void __launch_bounds__(grp_threads(WPC))
-gmm_update_mu_kernel(vmp_gmm_layout L, int D, int K, double *st)
+gmm_update_mu_kernel(vmp_gmm_layout L, int D, int K, double *st, double ab = 1.0)
 {
     constexpr int TPC = 64 * WPC, CPB = grp_threads(WPC) / TPC;
     __shared__ double Ms[CPB][TPC];
@@ -588,6 +593,7 @@ gmm_update_mu_kernel(vmp_gmm_layout L, int D, int K, double *st)
     const double *Lam = st + L.off_Lam + (int64_t)kk * D * D;
     const double R = T[0];
     double v = act ? R * Lam[l] + ((i == j) ? beta0 : 0.0) : 0.0;
+    if constexpr (ANN) v *= ab;
     double ld;
     int bad = 0;
     v = grp_spd_inverse<WPC>(v, D, i, j, act, l, Ms[w], &ld, &bad);
@@ -595,6 +601,7 @@ gmm_update_mu_kernel(vmp_gmm_layout L, int D, int K, double *st)
     if (l < D) {
         double s = 0.0;
         for (int c = 0; c < D; ++c) s += Lam[l * D + c] * T[1 + c];     // <Lambda> S1
+        if constexpr (ANN) s *= ab;
         bs[w][l] = s;
     }
     grp_sync<WPC>();
@@ -612,9 +619,11 @@ gmm_update_mu_kernel(vmp_gmm_layout L, int D, int K, double *st)
 
 // Lambda.update(): n_k = n0 + R_k, V_k = V0 + S2 - S1 mu^T - mu S1^T + R <mu mu^T>
 // (wishart.py:153-188 with the message gaussian.py:2516-2520 weighted by r)
-template <int WPC>
+// ANN: n_k = ab (n0 + R_k), V_k = ab (V0 + ...), both stored annealed (the bound reads them).  An
+// annealed n_k <= D - 1 is no Wishart: the status word gets VMP_ERR_INVALID.
+template <int WPC, bool ANN = false>
 __global__ void __launch_bounds__(grp_threads(WPC))
-gmm_update_lambda_kernel(vmp_gmm_layout L, int D, int K, double *st)
+gmm_update_lambda_kernel(vmp_gmm_layout L, int D, int K, double *st, double ab = 1.0)
 {
     constexpr int TPC = 64 * WPC, CPB = grp_threads(WPC) / TPC;
     __shared__ double Ms[CPB][TPC];
@@ -629,11 +638,13 @@ gmm_update_lambda_kernel(vmp_gmm_layout L, int D, int K, double *st)
     const double *mu = st + L.off_mu + (int64_t)kk * D;
     const double *Cmu = st + L.off_Cmu + (int64_t)kk * D * D;
     const double R = T[0];
-    const double nk = n0 + R;
+    double nk = n0 + R;
+    if constexpr (ANN) nk *= ab;
     double v = 0.0;
     if (act) {
         const double mm = Cmu[l] + mu[i] * mu[j];
         v = V0[l] + T[1 + D + l] - T[1 + i] * mu[j] - mu[i] * T[1 + j] + R * mm;
+        if constexpr (ANN) v *= ab;
         st[L.off_Vk + (int64_t)k * D * D + l] = v;
     }
     // symmetrise before factorising
@@ -652,6 +663,8 @@ gmm_update_lambda_kernel(vmp_gmm_layout L, int D, int K, double *st)
         st[L.off_logdetV + k] = ld;
         st[L.off_logdetLam + k] = md + (double)D * log(2.0) - ld;           // wishart.py:185
         if (bad) st[L.off_scal + 3] = (double)VMP_ERR_NOT_POSDEF;
+        if constexpr (ANN)
+            if (!(nk > (double)(D - 1))) st[L.off_scal + 3] = (double)VMP_ERR_INVALID;
     }
 }
 
@@ -814,8 +827,11 @@ __device__ inline double gmm_ck(const double *st, const vmp_gmm_layout &L, int D
 
 // z.update(), replicated half: the coefficient matrix C of the pass
 // (phi of the Categorical = <log pi> + E[log p(y | k)], mixture.py:67-104)
+// ANN: the whole row times `ab` (every constant of the emission term included; the -inf of a
+// padded cluster stays -inf); q(z) from its prior is not annealed.
+template <bool ANN = false>
 __global__ void __launch_bounds__(NT)
-gmm_prepare_z_kernel(vmp_gmm_layout L, int D, int K, int prior_only, double *st)
+gmm_prepare_z_kernel(vmp_gmm_layout L, int D, int K, int prior_only, double *st, double ab = 1.0)
 {
     // Row k of C holds the coefficients of  ell_nk = c_k + b_k . y - 1/2 y^T Lam_k y  in the
     // compact feature order of the pass kernel: pairs y_a y_b (a <= b), then y_d, then 1.
@@ -846,18 +862,23 @@ gmm_prepare_z_kernel(vmp_gmm_layout L, int D, int K, int prior_only, double *st)
         } else if (f == npair + D) {
             v = -INFINITY;                    // padded clusters get zero responsibility
         }
+        if constexpr (ANN)
+            if (!prior_only) v *= ab;
         st[L.off_C + e] = v;
     }
 }
 
+// ANN: alpha_k = ab (alpha0_k + R_k)
+template <bool ANN = false>
 __global__ void __launch_bounds__(NT)
-gmm_update_alpha_kernel(vmp_gmm_layout L, int D, int K, double *st)
+gmm_update_alpha_kernel(vmp_gmm_layout L, int D, int K, double *st, double ab = 1.0)
 {
     __shared__ double red[NT / 64];
     const int tid = threadIdx.x;
     double s = 0.0;
     for (int k = tid; k < K; k += NT) {
-        const double a = st[L.off_prior + k] + st[L.off_T + (int64_t)k * L.FS];   // alpha0 + R_k
+        double a = st[L.off_prior + k] + st[L.off_T + (int64_t)k * L.FS];         // alpha0 + R_k
+        if constexpr (ANN) a *= ab;
         st[L.off_alpha + k] = a;
         s += a;
     }
@@ -898,9 +919,21 @@ __device__ inline void wave_sum_dd(double &h, double &lo)
 
 // expfamily.py:400-480 for Y, z, alpha, mu, Lambda.  One workgroup of 16
 // wavefronts; a wavefront owns clusters k = w, w+8, ... with the (i,j) matrix elements dealt to its lanes.
+//
+// ANN: every node's term is [cgf from parents + phi_p . u] - T [phi_q . u + g_q] with the node's own
+// temperature T = 1 / annealing (expfamily.py:410-468; f cancels as at T = 1), q being whatever the
+// state holds.  With the moments formed from phi_q the q parts are
+//   z       -(sum_n lse_n - sum_nk r phi)                       (the annealed logits of the pass)
+//   mu      1/2 log|Lambda_mu| - 1/2 D
+//   Lambda  g_q - 1/2 tr(V_k <Lambda>) + 1/2 n_k <log|Lambda|>
+//   alpha   ln Gamma(sum alpha) - sum ln Gamma(alpha_k) + sum alpha_k <log pi_k>
+// The temperatures enter as factors of the plain form's own operands, so T = 1 gives its bits;
+// the alpha term keeps the (value, rounding error) evaluation at T = 1.
 constexpr int NTLB = 512;
+template <bool ANN = false>
 __global__ void __launch_bounds__(NTLB)
-gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st)
+gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st, double Tz = 1.0, double Ta = 1.0,
+                       double Tm = 1.0, double TL = 1.0)
 {
     __shared__ double red[NTLB / 64];
     __shared__ double lgs[MAXK][2 * MAXD];         // the log-Gamma values of Lambda, ONE call site
@@ -946,14 +979,22 @@ gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st)
             const double ck = 0.5 * ldL - 0.5 * (double)D * log(2.0 * M_PI) - 0.5 * trLmm;
             LY += R * ck + bs - 0.5 * ls2;
             Lz += R * st[L.off_alpha + KP + k];
-            Lmu += -0.5 * beta0 * trmm + 0.5 * (double)D * log(beta0)
-                   - 0.5 * st[L.off_logdetLmu + k] + 0.5 * (double)D;
+            if constexpr (ANN)
+                Lmu += -0.5 * beta0 * trmm + 0.5 * (double)D * log(beta0)
+                       - (Tm * 0.5) * st[L.off_logdetLmu + k] + (Tm * 0.5) * (double)D;
+            else
+                Lmu += -0.5 * beta0 * trmm + 0.5 * (double)D * log(beta0)
+                       - 0.5 * st[L.off_logdetLmu + k] + 0.5 * (double)D;
             const double nk = st[L.off_nk + k];
             double mg0 = mgc, mgk = mgc;
             for (int c = 0; c < D; ++c) { mg0 += lgs[k][c]; mgk += lgs[k][D + c]; }
             const double gp = 0.5 * n0 * ldV0 - 0.5 * D * n0 * log(2.0) - mg0;
             const double gq = 0.5 * nk * st[L.off_logdetV + k] - 0.5 * D * nk * log(2.0) - mgk;
-            LL += gp - gq - 0.5 * trV0 + 0.5 * n0 * ldL + 0.5 * trVk - 0.5 * nk * ldL;
+            if constexpr (ANN)
+                LL += gp - TL * gq - 0.5 * trV0 + 0.5 * n0 * ldL + (TL * 0.5) * trVk
+                      - (TL * 0.5 * nk) * ldL;
+            else
+                LL += gp - gq - 0.5 * trV0 + 0.5 * n0 * ldL + 0.5 * trVk - 0.5 * nk * ldL;
         }
     }
     LY = block_sum<NTLB>(LY, red);
@@ -966,7 +1007,27 @@ gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st)
     // Wavefront 0, lane k holding cluster k, adds the K <= 64 terms and both sums of alpha as
     // (value, rounding error) pairs, with every ln Gamma such a pair too (vmp_lgamma_dd).
     double La = 0.0;
-    if (w == 0) {
+    if (ANN && Ta != 1.0) {
+        // A - Ta B in plain doubles (the sums as value + rounding error).  Far from Ta = 1 no
+        // difference of nearly equal ln Gamma is left to protect; as Ta approaches 1 it is one again
+        // and this path has about 1e-13 absolute on values of a few thousand where the Ta = 1 path
+        // below has its (value, rounding error) pairs throughout.
+        if (w == 0) {
+            const bool on = l < K;
+            const double a0 = on ? st[L.off_prior + l] : 0.0, a1 = on ? st[L.off_alpha + l] : 0.0;
+            const double elp = on ? st[L.off_alpha + KP + l] : 0.0;
+            double s0h = a0, s0l = 0.0, s1h = a1, s1l = 0.0;
+            double ah = on ? a0 * elp - lgamma_ni(a0) : 0.0, al = 0.0;
+            double bh = on ? a1 * elp - lgamma_ni(a1) : 0.0, bl = 0.0;
+            wave_sum_dd(ah, al);
+            wave_sum_dd(bh, bl);
+            wave_sum_dd(s0h, s0l);
+            wave_sum_dd(s1h, s1l);
+            const double g = lgamma_ni(l == 0 ? s0h + s0l : s1h + s1l);
+            const double A = __shfl(g, 0, 64) + (ah + al), B = __shfl(g, 1, 64) + (bh + bl);
+            La = A - Ta * B;
+        }
+    } else if (w == 0) {
         const bool on = l < K;
         double s0h = on ? st[L.off_prior + l] : 0.0, s0l = 0.0;
         double s1h = on ? st[L.off_alpha + l] : 0.0, s1l = 0.0;
@@ -988,7 +1049,8 @@ gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st)
         La = (th + d) + (((g0l - g1l) + de) + tl);
     }
     if (tid == 0) {
-        Lz += st[L.off_zs + 0] - st[L.off_zs + 1];
+        if constexpr (ANN) Lz += Tz * (st[L.off_zs + 0] - st[L.off_zs + 1]);
+        else Lz += st[L.off_zs + 0] - st[L.off_zs + 1];
         st[L.off_L + 0] = LY;
         st[L.off_L + 1] = Lz;
         st[L.off_L + 2] = La;
@@ -1227,13 +1289,13 @@ int32_t vmp_gmm_update_mu(vmp_ctx *ctx, int32_t D, int32_t K, double *state)
     VMP_GMM_PROLOGUE();
     if (D * D <= 64)
         hipLaunchKernelGGL(gmm_update_mu_kernel<1>, dim3((K + 3) / 4), dim3(NT), 0, ctx->stream, L,
-                           D, K, state);
+                           D, K, state, 1.0);
     else if (D * D <= 256)
         hipLaunchKernelGGL(gmm_update_mu_kernel<4>, dim3(K), dim3(NT), 0, ctx->stream, L, D, K,
-                           state);
+                           state, 1.0);
     else
         hipLaunchKernelGGL(gmm_update_mu_kernel<16>, dim3(K), dim3(1024), 0, ctx->stream, L, D, K,
-                           state);
+                           state, 1.0);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }
@@ -1243,13 +1305,13 @@ int32_t vmp_gmm_update_lambda(vmp_ctx *ctx, int32_t D, int32_t K, double *state)
     VMP_GMM_PROLOGUE();
     if (D * D <= 64)
         hipLaunchKernelGGL(gmm_update_lambda_kernel<1>, dim3((K + 3) / 4), dim3(NT), 0,
-                           ctx->stream, L, D, K, state);
+                           ctx->stream, L, D, K, state, 1.0);
     else if (D * D <= 256)
         hipLaunchKernelGGL(gmm_update_lambda_kernel<4>, dim3(K), dim3(NT), 0, ctx->stream, L, D, K,
-                           state);
+                           state, 1.0);
     else
         hipLaunchKernelGGL(gmm_update_lambda_kernel<16>, dim3(K), dim3(1024), 0, ctx->stream, L, D,
-                           K, state);
+                           K, state, 1.0);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }
@@ -1258,8 +1320,8 @@ int32_t vmp_gmm_prepare_z(vmp_ctx *ctx, int32_t D, int32_t K, int32_t prior_only
 {
     VMP_GMM_PROLOGUE();
     const int n = (int)(L.KP * L.F2P);
-    hipLaunchKernelGGL(gmm_prepare_z_kernel, dim3((n + NT - 1) / NT), dim3(NT), 0, ctx->stream, L,
-                       D, K, (int)prior_only, state);
+    hipLaunchKernelGGL(gmm_prepare_z_kernel<false>, dim3((n + NT - 1) / NT), dim3(NT), 0,
+                       ctx->stream, L, D, K, (int)prior_only, state, 1.0);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }
@@ -1267,7 +1329,8 @@ int32_t vmp_gmm_prepare_z(vmp_ctx *ctx, int32_t D, int32_t K, int32_t prior_only
 int32_t vmp_gmm_update_alpha(vmp_ctx *ctx, int32_t D, int32_t K, double *state)
 {
     VMP_GMM_PROLOGUE();
-    hipLaunchKernelGGL(gmm_update_alpha_kernel, dim3(1), dim3(NT), 0, ctx->stream, L, D, K, state);
+    hipLaunchKernelGGL(gmm_update_alpha_kernel<false>, dim3(1), dim3(NT), 0, ctx->stream, L, D, K,
+                       state, 1.0);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }
@@ -1309,8 +1372,73 @@ int32_t vmp_gmm_natural_step(vmp_ctx *ctx, int32_t D, int32_t K, int32_t nodes, 
 int32_t vmp_gmm_lower_bound(vmp_ctx *ctx, int32_t D, int32_t K, double *state)
 {
     VMP_GMM_PROLOGUE();
-    hipLaunchKernelGGL(gmm_lower_bound_kernel, dim3(1), dim3(NTLB), 0, ctx->stream, L, D, K,
-                       state);
+    hipLaunchKernelGGL(gmm_lower_bound_kernel<false>, dim3(1), dim3(NTLB), 0, ctx->stream, L, D, K,
+                       state, 1.0, 1.0, 1.0, 1.0);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+// ---- deterministic annealing (expfamily.py:343-350, :400-480) --------------------------------------
+static bool gmm_coefficient_ok(double b) { return b > 0.0 && b <= 1.0; }
+
+int32_t vmp_gmm_prepare_z_annealed(vmp_ctx *ctx, int32_t D, int32_t K, int32_t prior_only,
+                                   double annealing, double *state)
+{
+    VMP_GMM_PROLOGUE();
+    VMP_REQUIRE(ctx, gmm_coefficient_ok(annealing), VMP_ERR_INVALID,
+                "annealing must be in (0, 1], got %g", annealing);
+    const int n = (int)(L.KP * L.F2P);
+    hipLaunchKernelGGL(gmm_prepare_z_kernel<true>, dim3((n + NT - 1) / NT), dim3(NT), 0,
+                       ctx->stream, L, D, K, (int)prior_only, state, annealing);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+int32_t vmp_gmm_update_annealed(vmp_ctx *ctx, int32_t D, int32_t K, int32_t node, double annealing,
+                                double *state)
+{
+    VMP_GMM_PROLOGUE();
+    VMP_REQUIRE(ctx, node == STEP_MU || node == STEP_LAMBDA || node == STEP_ALPHA, VMP_ERR_INVALID,
+                "node is 1 (mu), 2 (Lambda) or 4 (alpha), got %d", node);
+    VMP_REQUIRE(ctx, gmm_coefficient_ok(annealing), VMP_ERR_INVALID,
+                "annealing must be in (0, 1], got %g", annealing);
+    hipStream_t s = ctx->stream;
+    const dim3 g1((K + 3) / 4), gk(K);
+    if (node == STEP_ALPHA)
+        hipLaunchKernelGGL(gmm_update_alpha_kernel<true>, dim3(1), dim3(NT), 0, s, L, D, K, state,
+                           annealing);
+    else if (node == STEP_MU && D * D <= 64)
+        hipLaunchKernelGGL((gmm_update_mu_kernel<1, true>), g1, dim3(NT), 0, s, L, D, K, state,
+                           annealing);
+    else if (node == STEP_MU && D * D <= 256)
+        hipLaunchKernelGGL((gmm_update_mu_kernel<4, true>), gk, dim3(NT), 0, s, L, D, K, state,
+                           annealing);
+    else if (node == STEP_MU)
+        hipLaunchKernelGGL((gmm_update_mu_kernel<16, true>), gk, dim3(1024), 0, s, L, D, K, state,
+                           annealing);
+    else if (D * D <= 64)
+        hipLaunchKernelGGL((gmm_update_lambda_kernel<1, true>), g1, dim3(NT), 0, s, L, D, K, state,
+                           annealing);
+    else if (D * D <= 256)
+        hipLaunchKernelGGL((gmm_update_lambda_kernel<4, true>), gk, dim3(NT), 0, s, L, D, K, state,
+                           annealing);
+    else
+        hipLaunchKernelGGL((gmm_update_lambda_kernel<16, true>), gk, dim3(1024), 0, s, L, D, K,
+                           state, annealing);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+int32_t vmp_gmm_lower_bound_annealed(vmp_ctx *ctx, int32_t D, int32_t K, double T_z, double T_alpha,
+                                     double T_mu, double T_lambda, double *state)
+{
+    VMP_GMM_PROLOGUE();
+    const double Ts[4] = {T_z, T_alpha, T_mu, T_lambda};
+    for (double t : Ts)
+        VMP_REQUIRE(ctx, t >= 1.0 && t < INFINITY, VMP_ERR_INVALID,
+                    "a temperature is 1 / annealing >= 1, got %g", t);
+    hipLaunchKernelGGL(gmm_lower_bound_kernel<true>, dim3(1), dim3(NTLB), 0, ctx->stream, L, D, K,
+                       state, T_z, T_alpha, T_mu, T_lambda);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }

@@ -80,6 +80,20 @@ class DGMMKernels(DirichletKernels):
                                                _p(S1), _p(S2), _p(Nk), _p(other), _p(par), _p(mom),
                                                _p(bound)))
 
+    # deterministic annealing
+    def tables_annealed(self, D, K, annealing, mu_mom, tau_mom, elog_pi, h, q, c, gsum=None):
+        self.rt.check(self.lib.vmp_dgmm_tables_annealed(self.ctx, D, K, float(annealing),
+                                                        _p(mu_mom), _p(tau_mom), _p(elog_pi), _p(h),
+                                                        _p(q), _p(c), _p(gsum)))
+
+    def update_annealed(self, D, K, which, annealing, prior_a, prior_b, S1, S2, Nk, other, par, mom,
+                        ab):
+        """which 0 / 1: the annealed update of mu / tau; 2 / 3: only the parts ``ab`` = (A, B) of
+        the bound term of the q that ``par`` and ``mom`` hold."""
+        self.rt.check(self.lib.vmp_dgmm_update_annealed(
+            self.ctx, D, K, which, float(annealing), _p(prior_a), _p(prior_b), _p(S1), _p(S2),
+            _p(Nk), _p(other), _p(par), _p(mom), _p(ab)))
+
 
 def _plates_reason(Y, mu):
     if len(Y.plates) != 2 or len(mu.plates) != 2 or mu.ndim != 0 or Y.ndim != 0:
@@ -123,6 +137,7 @@ class DiagGaussianMixturePlan(PlateMixturePlan):
     LABEL, KIND = _SPEC.label, 'dgmm'
     OBSERVED, WEIGHTS = 'Y', 'alpha'
     TERMS = ('Y', 'Z', 'mu', 'tau', 'alpha')
+    ANNEALING = True        # VB.set_annealing: the updates and the bound read node.annealing
 
     @staticmethod
     def describe():
@@ -197,6 +212,13 @@ class DiagGaussianMixturePlan(PlateMixturePlan):
         # [0] sum lse, [1] N_k . c used, [2] S1 . h + S2 . q used, [3] bound of mu, [4] of tau,
         # [5] of alpha, [6] S1 . h, [7] S2 . q, [8] N_k . g (present moments), [9] N_k . <log pi>
         self.scal = rt.zeros(12)
+        # the parts (A, B) of the bound terms of mu and tau under annealing; a node's pair is formed
+        # again at the request unless its last update was the annealed one, which leaves it here
+        self.ab = rt.zeros(4)
+        self._ab_fresh = dict(mu=False, tau=False)
+        # whose q the plain entry points made (their single bound slots hold its term at T = 1);
+        # scal[10] keeps the others as a bit set (1 mu, 2 tau, 4 alpha), so a checkpoint knows
+        self._plain = dict(mu=True, tau=True, alpha=True)
         # the priors; a given initial state replaces them below
         k.update(D, K, 0, self.m0, self.beta0, None, None, None, None, self.mu_par, self.mu_mom,
                  self.scal[3:4])
@@ -258,6 +280,53 @@ class DiagGaussianMixturePlan(PlateMixturePlan):
         self.kernels.update(self.D, self.K, which, prior_a, prior_b, self.S1, self.S2, self.Nk,
                             other, par, mom, bound)
 
+    # -- deterministic annealing (VB.set_annealing) --------------------------------------------------
+    def _annealing(self, node):
+        """The coefficient the node carries NOW; a form of the block that has no annealed kernels
+        declines any other than 1 here too (the attribute can be set without VB.set_annealing)."""
+        b = float(getattr(node, 'annealing', 1.0))
+        if b != 1.0 and not type(self).ANNEALING:
+            raise NotImplementedError(
+                "annealing is not built into the fused %s plan; build the engine with "
+                "VB(..., engine='generic')" % type(self).__name__)
+        return b
+
+    _PLAIN_BITS = dict(mu=1, tau=2, alpha=4)
+
+    def _set_plain(self, key, plain):
+        if self._plain[key] != plain:
+            self._plain[key] = plain
+            self.scal[10:11].fill_(float(sum(bit for k, bit in self._PLAIN_BITS.items()
+                                             if not self._plain[k])))
+
+    def load_state(self, reader, nodes, index):
+        super().load_state(reader, nodes, index)
+        bits = int(self.scal[10].item())
+        self._plain = {k: not (bits & bit) for k, bit in self._PLAIN_BITS.items()}
+        self._ab_fresh = dict(mu=False, tau=False)
+        self._L_annealing = None
+
+    def _tables_annealed(self, b):
+        self.kernels.tables_annealed(self.D, self.K, b, self.mu_mom, self.tau_mom, self.elog_r,
+                                     self.h, self.q, self.c)
+
+    def _update_annealed(self, key, b):
+        D, K = self.D, self.K
+        if key == 'mu':
+            self.kernels.update_annealed(D, K, 0, b, self.m0, self.beta0, self.S1, self.S2, self.Nk,
+                                         self.tau_mom, self.mu_par, self.mu_mom, self.ab[0:2])
+        else:
+            self.kernels.update_annealed(D, K, 1, b, self.a0, self.b0, self.S1, self.S2, self.Nk,
+                                         self.mu_mom, self.tau_par, self.tau_mom, self.ab[2:4])
+        self._ab_fresh[key] = True
+
+    def _weights_annealed(self, b):
+        """alpha = b (prior + N_k): the shared Dirichlet kernel on the scaled prior and counts
+        (its own bound term is of the scaled prior and is not used: scal[11] is a spare slot)."""
+        K = self.K
+        self.kernels.dirichlet(1, K, K, 1, b * self.prior_r, b * self.Nk, self.alpha_r, self.elog_r,
+                               self.ws_small, self.scal[11:12])
+
     def _run_pass(self, r_out=None):
         """The statistics of the present ``Z`` state (tables ``h`` / ``q`` / ``c`` or labels)."""
         self.kernels.pass_(self.N, self.D, self.K, self.y, self.labels, self.h, self.q, self.c,
@@ -269,25 +338,80 @@ class DiagGaussianMixturePlan(PlateMixturePlan):
         self._materialize()
         _delta.updated(self._delta, self.roles, node)
         self.rt.sync_stream()
+        # the coefficient of deterministic annealing; 1.0 runs exactly the plain entry points
+        b = self._annealing(node)
         if node is self.Z:
             self.labels = None
-            self._tables(self.mu_mom, self.tau_mom)
+            if b == 1.0:
+                self._tables(self.mu_mom, self.tau_mom)
+            else:
+                self._tables_annealed(b)
             self._run_pass()
         elif node is self.mu:
-            self._update_from_statistics(0, self.m0, self.beta0, self.tau_mom, self.mu_par,
-                                         self.mu_mom, self.scal[3:4])
+            if b == 1.0:
+                self._update_from_statistics(0, self.m0, self.beta0, self.tau_mom, self.mu_par,
+                                             self.mu_mom, self.scal[3:4])
+            else:
+                self._update_annealed('mu', b)
+            self._set_plain('mu', b == 1.0)
         elif node is self.tau:
-            self._update_from_statistics(1, self.a0, self.b0, self.mu_mom, self.tau_par,
-                                         self.tau_mom, self.scal[4:5])
+            if b == 1.0:
+                self._update_from_statistics(1, self.a0, self.b0, self.mu_mom, self.tau_par,
+                                             self.tau_mom, self.scal[4:5])
+            else:
+                self._update_annealed('tau', b)
+            self._set_plain('tau', b == 1.0)
         elif node is self.alpha:
-            self._weights_step(5, self.Nk)
+            if b == 1.0:
+                self._weights_step(5, self.Nk)
+            else:
+                self._weights_annealed(b)
+            self._set_plain('alpha', b == 1.0)
         else:
             return
+        if b == 1.0 and node is not self.Z and node is not self.alpha:
+            self._ab_fresh['mu' if node is self.mu else 'tau'] = False
         self._version += 1
+
+    def _lower_bound_terms(self):
+        # the temperature of a term is its node's at the request: the cached terms hold for the
+        # coefficients they were formed with
+        ann = tuple(self._annealing(n) for n in (self.Z, self.mu, self.tau, self.alpha))
+        if getattr(self, '_L_annealing', None) != ann:
+            self._L_version = -1
+            self._L_annealing = ann
+        return super()._lower_bound_terms()
+
+    def _annealed_term(self, key, b):
+        """A - T B of mu or tau, T = 1 / b, from the parts of the q the tables hold."""
+        D, K = self.D, self.K
+        if not self._ab_fresh[key]:
+            if key == 'mu':
+                self.kernels.update_annealed(D, K, 2, 1.0, self.m0, self.beta0, None, None, None,
+                                             None, self.mu_par, self.mu_mom, self.ab[0:2])
+            else:
+                self.kernels.update_annealed(D, K, 3, 1.0, self.a0, self.b0, None, None, None,
+                                             None, self.tau_par, self.tau_mom, self.ab[2:4])
+            self._ab_fresh[key] = True
+        ab = self.ab.cpu().numpy()
+        A, B = (ab[0], ab[1]) if key == 'mu' else (ab[2], ab[3])
+        return float(A - B / b)
+
+    def _annealed_weights_term(self, b):
+        """A - T B of the Dirichlet weights from their K parameters and moments (host, K <= 64)."""
+        from scipy.special import gammaln
+        a0 = self.prior_r.cpu().numpy().astype(np.float64)
+        a, e = self.alpha_r.cpu().numpy(), self.elog_r.cpu().numpy()
+        A = gammaln(a0.sum()) - gammaln(a0).sum() + np.dot(a0, e)
+        B = gammaln(a.sum()) - gammaln(a).sum() + np.dot(a, e)
+        return float(A - B / b)
 
     def _bound_terms(self):
         k = self.kernels
         D, K = self.D, self.K
+        bz, bmu, btau, bal = self._L_annealing
+        if (bz, bmu, btau, bal) != (1.0, 1.0, 1.0, 1.0) or not all(self._plain.values()):
+            return self._bound_terms_annealed(bz, bmu, btau, bal)
         k.tables(D, K, self.mu_mom, self.tau_mom, self.elog_r, self.h_now, self.q_now,
                  self.c_now, self.gsum)
         k.dot(D * K, self.S1, self.h_now, self.ws_small, self.scal[6:7])
@@ -297,6 +421,28 @@ class DiagGaussianMixturePlan(PlateMixturePlan):
         s, entropy = self._host_scal()
         return dict(Y=float(s[6] + s[7] + s[8]) - 0.5 * self.N * D * np.log(2 * np.pi),
                     Z=float(s[9]) + entropy, mu=float(s[3]), tau=float(s[4]), alpha=float(s[5]))
+
+    def _bound_terms_annealed(self, bz, bmu, btau, bal):
+        """The terms when a coefficient is not 1, or a q was made by an annealed update: Y as ever,
+        Z with its entropy part times T_z, mu / tau / alpha as A - T B (the single slots of the
+        plain updates hold A - B of a q made by a plain update, and serve at T = 1)."""
+        k = self.kernels
+        D, K = self.D, self.K
+        k.tables(D, K, self.mu_mom, self.tau_mom, self.elog_r, self.h_now, self.q_now,
+                 self.c_now, self.gsum)
+        k.dot(D * K, self.S1, self.h_now, self.ws_small, self.scal[6:7])
+        k.dot(D * K, self.S2, self.q_now, self.ws_small, self.scal[7:8])
+        k.dot(K, self.Nk, self.gsum, self.ws_small, self.scal[8:9])
+        k.dot(K, self.Nk, self.elog_r, self.ws_small, self.scal[9:10])
+        s, entropy = self._host_scal()
+        t = dict(Y=float(s[6] + s[7] + s[8]) - 0.5 * self.N * D * np.log(2 * np.pi),
+                 Z=float(s[9]) + entropy / bz)
+        for key, b, slot in (('mu', bmu, 3), ('tau', btau, 4)):
+            plain = b == 1.0 and self._plain[key]
+            t[key] = float(s[slot]) if plain else self._annealed_term(key, b)
+        t['alpha'] = float(s[5]) if bal == 1.0 and self._plain['alpha'] \
+            else self._annealed_weights_term(bal)
+        return t
 
     def get_moments(self, node):
         self._materialize()

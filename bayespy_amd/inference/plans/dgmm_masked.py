@@ -101,6 +101,8 @@ _MASKED_SPEC = _SPEC._replace(mask=_mask_reason,
 
 class MaskedDiagGaussianMixturePlan(DiagGaussianMixturePlan):
 
+    ANNEALING = False       # the masked tables and updates have no annealed forms
+
     KERNELS = MaskedDGMMKernels
 
     @staticmethod

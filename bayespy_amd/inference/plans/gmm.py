@@ -27,6 +27,10 @@ from ...nodes.categorical import Categorical
 from ...nodes.mixture import Mixture
 
 
+# the bit set of vmp_gmm_natural_step; one of them selects the node of vmp_gmm_update_annealed
+STEP_MU, STEP_LAMBDA, STEP_ALPHA = 1, 2, 4
+
+
 class GMMKernels:
 
     def __init__(self, rt):
@@ -75,6 +79,20 @@ class GMMKernels:
     def lower_bound(self, D, K, state):
         self.rt.check(self.lib.vmp_gmm_lower_bound(self.ctx, D, K, ptr(state)))
 
+    # deterministic annealing: the forms with a coefficient (update) or temperatures (bound)
+    def prepare_z_annealed(self, D, K, prior_only, annealing, state):
+        self.rt.check(self.lib.vmp_gmm_prepare_z_annealed(self.ctx, D, K, 1 if prior_only else 0,
+                                                          float(annealing), ptr(state)))
+
+    def update_annealed(self, D, K, node, annealing, state):
+        self.rt.check(self.lib.vmp_gmm_update_annealed(self.ctx, D, K, int(node), float(annealing),
+                                                       ptr(state)))
+
+    def lower_bound_annealed(self, D, K, temperatures, state):
+        tz, ta, tm, tl = (float(t) for t in temperatures)
+        self.rt.check(self.lib.vmp_gmm_lower_bound_annealed(self.ctx, D, K, tz, ta, tm, tl,
+                                                            ptr(state)))
+
     def natural_init(self, D, K, state, phi_mu):
         self.rt.check(self.lib.vmp_gmm_natural_init(self.ctx, D, K, ptr(state), ptr(phi_mu)))
 
@@ -102,6 +120,7 @@ class GMMKernels:
 class GMMPlan:
 
     KIND = 'gmm'            # of its checkpoints
+    ANNEALING = True        # VB.set_annealing: the updates and the bound read node.annealing
 
     @staticmethod
     def describe():
@@ -175,6 +194,7 @@ class GMMPlan:
         self._ready = False
         self._version = 0
         self._L_version = -1
+        self._L_annealing = None
         self._L = None
         for n in roles.values():
             n._plan = self
@@ -279,35 +299,69 @@ class GMMPlan:
         rt, k = self.rt, self.kernels
         rt.sync_stream()
         D, K = self.D, self.K
+        # the coefficient of deterministic annealing (VB.set_annealing); 1.0 runs the plain kernels
+        b = self._annealing(node)
         if node is self.mu:
-            k.update_mu(D, K, self.state)
+            if b == 1.0:
+                k.update_mu(D, K, self.state)
+            else:
+                k.update_annealed(D, K, STEP_MU, b, self.state)
         elif node is self.Lam:
-            k.update_lambda(D, K, self.state)
+            if b == 1.0:
+                k.update_lambda(D, K, self.state)
+            else:
+                k.update_annealed(D, K, STEP_LAMBDA, b, self.state)
         elif node is self.z:
-            k.prepare_z(D, K, False, self.state)
+            # the factor sits in the C table; the pass is the same launch.  The statistics are
+            # sums of r alone, so the all-reduce over a sharded plate is as at 1.0
+            if b == 1.0:
+                k.prepare_z(D, K, False, self.state)
+            else:
+                k.prepare_z_annealed(D, K, False, b, self.state)
             k.pass_(self.Yd, self.N, D, K, self.Rd, self.state, self.ws)
             # child -> parent message sums over the sharded plate (node.py:650)
             self._all_reduce_stats()
         elif node is self.alpha:
-            k.update_alpha(D, K, self.state)
+            if b == 1.0:
+                k.update_alpha(D, K, self.state)
+            else:
+                k.update_annealed(D, K, STEP_ALPHA, b, self.state)
         else:
             return
         self._version += 1
 
+    @staticmethod
+    def _annealing(node):
+        return float(getattr(node, 'annealing', 1.0))
+
+    def _bound_annealing(self):
+        """The coefficients of (z, alpha, mu, Lambda) as the nodes carry them NOW: the temperature
+        of a bound term is the node's at the request, not that of its last update."""
+        return tuple(self._annealing(n) for n in (self.z, self.alpha, self.mu, self.Lam))
+
     def _lower_bound_terms(self):
         self._materialize()
-        if self._L_version != self._version:
+        ann = self._bound_annealing()
+        if self._L_version != self._version or self._L_annealing != ann:
             rt, k, L = self.rt, self.kernels, self.layout
             rt.sync_stream()
-            k.lower_bound(self.D, self.K, self.state)
+            if all(b == 1.0 for b in ann):
+                k.lower_bound(self.D, self.K, self.state)
+            else:
+                k.lower_bound_annealed(self.D, self.K, [1.0 / b for b in ann], self.state)
             host = self.state[L.off_scal:L.off_L + 8].cpu().numpy()
             status = int(host[3])
+            if status == _lib.VMP_ERR_INVALID:
+                _lib.raise_for_status(status, 'annealing leaves a Wishart node of the fused '
+                                      'Gaussian-mixture block with annealing * (n0 + R_k) <= D - 1 '
+                                      'degrees of freedom: raise n0 or the coefficient')
             if status != 0:
                 _lib.raise_for_status(status)
             t = host[8:]
             self._L = dict(Y=float(t[0]), z=float(t[1]), alpha=float(t[2]), mu=float(t[3]),
                            Lambda=float(t[4]), total=float(t[5]))
             self._L_version = self._version
+            self._L_annealing = ann
         return _delta.bound_terms(self._L, self._delta)
 
     def lower_bound_contribution(self, node):
@@ -390,8 +444,6 @@ class GMMPlan:
 
 # ---- stochastic variational inference -----------------------------------------------------------
 
-STEP_MU, STEP_LAMBDA, STEP_ALPHA = 1, 2, 4          # the bit set of vmp_gmm_natural_step
-
 
 def _scalar_multiplier(node):
     """The one factor of a node with at most one plate axis, or None."""
@@ -444,6 +496,17 @@ class GMMSVIPlan(GMMPlan):
     constant.  Opt-in: ``VB(..., engine='fused')``, tried after ``GMMPlan``."""
 
     KIND = 'gmm_svi'
+    ANNEALING = False       # the natural-gradient step has no annealed form
+
+    @staticmethod
+    def _annealing(node):
+        """No node of this plan may carry a coefficient other than 1, however it was set."""
+        b = float(getattr(node, 'annealing', 1.0))
+        if b != 1.0:
+            raise NotImplementedError(
+                "annealing is not built into the fused GMMSVIPlan plan; build the engine with "
+                "VB(..., engine='generic')")
+        return b
 
     @staticmethod
     def describe():

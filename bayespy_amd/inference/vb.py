@@ -434,17 +434,25 @@ class VB:
     # -- deterministic annealing (vmp.py:665-677) ------------------------------------------
     def set_annealing(self, annealing):
         """Annealing coefficient from (0, 1]; 1 = standard updates.  The next iteration's
-        bound is not compared with the previous one (the objective changed)."""
+        bound is not compared with the previous one (the objective changed).  Built into the
+        generic engine and into the fused blocks that declare ``ANNEALING = True`` (the
+        Gaussian mixtures ``GMMPlan`` and ``DiagGaussianMixturePlan``); every other fused plan
+        declines a coefficient other than 1."""
         if not (0.0 < annealing <= 1.0):
             raise ValueError('annealing must be in (0, 1]')
-        for node in self.model:
-            if hasattr(node, 'annealing'):
-                if annealing != 1.0 and node._plan is not None and \
-                        not hasattr(node._plan, 'riemannian_gradient'):
-                    raise NotImplementedError(
-                        "annealing is not built into the fused %s plan; build the engine with "
-                        "VB(..., engine='generic')" % type(node._plan).__name__)
-                node.annealing = float(annealing)
+        todo = [node for node in self.model if hasattr(node, 'annealing')]
+        for node in todo:
+            plan = node._plan
+            if annealing != 1.0 and plan is not None and \
+                    not hasattr(plan, 'riemannian_gradient') and \
+                    not getattr(plan, 'ANNEALING', False):
+                raise NotImplementedError(
+                    "annealing is not built into the fused %s plan (of the fused blocks, the "
+                    "Gaussian mixtures GMMPlan and DiagGaussianMixturePlan take it); build the engine "
+                    "with "
+                    "VB(..., engine='generic')" % type(plan).__name__)
+        for node in todo:
+            node.annealing = float(annealing)
         self.annealing_changed = True
 
     # -- parameter vectors and gradients (vmp.py:401-466) ------------------------------------

@@ -657,6 +657,26 @@ int32_t vmp_gmm_natural_step(vmp_ctx *ctx, int32_t D, int32_t K, int32_t nodes, 
                              double scale, double *state, double *phi_mu);
 /* Lower bound of Y, z, alpha, mu, Lambda (expfamily.py:400-480). */
 int32_t vmp_gmm_lower_bound(vmp_ctx *ctx, int32_t D, int32_t K, double *state);
+/* Deterministic annealing (vmp.py:665-677, expfamily.py:343-350, :400-480): a node with the
+ * coefficient `annealing` = b in (0, 1] updates to b times its natural parameters, and its bound term
+ * weighs the q part by the temperature T = 1 / b.  The plate pass is the one of vmp_gmm_pass: the
+ * factor of z sits in the C table.
+ *   vmp_gmm_prepare_z_annealed   C = b (<log pi_k> + E[log p(y | k)]), every constant included; the
+ *                                -inf of padded clusters stays; prior_only != 0 ignores b
+ *   vmp_gmm_update_annealed      node 1: mu, precision b (beta0 I + R_k <Lambda_k>), the mean as at
+ *                                b = 1; node 2: Lambda, n_k = b (n0 + R_k), V_k = b (V0 + ...), both
+ *                                stored annealed; node 4: alpha_k = b (alpha0_k + R_k)
+ *   vmp_gmm_lower_bound_annealed every term as [cgf_p + phi_p . u] - T [phi_q . u + g_q] with the
+ *                                temperature of its node, q being what the state holds
+ * With b = 1 (T = 1) each gives the bits of the entry point it stands beside.  An annealed Wishart
+ * with b (n0 + R_k) <= D - 1 sets the status word of the state to VMP_ERR_INVALID (the reference
+ * goes on with NaN). */
+int32_t vmp_gmm_prepare_z_annealed(vmp_ctx *ctx, int32_t D, int32_t K, int32_t prior_only,
+                                   double annealing, double *state);
+int32_t vmp_gmm_update_annealed(vmp_ctx *ctx, int32_t D, int32_t K, int32_t node, double annealing,
+                                double *state);
+int32_t vmp_gmm_lower_bound_annealed(vmp_ctx *ctx, int32_t D, int32_t K, double T_z, double T_alpha,
+                                     double T_mu, double T_lambda, double *state);
 
 /* ---- generic plate-broadcast kernels -------------------------------------- *
  *
@@ -1091,6 +1111,22 @@ int32_t vmp_dgmm_update(vmp_ctx *ctx, int32_t D, int32_t K, int32_t which, const
                         const double *prior_b, const double *S1, const double *S2,
                         const double *Nk, const double *other_mom, double *par, double *mom,
                         double *bound);
+/* Deterministic annealing on this block (see vmp_gmm_*_annealed above for the semantics).
+ *   vmp_dgmm_tables_annealed: h, q and c times `annealing` (c less its maximum AFTER the scaling);
+ *       gsum is not scaled, it feeds L_Y.
+ *   vmp_dgmm_update_annealed: which 0 (mu) / 1 (tau): the update with every natural parameter times
+ *       `annealing`; the bound term comes in two parts, ab[0] = A (cgf from the parents + phi_p . u)
+ *       and ab[1] = B (phi_q . u + g_q): the caller forms A - T B with the temperature the node has
+ *       when the bound is asked for.  which 2 (mu) / 3 (tau): A and B alone of the q that par and mom
+ *       hold (whatever update or initialisation made it); the statistics are not read.
+ * With annealing = 1 the tables, par and mom are those of the plain entry points bit for bit. */
+int32_t vmp_dgmm_tables_annealed(vmp_ctx *ctx, int32_t D, int32_t K, double annealing,
+                                 const double *mu_mom, const double *tau_mom, const double *elog_pi,
+                                 double *h, double *q, double *c, double *gsum);
+int32_t vmp_dgmm_update_annealed(vmp_ctx *ctx, int32_t D, int32_t K, int32_t which,
+                                 double annealing, const double *prior_a, const double *prior_b,
+                                 const double *S1, const double *S2, const double *Nk,
+                                 const double *other_mom, double *par, double *mom, double *ab);
 
 /* The same block with missing observations, Y.observe(y, mask=m) with m of the full shape (N, D)
  * (details: bayespy_amd/csrc/vmp_dgmm_masked.hip, vmp_dgmm_masked_dev.h).  With yt = m o y the logit
