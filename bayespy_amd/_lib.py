@@ -295,6 +295,9 @@ SIGNATURES = {
     'vmp_mix_natural_step': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                      c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                      c_f64, c_f64, c_vp, c_vp]),
+    'vmp_dgmm_natural_step_workspace': (c_i32, [c_i32, c_i32, P(c_i64)]),
+    'vmp_dgmm_natural_step': (c_i32, [c_vp, c_i32, c_i32, c_i32] + [c_vp] * 7 + [c_i32]
+                              + [c_vp] * 8 + [c_f64, c_f64, c_vp, c_vp]),
     'vmp_ctx_set_timing': (c_i32, [c_vp, c_i32]),
     'vmp_pca_xjoin': (c_i32, [c_vp]),
     'vmp_pca_hold_passes': (c_i32, [c_vp, c_i32]),

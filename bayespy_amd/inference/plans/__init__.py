@@ -14,6 +14,7 @@ from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
+from .dgmm_svi import DiagGaussianMixtureSVIPlan, MaskedDiagGaussianMixtureSVIPlan
 from .cmm import CategoricalMixturePlan, CategoricalMixtureSVIPlan
 from .pmm import PoissonMixturePlan, PoissonMixtureSVIPlan
 from .mmm import MultinomialMixturePlan, MultinomialMixtureSVIPlan
@@ -57,6 +58,11 @@ OPT_IN_BATCHES = {BernoulliMixturePlan: [BernoulliMixtureSVIPlan],
                   PoissonMixturePlan: [PoissonMixtureSVIPlan],
                   MultinomialMixturePlan: [MultinomialMixtureSVIPlan],
                   BinomialMixturePlan: [BinomialMixtureSVIPlan]}
+# engine='fused+batches+gaussian': the forms of the two diagonal-Gaussian blocks under mini-batches
+# (plans/dgmm_svi.py), each tried right after its block.  Everything else is engine='fused+batches';
+# 'fused' and 'fused+batches' do not try these forms and keep raising for such a model
+OPT_IN_GAUSSIAN_BATCHES = {DiagGaussianMixturePlan: [DiagGaussianMixtureSVIPlan],
+                           MaskedDiagGaussianMixturePlan: [MaskedDiagGaussianMixtureSVIPlan]}
 
 
 def _with_masked(types):
@@ -67,6 +73,11 @@ def _with_masked(types):
 def _with_batches(types):
     """``types`` with the plan classes of ``OPT_IN_BATCHES`` inserted after their block."""
     return [Q for P in types for Q in [P] + OPT_IN_BATCHES.get(P, [])]
+
+
+def _with_gaussian_batches(types):
+    """``types`` with the plan classes of ``OPT_IN_GAUSSIAN_BATCHES`` inserted after their block."""
+    return [Q for P in types for Q in [P] + OPT_IN_GAUSSIAN_BATCHES.get(P, [])]
 
 
 def opt_in_types():
@@ -136,13 +147,17 @@ def compile_model(nodes, engine=None, **options):
     import os
     if engine is None:
         engine = os.environ.get('BAYESPY_AMD_ENGINE', 'auto')
-    batches = engine == 'fused+batches'
+    gaussian = engine == 'fused+batches+gaussian'
+    batches = gaussian or engine == 'fused+batches'
     if batches:
         engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
     if kept is not None and not batches \
             and any(type(p) in v for p in kept for v in OPT_IN_BATCHES.values()):
         kept = None             # a mini-batch form is kept only where it is asked for
+    if kept is not None and not gaussian \
+            and any(type(p) in v for p in kept for v in OPT_IN_GAUSSIAN_BATCHES.values()):
+        kept = None
     if kept is not None:
         return kept
     stale = [n.name for n in nodes if isinstance(n, Stochastic) and n._plan is not None
@@ -163,6 +178,8 @@ def compile_model(nodes, engine=None, **options):
         else PLAN_TYPES
     if batches:
         types = _with_batches(types)
+    if gaussian:
+        types = _with_gaussian_batches(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

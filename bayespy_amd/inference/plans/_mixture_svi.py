@@ -28,8 +28,9 @@ multiplied by m (expfamily.py:470-480) and the total is formed again from the te
 Opt-in: ``VB(..., engine='fused+batches')``, which is ``engine='fused'`` plus the forms of
 ``plans.OPT_IN_BATCHES``; plain ``engine='fused'`` keeps raising for such a model with the blocks'
 reasons.  Declined with a reason: a multiplier on a global node, different or non-positive factors on ``Z``
-and ``X``, a factor on another axis, sharded plates; both diagonal-Gaussian blocks have no such
-form (their means and precisions are two coupled tables).
+and ``X``, a factor on another axis, sharded plates.  Both diagonal-Gaussian blocks have such a
+form too, with a step kernel of their own for their two coupled tables (dgmm_svi.py,
+``engine='fused+batches+gaussian'``).
 """
 import numpy as np
 
@@ -82,6 +83,11 @@ class MixtureSVI:
         self._m_seen = batch_multiplier(self.Z)
         self._z_init_seen = self.Z._init
         self._pass_due = False
+        self._step_setup()
+
+    def _step_setup(self):
+        """Once, after the set-up of the block: the workspace of the step, and the parameters a
+        point mass steps from."""
         t = self._step_table()
         self.ws_step = self.rt.empty(self.kernels.natural_step_workspace(t['kind'], t['rows'],
                                                                          t['cols'], self.K))
@@ -132,6 +138,10 @@ class MixtureSVI:
             return gammaln(v.sum(-1)) - gammaln(v).sum(-1)
         elog = digamma(a) - digamma(a.sum(-1, keepdims=True))
         return float(np.sum((p - a) * elog) + np.sum(g(p) - g(a)))
+
+    def _unseen_terms(self):
+        """``_unseen_term`` per role whose bound term leaves the rows of ``_unseen_rows`` out."""
+        return {self.PARAM: self._unseen_term()}
 
     def _run_pass(self, r_out=None):
         self._pass_due = False
@@ -212,7 +222,8 @@ class MixtureSVI:
             t = self._L
             for key in (self.OBSERVED, 'Z'):
                 t[key] = m * t[key]
-            t[self.PARAM] = t[self.PARAM] - self._unseen_term()
+            for key, left_out in self._unseen_terms().items():
+                t[key] = t[key] - left_out
             total = t[self.TERMS[0]]
             for key in self.TERMS[1:]:
                 total = total + t[key]

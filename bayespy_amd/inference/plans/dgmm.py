@@ -23,7 +23,8 @@ g = sum_d (1/2 <log tau> - 1/2 <tau><mu^2>) of the PRESENT moments:
 The bound terms of ``mu`` and ``tau`` come from ``vmp_dgmm_update``, that of ``alpha`` from the
 Dirichlet kernel.  Masks, mini-batches and sharded plates are declined (generic engine); a mask of
 the full shape (N, D) is taken by the subclass of dgmm_masked.py, to which an unobserved model
-goes over when ``Y`` is observed with such a mask.
+goes over when ``Y`` is observed with such a mask, and mini-batches by the forms of dgmm_svi.py
+(``engine='fused+batches+gaussian'``).
 
 Checkpoints: the block writes its own ``plans/<i>/`` group (kind 'dgmm') like every fused plan.
 """
@@ -79,6 +80,22 @@ class DGMMKernels(DirichletKernels):
         self.rt.check(self.lib.vmp_dgmm_update(self.ctx, D, K, which, _p(prior_a), _p(prior_b),
                                                _p(S1), _p(S2), _p(Nk), _p(other), _p(par), _p(mom),
                                                _p(bound)))
+
+    # stochastic VI (dgmm_svi.py); these take the place of the one-table forms of DirichletKernels
+    def natural_step_workspace(self, D, K):
+        """The doubles of ``ws`` that ``natural_step`` needs."""
+        w = ctypes.c_int64()
+        self.rt.check(self.lib.vmp_dgmm_natural_step_workspace(D, K, ctypes.byref(w)))
+        return w.value
+
+    def natural_step(self, D, K, nodes, m0, beta0, a0, b0, S1, S2, cnt, per_element, mu_par, mu_mom,
+                     tau_par, tau_mom, prior_r, Nk, alpha_r, elog_r, mult, scale, ws, bound):
+        """``vmp_dgmm_natural_step``: mu (bit 1 of ``nodes``), tau (bit 2) and the weights row
+        (bit 4) one step along their natural gradients, in one launch; ``bound`` has three slots."""
+        self.rt.check(self.lib.vmp_dgmm_natural_step(
+            self.ctx, D, K, nodes, _p(m0), _p(beta0), _p(a0), _p(b0), _p(S1), _p(S2), _p(cnt),
+            per_element, _p(mu_par), _p(mu_mom), _p(tau_par), _p(tau_mom), _p(prior_r), _p(Nk),
+            _p(alpha_r), _p(elog_r), float(mult), float(scale), _p(ws), _p(bound)))
 
     # deterministic annealing
     def tables_annealed(self, D, K, annealing, mu_mom, tau_mom, elog_pi, h, q, c, gsum=None):
@@ -177,6 +194,10 @@ class DiagGaussianMixturePlan(PlateMixturePlan):
         self.y = t
         self._stale = False
 
+    def _repack(self):
+        """New observations of the same shape: y again (with its mask in dgmm_masked.py)."""
+        self._upload_y()
+
     def _const(self, node, i, positive, what):
         a = np.asarray(node.parents[i].value, dtype=np.float64)
         if positive and np.any(a <= 0):
@@ -186,8 +207,7 @@ class DiagGaussianMixturePlan(PlateMixturePlan):
     def _materialize(self):
         if self._ready:
             if self._stale:
-                self._upload_y()
-                self._run_pass()
+                self._restate()
             return
         self._delta = _delta.delta_roles(self.roles)
         rt, k = self.rt, self.kernels

@@ -1492,6 +1492,41 @@ int32_t vmp_mix_natural_step(vmp_ctx *ctx, int32_t kind, int32_t nodes, int64_t 
                              const double *prior_r, const double *Nk, double *alpha_r,
                              double *elog_r, double mult, double scale, double *ws, double *bound);
 
+/* Stochastic VI on the two diagonal-Gaussian-mixture blocks: the global half of a step in one launch
+ * (details: bayespy_amd/csrc/vmp_dgmm_svi.hip, vmp_dgmm_svi_dev.h).  `nodes` is a bit set: 1 = mu,
+ * 2 = tau, 4 = the mixing weights.  Tables in the layout of vmp_dgmm_update: priors, S1, S2 (D x K),
+ * par and mom (D K, 2) with mu = ((m, lambda), (<mu>, <mu^2>)) and tau = ((a, b), (<tau>, <log tau>));
+ * cnt = N_k (K, per_element 0) or the count of the element M (D x K, per_element 1, the block with
+ * missing observations).  S1, S2 and cnt are given together or all null (phi* is the prior).
+ * Element e = d K + k moves in the natural parameters, both nodes from the state at entry:
+ *   mu:  lambda* = beta0 + mult <tau> cnt, (lambda m)* = beta0 m0 + mult <tau> S1
+ *   tau: a* = a0 + mult cnt / 2, b* = b0 + mult (S2 - 2 <mu> S1 + <mu^2> cnt) / 2
+ *   phi <- phi + scale (phi* - phi)
+ * and the weights (K <= 64 contiguous columns: prior_r, Nk (null: the prior), alpha_r, elog_r) as in
+ * vmp_mix_natural_step.  A thread owns element e of both tables and reads whatever it needs of both
+ * before it stores; the weights row is one more workgroup.  What a node that is not named owns is not
+ * written (its moments are read where the named node needs them: <tau> by mu, <mu> and <mu^2> by
+ * tau), nor is its bound slot.
+ *   scale == 1 does not read the old parameters (they may be NaN) and, with mult == 1, leaves par, mom
+ *   and the bound term of vmp_dgmm_update (per_element 1: of vmp_dgmm_update_masked) bit for bit.
+ *   bound[0] = <log p> - <log q> of mu, bound[1] of tau, bound[2] of the weights, each written only
+ *   when its node is named.  No floating-point atomics: a thread leaves the terms of its element in ws
+ *   (vmp_dgmm_natural_step_workspace doubles, host only; its last word is the ticket, cleared on the
+ *   stream ahead of the launch) and the workgroup that finishes last adds them in the order of
+ *   vmp_dgmm_update; the grid depends on (D, K, nodes) and the bits of every output on the inputs
+ *   and the shape only.
+ *   D or K < 1, nodes outside 1..7, per_element outside 0..1, mult <= 0, a NaN mult or scale, a null
+ *   required pointer, statistics given in part: VMP_ERR_INVALID; D or K above vmp_dgmm_limits:
+ *   VMP_ERR_UNSUPPORTED.  Nothing is launched or written after a refusal. */
+int32_t vmp_dgmm_natural_step_workspace(int32_t D, int32_t K, int64_t *workspace_doubles);
+int32_t vmp_dgmm_natural_step(vmp_ctx *ctx, int32_t D, int32_t K, int32_t nodes, const double *m0,
+                              const double *beta0, const double *a0, const double *b0,
+                              const double *S1, const double *S2, const double *cnt,
+                              int32_t per_element, double *mu_par, double *mu_mom, double *tau_par,
+                              double *tau_mom, const double *prior_r, const double *Nk,
+                              double *alpha_r, double *elog_r, double mult, double scale, double *ws,
+                              double *bound);
+
 /* Measurement knob: overrides a launch parameter the library otherwise takes from its
  * environment variable / default ("xpass_nt", "xpass_wgs_per_cu", "xpass_occ",
  * "plate_stream", ...); process-wide, for A/B harnesses (tools/xpass_lab.hip). */
