@@ -310,6 +310,7 @@ SIGNATURES = {
     'vmp_pca_sweep_mid_count': (c_i32, [c_vp, P(c_i64)]),
     'vmp_pca_sweep_stamps': (c_i32, [c_vp, c_vp, c_i32, P(c_i32), P(c_i32)]),
     'vmp_pca_gram_stats_form': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32]),
+    'vmp_mfma_order_probe': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'vmp_pca_small_ops': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_f64, c_f64, c_f64, c_f64, c_f64,
                                   c_i32, P(c_i32), c_vp]),
     'vmp_pca_small_ops_mean': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_f64, c_f64, c_f64, c_f64, c_f64,

@@ -130,7 +130,8 @@ int32_t vmp_pca_launch_sweep_tail(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_
 // workgroups (pca_sweep_mid_kernel, vmp_pca_small.hip); `ticket` is the sweep's own zeroed word, which
 // the launch leaves zero again; `wide` = 1 selects the wide tail and head of phase B, 2 those and sum
 // <x><x>^T formed by the tail ("pca_sweep_local_pxx"), 3 those and the bound deferred to the first
-// inverse of the head ("pca_sweep_defer"; vmp_pca_sweep_constants first); `stamps` (null: none) the
+// inverse of the head ("pca_sweep_defer"; vmp_pca_sweep_constants first), 4 those and the chains of
+// sum y<x>^T and sum <x><x>^T on the matrix cores ("pca_sweep_mfma"); `stamps` (null: none) the
 // stamped build and its row, `stamp_level` the value of "pca_sweep_stamps"
 int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                                  double a0t, double b0t, double a0a, double b0a, double *state,
@@ -145,6 +146,7 @@ int32_t vmp_pca_launch_sweep_head_wide(vmp_ctx *ctx, int32_t D, int32_t K, int64
                                        double x_prec, double a0t, double b0t, double a0a, double b0a,
                                        double *state);
 // the Gram statistics of that kernel alone: Syx rows into the state, DP / 8 partial blocks into P
+// (`wide` 0: the narrow body, 1: the wide body, 2: the wide body with Syx on the matrix cores)
 int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P,
                                  int32_t wide);
 

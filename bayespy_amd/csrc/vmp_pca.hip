@@ -1359,6 +1359,11 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
     // sweep instead of reading the sweep-invariant ones from ctx->sweep_sf (the same bits)
     if (wide == 2 && vmp_tune_get("pca_sweep_defer", env_int("VMP_PCA_SWEEP_DEFER", 1, 0, 1)))
         wide = 3;
+    // "pca_sweep_mfma" = 0 (VMP_PCA_SWEEP_MFMA=0), with all of the above: the chains of sum y<x>^T in
+    // phase A and of sum <x><x>^T in the tail are scalar fused multiply-adds fed from LDS instead of
+    // running on the matrix cores (the same bits: the fp64 matrix instructions add their products in
+    // ascending order of the k-slots, fused; tests/test_mfma_order_gpu.py)
+    const bool mfma = wide == 3 && vmp_tune_get("pca_sweep_mfma", env_int("VMP_PCA_SWEEP_MFMA", 1, 0, 1));
     if (ticket && wide == 3) {
         rc = vmp_pca_sweep_constants(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha, b0_alpha);
         if (rc != VMP_OK) return rc;
@@ -1420,7 +1425,7 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
         if (ticket && !last) {
             // Gram statistics, tail and the head of sweep i + 1 in one launch
             rc = vmp_pca_launch_sweep_mid(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
-                                          b0_alpha, state, P, t, ctx->sweep_tickets + i, wide,
+                                          b0_alpha, state, P, t, ctx->sweep_tickets + i, mfma ? 4 : wide,
                                           stamps ? ctx->sweep_stamps + (size_t)i * VMP_SWEEP_NSTAMP
                                                  : nullptr, stamp_level);
             if (rc != VMP_OK) return rc;
@@ -1486,8 +1491,8 @@ int32_t vmp_pca_gram_stats_form(vmp_ctx *ctx, int32_t D, int32_t K, double *stat
     VMP_REQUIRE(ctx, rc == VMP_OK, rc, "unsupported dims D=%d K=%d", D, K);
     double *P = reinterpret_cast<double *>(workspace);
     if (form == 0) return run_gram_stats(ctx, L, D, K, state, P, ctx->stream, nullptr, false);
-    VMP_REQUIRE(ctx, form == 1 || form == 2, VMP_ERR_INVALID, "form %d (0, 1 or 2)", form);
-    return vmp_pca_launch_gram_fast(ctx, D, K, state, P, form == 2);
+    VMP_REQUIRE(ctx, form >= 1 && form <= 3, VMP_ERR_INVALID, "form %d (0, 1, 2 or 3)", form);
+    return vmp_pca_launch_gram_fast(ctx, D, K, state, P, form - 1);
 }
 
 int32_t vmp_pca_last_pass_ms(vmp_ctx *ctx, double *ms_pass, double *ms_reduce)

@@ -841,7 +841,7 @@ static_assert(sizeof(tail_lds<16>) % 16 == 0 && sizeof(tail_lds<32>) % 16 == 0, 
 // <log alpha>, the bound, the ring slot and the stop rule to defer_side below, which one wavefront
 // runs beside the head's first inverse.  resid and trx wait in red[0] and red[1].
 template <int KP, int MODE, bool WIDE = false, class STAMP = stamps_off, bool LOCAL = false,
-          bool DEFER = false>
+          bool DEFER = false, bool MFMA = false>
 __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, const vmp_sweep_tail *sw,
                                               tail_lds<KP> &s, double *SW = nullptr,
                                               const STAMP &stamp = STAMP(), const double *AL = nullptr)
@@ -849,6 +849,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
     static_assert(!WIDE || MODE == TAIL_SWEEP, "the wide tail is a sweep tail");
     static_assert(!LOCAL || WIDE, "sum <x><x>^T is formed locally by the wide tail only");
     static_assert(!DEFER || LOCAL, "the bound is deferred behind the local wide tail only");
+    static_assert(!MFMA || LOCAL, "sum <x><x>^T runs on the matrix cores in its local form only");
     constexpr bool GRAM = (MODE == TAIL_GRAM);
     constexpr int LDM = KP + 1, E = KP * KP / NTF;
     extern __shared__ __align__(16) double gl[];          // GRAM: A (KP x (DP+1)) | G batch (GB x (DP+1)) | S batch (GB x LDM)
@@ -1055,7 +1056,52 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
     (void)ww; (void)wy; (void)es0; (void)es1;
     __syncthreads();
     stamp(SP_T_LOADS);
-    if constexpr (LOCAL) {
+    if constexpr (LOCAL && MFMA) {
+        // The local form below on v_mfma_f64_16x16x4_f64 ("pca_sweep_mfma"): a wavefront owns a 16 x 16
+        // tile of outputs, a group's partial is two instructions from zero -- rows 0..3 of the group
+        // in the four k-slots, then rows 4..7, C carried -- and the instruction adds its four products
+        // to C as a chain of fused multiply-adds in ascending slot order (tests/test_mfma_order_gpu.py):
+        // the chain of 8 of the scalar form.  The partials are added as there.  Lane l: A operand
+        // A[16 ti + l % 16][8 b + 4 h + l / 16], B operand Syx[8 b + 4 h + l / 16][16 tj + l % 16],
+        // results (16 ti + l / 16 + 4 reg, 16 tj + l % 16).
+        constexpr int KT = KP / 16;
+        const int LA = L.DP + 2;
+        const int w = tid >> 6, l15 = tid & 15, l4 = (tid & 63) >> 4;
+        const int nb = sw->nb, nb4 = nb & ~3;
+        if (w < KT * KT) {
+            const int ti = w / KT, tj = w % KT;
+            const double *ar = AL + (16 * ti + l15) * LA + l4;
+            const double *sr = SW + l4 * LDM + 16 * tj + l15;
+            const auto group = [&](int b) {
+                v4f64 p = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int h = 0; h < GRA; h += 4)
+                    p = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[b * GRA + h], sr[(b * GRA + h) * LDM], p,
+                                                             0, 0, 0);
+                return p;
+            };
+            v4f64 acc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = v4f64{0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+            for (int b = 0; b < nb4; b += 4) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[q] += group(b + q);
+            }
+#pragma unroll 1
+            for (int b = nb4; b < nb; ++b) acc[0] += group(b);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = 16 * ti + l4 + 4 * r, k2 = 16 * tj + l15;
+                const bool in = (k < K && k2 < K);
+                const double x = in ? (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]) : 0.0;
+                st[L.off_S + (L.DP + k) * KP + k2] = x;
+                Sx[k * LDM + k2] = x;
+            }
+        }
+        __syncthreads();
+        stamp(SP_T_PXX);
+    } else if constexpr (LOCAL) {
         // sum <x><x>^T [k][k'] = sum_b Pxx_b[k][k'], Pxx_b[k][k'] = sum_{r in group b} A[k][r] Syx[r][k']:
         // each partial its own chain of multiply-adds from zero over the 8 rows in ascending order
         // (gram_phase_a_wide), the partials added four at a time as above (reduce_partials_kernel).
@@ -1418,7 +1464,13 @@ __host__ __device__ inline size_t gram_phase_a_wide_lds(int KP, int DP)
 }
 
 // PXX = false ("pca_sweep_local_pxx"): the phase ends with the Syx rows; A stays in LDS for the tail
-template <int KP, class STAMP = stamps_off, bool PXX = true>
+// MFMA ("pca_sweep_mfma"): the Syx chains run on v_mfma_f64_4x4x4_4b_f64, which adds its four products
+// to C as a chain of fused multiply-adds over the k-slots in ascending order
+// (tests/test_mfma_order_gpu.py) -- so d = 4 q + slot, C carried over q, is the scalar chain of every
+// output bit for bit.  A wavefront owns the same 4 rows x 16 columns as below, as four 4 x 4 blocks
+// (lane x + 4 b + 16 s: row x of G and column 4 b + x of the 16, both at d = 4 q + s; its result is
+// row s, column 4 b + x: the output the scalar form gives this lane).  Operands at d >= D are zero.
+template <int KP, class STAMP = stamps_off, bool PXX = true, bool MFMA = false>
 __device__ __forceinline__ void gram_phase_a_wide(const vmp_pca_layout &L, int D, int K, double *st,
                                                   double *P, double *lds, int blk,
                                                   const STAMP &stamp = STAMP())
@@ -1466,10 +1518,37 @@ __device__ __forceinline__ void gram_phase_a_wide(const vmp_pca_layout &L, int D
         const int w = tid >> 6, l = tid & 63;
         if (w < 2 * KT) {
             const int k = (l & 15) + 16 * (w % KT), r = (l >> 4) + 4 * (w / KT);
-            const double *g = Gs + r * DP, *ar = As + k * LA;
             double s = 0.0;
+            if constexpr (MFMA) {
+                // (r - l / 16 is the first of the wavefront's 4 rows, l / 16 this lane's k-slot)
+                const int sl = l >> 4;
+                const double *gx = Gs + (r - sl + (l & 3)) * DP + sl, *ax = As + k * LA + sl;
+                const int D4 = D & ~3;
+                int d = 0;
+                // eight k-steps at a time, their sixteen LDS reads requested before the first is used
+                for (; d + 32 <= D4; d += 32) {
+                    double gq[8], aq[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        gq[q] = gx[d + 4 * q];
+                        aq[q] = ax[d + 4 * q];
+                    }
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) s = __builtin_amdgcn_mfma_f64_4x4x4f64(gq[q], aq[q], s, 0, 0, 0);
+                }
+                for (; d < D4; d += 4) s = __builtin_amdgcn_mfma_f64_4x4x4f64(gx[d], ax[d], s, 0, 0, 0);
+                // D % 4 != 0: the last step, its k-slots at d >= D zero (read in bounds -- D4 + 3 < DP --
+                // and masked afterwards, not behind a branch)
+                if (D4 < D) {
+                    const double g4 = gx[D4], a4 = ax[D4];
+                    const bool in = D4 + sl < D;
+                    s = __builtin_amdgcn_mfma_f64_4x4x4f64(in ? g4 : 0.0, in ? a4 : 0.0, s, 0, 0, 0);
+                }
+            } else {
+                const double *g = Gs + r * DP, *ar = As + k * LA;
 #pragma unroll 16
-            for (int d = 0; d < D; ++d) s = __builtin_fma(g[d], ar[d], s);
+                for (int d = 0; d < D; ++d) s = __builtin_fma(g[d], ar[d], s);
+            }
             Ss[r * LDS_S + k] = s;
             if (r0 + r < D && k < K) st[L.off_S + (r0 + r) * KP + k] = s;
         }
@@ -1495,12 +1574,12 @@ __device__ __forceinline__ void gram_phase_a_wide(const vmp_pca_layout &L, int D
 }
 
 // that phase A alone (tests: bitwise against pca_gram_stats_kernel)
-template <int KP>
+template <int KP, bool MFMA = false>
 __global__ void __launch_bounds__(NTF)
 pca_gram_wide_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
 {
     extern __shared__ __align__(16) double gl[];
-    gram_phase_a_wide<KP>(L, D, K, st, P, gl, blockIdx.x);
+    gram_phase_a_wide<KP, stamps_off, true, MFMA>(L, D, K, st, P, gl, blockIdx.x);
 }
 
 // Phase B, the workgroup that draws the last ticket: the tail of this sweep and, unless that tail
@@ -1773,13 +1852,14 @@ __host__ __device__ inline size_t sweep_local_lds(int KP, int DP)
     return ((size_t)KP * (DP + 2) + (size_t)DP * (KP + 1) + 2) * sizeof(double);
 }
 
-template <int KP, bool WIDE, bool LOCAL, bool DEFER, class STAMP>
+template <int KP, bool WIDE, bool LOCAL, bool DEFER, bool MFMA, class STAMP>
 __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *st, double *P,
                                                    const vmp_sweep_tail &sw, unsigned int *ticket,
                                                    const double *sf, const STAMP &stamp)
 {
     static_assert(!LOCAL || WIDE, "sum <x><x>^T is formed locally beside the wide bodies only");
     static_assert(!DEFER || LOCAL, "the bound is deferred behind the local wide tail only");
+    static_assert(!MFMA || DEFER, "the matrix-core Gram products are built for the deferred form only");
     extern __shared__ __align__(16) double gl[];
     __shared__ tail_lds<KP> ts;
     const int tid = threadIdx.x;
@@ -1793,7 +1873,7 @@ __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *
     }
     stamp(SP_ENTRY);
     if constexpr (WIDE)
-        gram_phase_a_wide<KP, STAMP, !LOCAL>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
+        gram_phase_a_wide<KP, STAMP, !LOCAL, MFMA>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
     else
         gram_phase_a<KP>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1821,7 +1901,7 @@ __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *
     __syncthreads();
     stamp(SP_ACQUIRE);
     // (every thread has read the ticket word: the dynamic region is free for SW)
-    pca_tail_body<KP, TAIL_SWEEP, WIDE, STAMP, LOCAL, DEFER>(a, st, &sw, ts, SW, stamp, gl);
+    pca_tail_body<KP, TAIL_SWEEP, WIDE, STAMP, LOCAL, DEFER, MFMA>(a, st, &sw, ts, SW, stamp, gl);
     __syncthreads();
     if constexpr (DEFER) {
         // the rest of the tail, the stop rule included, runs beside the head's first inverse; the
@@ -1845,18 +1925,18 @@ __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *
 // ("pca_sweep_defer", default, with LOCAL): the tail hands over as soon as the head's inputs are
 // ready and the bound, the ring slot and the stop rule run beside the head's first inverse, with the
 // sweep-invariant special functions read from `sf` (vmp_ctx::sweep_sf; not read otherwise).
-template <int KP, bool WIDE, bool LOCAL, bool DEFER = false>
+template <int KP, bool WIDE, bool LOCAL, bool DEFER = false, bool MFMA = false>
 __global__ void __launch_bounds__(NTF)
 pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, unsigned int *ticket,
                      const double *sf)
 {
-    pca_sweep_mid_body<KP, WIDE, LOCAL, DEFER>(a, st, P, sw, ticket, sf, stamps_off());
+    pca_sweep_mid_body<KP, WIDE, LOCAL, DEFER, MFMA>(a, st, P, sw, ticket, sf, stamps_off());
 }
 
 // the same with wall_clock64 stamps ("pca_sweep_stamps"): `out` is this launch's row of
 // VMP_SWEEP_NSTAMP words, written by the workgroup that ran phase B; `level` the key's value (2: the
 // side wavefront of the deferred form stamps too)
-template <int KP, bool WIDE, bool LOCAL, bool DEFER = false>
+template <int KP, bool WIDE, bool LOCAL, bool DEFER = false, bool MFMA = false>
 __global__ void __launch_bounds__(NTF)
 pca_sweep_mid_stamped_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw,
                              unsigned int *ticket, const double *sf, unsigned long long *out, int level)
@@ -1865,7 +1945,7 @@ pca_sweep_mid_stamped_kernel(small_args a, double *st, double *P, vmp_sweep_tail
     if (threadIdx.x < VMP_SWEEP_NSTAMP) stl[threadIdx.x] = 0;
     __syncthreads();
     const stamps_on stamp{stl, level};
-    pca_sweep_mid_body<KP, WIDE, LOCAL, DEFER>(a, st, P, sw, ticket, sf, stamp);
+    pca_sweep_mid_body<KP, WIDE, LOCAL, DEFER, MFMA>(a, st, P, sw, ticket, sf, stamp);
     // (a workgroup that did not run phase B leaves no tail stamp)
     if (threadIdx.x == 0 && stl[SP_T_LOADS] != 0)
         for (int i = 0; i < VMP_SWEEP_NSTAMP; ++i) out[i] = stl[i];
@@ -1939,6 +2019,36 @@ pca_sweep_sf_kernel(small_args a, double *sf)
     default: v = sf_log(a.x_prec); break;
     }
     sf[l] = v;
+}
+
+// The two fp64 matrix instructions on caller-supplied tiles, one wavefront, one instruction per
+// tile (vmp_mfma_order_probe; tests/test_mfma_order_gpu.py reads the order of accumulation off the
+// bits).  FORM 0: v_mfma_f64_16x16x4_f64, A 16 x 4, B 4 x 16, C and D 16 x 16, row-major.
+// FORM 1: v_mfma_f64_4x4x4_4b_f64, four independent blocks, A[b][i][k], B[b][k][j], C and D [b][i][j].
+template <int FORM>
+__global__ void __launch_bounds__(64)
+mfma_order_probe_kernel(int n, const double *A, const double *B, const double *C, double *Dm)
+{
+    const int l = threadIdx.x, lo = l & 15, k = l >> 4;
+    for (int t = 0; t < n; ++t) {
+        if constexpr (FORM == 0) {
+            const double *Ct = C + (size_t)t * 256;
+            double *Dt = Dm + (size_t)t * 256;
+            v4f64 c;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) c[r] = Ct[(k + 4 * r) * 16 + lo];
+            const v4f64 d = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(size_t)t * 64 + lo * 4 + k],
+                                                                 B[(size_t)t * 64 + k * 16 + lo], c, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Dt[(k + 4 * r) * 16 + lo] = d[r];
+        } else {
+            // lane x + 4 b + 16 k holds A[b][x][k] and B[b][k][x]; lane j + 4 b + 16 i holds D[b][i][j]
+            const int x = l & 3, b = (l >> 2) & 3;
+            const size_t o = (size_t)t * 64 + b * 16;
+            Dm[o + k * 4 + x] = __builtin_amdgcn_mfma_f64_4x4x4f64(A[o + x * 4 + k], B[o + k * 4 + x],
+                                                                   C[o + k * 4 + x], 0, 0, 0);
+        }
+    }
 }
 
 bool fast_small_enabled()
@@ -2160,7 +2270,18 @@ int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *sta
     const int nb = (int)(L.DP / GRA);
     if (wide) {
         const size_t ldw = gram_phase_a_wide_lds((int)L.KP, (int)L.DP);
-        if (L.KP == 16)
+        if (wide == 2) {        // Syx on the matrix cores ("pca_sweep_mfma")
+            static bool raised_m[64] = {false};
+            const int32_t rm = raise_lds_once(ctx, pca_gram_wide_kernel<16, true>,
+                                              pca_gram_wide_kernel<32, true>, raised_m);
+            if (rm != VMP_OK) return rm;
+            if (L.KP == 16)
+                hipLaunchKernelGGL((pca_gram_wide_kernel<16, true>), dim3(nb), dim3(NTF), ldw, ctx->stream,
+                                   L, D, K, state, P);
+            else
+                hipLaunchKernelGGL((pca_gram_wide_kernel<32, true>), dim3(nb), dim3(NTF), ldw, ctx->stream,
+                                   L, D, K, state, P);
+        } else if (L.KP == 16)
             hipLaunchKernelGGL(pca_gram_wide_kernel<16>, dim3(nb), dim3(NTF), ldw, ctx->stream, L, D, K,
                                state, P);
         else
@@ -2181,7 +2302,7 @@ int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *sta
 }
 
 // one instantiation of the one-launch sweep; `stamps` (null: the default kernel) is the launch's row
-template <int KP, bool WIDE, bool LOCAL, bool DEFER = false>
+template <int KP, bool WIDE, bool LOCAL, bool DEFER = false, bool MFMA = false>
 static int32_t launch_mid(vmp_ctx *ctx, const small_args &a, double *state, double *P,
                           const vmp_sweep_tail &t, unsigned int *ticket, unsigned long long *stamps,
                           int stamp_level)
@@ -2191,8 +2312,8 @@ static int32_t launch_mid(vmp_ctx *ctx, const small_args &a, double *state, doub
     static bool raised[2][64] = {{false}};
     const int dev = ctx->device & 63, s = stamps ? 1 : 0;
     if (!raised[s][dev]) {
-        const void *f = stamps ? (const void *)pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL, DEFER>
-                               : (const void *)pca_sweep_mid_kernel<KP, WIDE, LOCAL, DEFER>;
+        const void *f = stamps ? (const void *)pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL, DEFER, MFMA>
+                               : (const void *)pca_sweep_mid_kernel<KP, WIDE, LOCAL, DEFER, MFMA>;
         VMP_HIP_CHECK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                96 * 1024));
         raised[s][dev] = true;
@@ -2204,11 +2325,11 @@ static int32_t launch_mid(vmp_ctx *ctx, const small_args &a, double *state, doub
                               : gram_phase_a_lds((int)a.L.KP, (int)a.L.DP);
     const dim3 nb((unsigned)(a.L.DP / GRA));
     if (stamps)
-        hipLaunchKernelGGL((pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL, DEFER>), nb, dim3(NTF), lds,
+        hipLaunchKernelGGL((pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL, DEFER, MFMA>), nb, dim3(NTF), lds,
                            ctx->stream, a, state, P, t, ticket, (const double *)ctx->sweep_sf, stamps,
                            stamp_level);
     else
-        hipLaunchKernelGGL((pca_sweep_mid_kernel<KP, WIDE, LOCAL, DEFER>), nb, dim3(NTF), lds, ctx->stream, a,
+        hipLaunchKernelGGL((pca_sweep_mid_kernel<KP, WIDE, LOCAL, DEFER, MFMA>), nb, dim3(NTF), lds, ctx->stream, a,
                            state, P, t, ticket, (const double *)ctx->sweep_sf);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
@@ -2224,11 +2345,13 @@ int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_t
     if (rc != VMP_OK) return rc;
     const int sl = stamp_level;
     if (a.L.KP == 16)
-        return wide == 3 ? launch_mid<16, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
+        return wide == 4 ? launch_mid<16, true, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
+               : wide == 3 ? launch_mid<16, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
                : wide == 2 ? launch_mid<16, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
                : wide      ? launch_mid<16, true, false>(ctx, a, state, P, t, ticket, stamps, sl)
                            : launch_mid<16, false, false>(ctx, a, state, P, t, ticket, stamps, sl);
-    return wide == 3 ? launch_mid<32, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
+    return wide == 4 ? launch_mid<32, true, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
+           : wide == 3 ? launch_mid<32, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
            : wide == 2 ? launch_mid<32, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
            : wide      ? launch_mid<32, true, false>(ctx, a, state, P, t, ticket, stamps, sl)
                        : launch_mid<32, false, false>(ctx, a, state, P, t, ticket, stamps, sl);
@@ -2269,6 +2392,21 @@ int32_t vmp_pca_launch_sweep_head_wide(vmp_ctx *ctx, int32_t D, int32_t K, int64
 }
 
 extern "C" {
+
+int32_t vmp_mfma_order_probe(vmp_ctx *ctx, int32_t form, int32_t ntiles, const double *A,
+                             const double *B, const double *C, double *D)
+{
+    VMP_REQUIRE(ctx, ctx && A && B && C && D, VMP_ERR_INVALID, "null argument");
+    VMP_REQUIRE(ctx, form == 0 || form == 1, VMP_ERR_INVALID, "form %d (0 or 1)", form);
+    VMP_REQUIRE(ctx, ntiles >= 1 && ntiles <= (1 << 20), VMP_ERR_INVALID, "ntiles %d out of range",
+                ntiles);
+    if (form == 0)
+        hipLaunchKernelGGL(mfma_order_probe_kernel<0>, dim3(1), dim3(64), 0, ctx->stream, ntiles, A, B, C, D);
+    else
+        hipLaunchKernelGGL(mfma_order_probe_kernel<1>, dim3(1), dim3(64), 0, ctx->stream, ntiles, A, B, C, D);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
 
 int32_t vmp_pca_small_ops(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                           double a0_tau, double b0_tau, double a0_alpha, double b0_alpha,

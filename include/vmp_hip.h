@@ -273,6 +273,11 @@ int32_t vmp_pca_sweep_mid_count(vmp_ctx *ctx, int64_t *launches);
  * computed by one small launch when the priors, D, the plate size or x_prec differ from those of the
  * previous call on the context, and read from a buffer of the context (not the state block) after
  * that.  Bitwise the same as 0, where the tail computes all of it each sweep.
+ * With all three and tune key "pca_sweep_mfma" / VMP_PCA_SWEEP_MFMA (default 1) the chains of
+ * sum y<x>^T (phase A, v_mfma_f64_4x4x4_4b_f64) and of the partials of sum <x><x>^T (the tail,
+ * v_mfma_f64_16x16x4_f64) run on the matrix cores instead of as scalar fused multiply-adds fed from
+ * LDS.  Both instructions add their four products to C in ascending order of the k-slots, every
+ * step fused (vmp_mfma_order_probe below), so every chain keeps its bits (0: the scalar chains).
  *
  * Measurement: while tune key "pca_sweep_stamps" is 1, vmp_pca_sweeps launches a stamped build of that
  * kernel, in which one lane records wall_clock64() (a constant 100 MHz counter) at the boundaries of
@@ -288,10 +293,18 @@ int32_t vmp_pca_sweep_stamps(vmp_ctx *ctx, uint64_t *out, int32_t max_rows, int3
 /* The Gram statistics of one sweep alone, from the A and G of the state block: rows of sum y<x>^T
  * into the state, the DP / 8 partial blocks of sum <x><x>^T into the workspace (not added up).
  * form 0: the kernel every other path uses; form 1: the body of the one-launch sweep with
- * "pca_sweep_wide" = 0, form 2: its body with "pca_sweep_wide" = 1 (both K <= 32, D <= 128, 16-byte
- * aligned state).  The three agree bitwise. */
+ * "pca_sweep_wide" = 0, form 2: its body with "pca_sweep_wide" = 1, form 3: that body with the chains of
+ * sum y<x>^T on the matrix cores, "pca_sweep_mfma" = 1 (all three K <= 32, D <= 128, 16-byte aligned
+ * state).  The four agree bitwise. */
 int32_t vmp_pca_gram_stats_form(vmp_ctx *ctx, int32_t D, int32_t K, double *state, void *workspace,
                                 int32_t form);
+/* Test entry: D = A B + C by ONE fp64 matrix instruction per tile, one wavefront, `ntiles` tiles in
+ * a row (device pointers, row-major doubles).  form 0: v_mfma_f64_16x16x4_f64, A 16 x 4, B 4 x 16,
+ * C and D 16 x 16 per tile.  form 1: v_mfma_f64_4x4x4_4b_f64, four independent blocks per tile,
+ * A[b][i][k], B[b][k][j], C and D [b][i][j], 64 doubles each.  tests/test_mfma_order_gpu.py reads
+ * the order in which the four products of an output are accumulated off the bits. */
+int32_t vmp_mfma_order_probe(vmp_ctx *ctx, int32_t form, int32_t ntiles, const double *A,
+                             const double *B, const double *C, double *D);
 /* Gram form: the messages to W of the latest latent pass, S = [G A^T ; A G A^T] in the state block
  * (dot.py:581 collapsed onto the Gram matrix), are formed lazily -- by the fused tau / alpha / bound
  * kernel when it comes next, else by this call, which every other entry point that reads S makes

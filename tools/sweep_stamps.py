@@ -21,6 +21,9 @@ and alpha are ready: the three boundaries behind 'tail: block sums done' are sta
 the stamped build runs at "pca_sweep_stamps" = 2, where the side wavefront -- which forms the bound, the
 ring slot and the stop word beside the head's first inverse -- stamps too.  Its two boundaries are
 printed since kernel entry, with whether the side work ends before 'head: inverse 1 done'.
+--mfma 0 ("pca_sweep_mfma" = 0, with all of the above on) runs the chains of 'Syx done' and 'tail: Pxx
+formed' as scalar fused multiply-adds instead of on the matrix cores.  The last column is the least and
+the greatest length of each phase over the launches.
 """
 import argparse
 import os
@@ -46,6 +49,7 @@ def main():
     ap.add_argument('--wide', type=int, default=1)
     ap.add_argument('--local', type=int, default=1)
     ap.add_argument('--defer', type=int, default=1)
+    ap.add_argument('--mfma', type=int, default=1)
     ap.add_argument('--D', type=int, default=128)
     ap.add_argument('--K', type=int, default=32)
     ap.add_argument('--N', type=int, default=4096)
@@ -59,6 +63,8 @@ def main():
     rt.check(rt.lib.vmp_tune_set(b'pca_sweep_local_pxx', a.local))
     defer = 1 if (a.wide and a.local and a.defer) else 0
     rt.check(rt.lib.vmp_tune_set(b'pca_sweep_defer', defer))
+    mfma = 1 if (defer and a.mfma) else 0
+    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_mfma', mfma))
     rt.check(rt.lib.vmp_tune_set(b'pca_sweep_stamps', 2 if defer else 1))
     rng = np.random.default_rng(0)
     y = rng.standard_normal((a.D, a.K)) @ rng.standard_normal((a.K, a.N)) \
@@ -84,10 +90,10 @@ def main():
         rows.append(r[:, :len(NAMES) + len(SIDE)].astype(np.int64))
     t = np.concatenate(rows[1:])                       # (the first chunk warms up)
     print('pca_sweep_mid_kernel stamps: D=%d K=%d N=%d, pca_sweep_wide=%d, pca_sweep_local_pxx=%d, '
-          'pca_sweep_defer=%d, %d launches' % (a.D, a.K, a.N, a.wide, a.local if a.wide else 0, defer,
-                                               t.shape[0]))
+          'pca_sweep_defer=%d, pca_sweep_mfma=%d, %d launches'
+          % (a.D, a.K, a.N, a.wide, a.local if a.wide else 0, defer, mfma, t.shape[0]))
     print('wall_clock64 at a constant 100 MHz: 1 tick = 0.01 us; medians over the launches')
-    print('%-28s %10s %12s' % ('boundary', 'phase_us', 'since_entry'))
+    print('%-28s %10s %12s %14s' % ('boundary', 'phase_us', 'since_entry', 'phase min-max'))
     prev = t[:, 0]
     ix = {name: i for i, name in enumerate(NAMES)}
     for i, name in enumerate(NAMES):
@@ -95,15 +101,18 @@ def main():
         if not have.all():
             print('%-28s %10s %12s' % (name, '-', '-'))
             continue
-        print('%-28s %10.2f %12.2f' % (name, np.median(t[:, i] - prev) * TICK_US,
-                                       np.median(t[:, i] - t[:, 0]) * TICK_US))
+        print('%-28s %10.2f %12.2f %7.2f-%.2f' % (name, np.median(t[:, i] - prev) * TICK_US,
+                                                  np.median(t[:, i] - t[:, 0]) * TICK_US,
+                                                  (t[:, i] - prev).min() * TICK_US,
+                                                  (t[:, i] - prev).max() * TICK_US))
         prev = t[:, i]
     print('phase A (entry -> ticket) %.2f | tail (acquire -> ring) %.2f | head (ring -> A stored) %.2f us'
           % tuple(np.median(x) * TICK_US for x in
                   (t[:, ix['ticket drawn']] - t[:, 0],
                    t[:, ix['tail: ring written']] - t[:, ix['acquire done']],
                    t[:, ix['head: A stored']] - t[:, ix['tail: ring written']])))
-    print('entry -> A stored %.2f us' % (np.median(t[:, ix['head: A stored']] - t[:, 0]) * TICK_US))
+    total = (t[:, ix['head: A stored']] - t[:, 0]) * TICK_US
+    print('entry -> A stored %.2f us (min %.2f, max %.2f)' % (np.median(total), total.min(), total.max()))
     if defer:
         inv1 = t[:, ix['head: inverse 1 done']]
         for i, name in enumerate(SIDE):
