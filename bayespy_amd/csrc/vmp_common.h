@@ -65,7 +65,7 @@ struct vmp_ctx {
     unsigned long long *sweep_stamps;
     int sweep_stamp_rows;
     // values of the special functions that do not change from sweep to sweep (VMP_SWEEP_SF_*), read
-    // by the deferred side work of pca_sweep_mid_kernel ("pca_sweep_defer"), and the host copy of the
+    // by the side wavefront of pca_sweep_mid_kernel, and the host copy of the
     // inputs they were computed from: a0t, b0t, a0a, b0a, D, n_total, x_prec (sweep_sf_valid: any)
     double *sweep_sf;
     double sweep_sf_key[7];
@@ -128,14 +128,12 @@ int32_t vmp_pca_launch_sweep_tail(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_
 
 // sweeps 1 .. n-1 of a chunk: Gram statistics, tail and the next sweep's head in ONE launch of DP / 8
 // workgroups (pca_sweep_mid_kernel, vmp_pca_small.hip); `ticket` is the sweep's own zeroed word, which
-// the launch leaves zero again; `wide` = 1 selects the wide tail and head of phase B, 2 those and sum
-// <x><x>^T formed by the tail ("pca_sweep_local_pxx"), 3 those and the bound deferred to the first
-// inverse of the head ("pca_sweep_defer"; vmp_pca_sweep_constants first), 4 those and the chains of
-// sum y<x>^T and sum <x><x>^T on the matrix cores ("pca_sweep_mfma"); `stamps` (null: none) the
-// stamped build and its row, `stamp_level` the value of "pca_sweep_stamps"
+// the launch leaves zero again.  The bound, the ring slot and the stop rule run beside the first
+// inverse of the head and read vmp_ctx::sweep_sf: vmp_pca_sweep_constants first.  `stamps` (null:
+// none) the stamped build and its row, `stamp_level` the value of "pca_sweep_stamps"
 int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                                  double a0t, double b0t, double a0a, double b0a, double *state,
-                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket, int32_t wide,
+                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket,
                                  unsigned long long *stamps, int32_t stamp_level);
 // makes vmp_ctx::sweep_sf hold the values for these arguments: a one-wavefront launch on the stream
 // when they differ from the ones it holds (the first call, another plan, changed priors or plates)
@@ -145,10 +143,8 @@ int32_t vmp_pca_sweep_constants(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_to
 int32_t vmp_pca_launch_sweep_head_wide(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total,
                                        double x_prec, double a0t, double b0t, double a0a, double b0a,
                                        double *state);
-// the Gram statistics of that kernel alone: Syx rows into the state, DP / 8 partial blocks into P
-// (`wide` 0: the narrow body, 1: the wide body, 2: the wide body with Syx on the matrix cores)
-int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P,
-                                 int32_t wide);
+// phase A of that kernel alone: the Syx rows into the state, nothing else
+int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state);
 
 // forms the pending S = [G A^T; A G A^T] of the Gram-form PCA block, if any (vmp_pca.hip)
 int32_t vmp_pca_ensure_gram(vmp_ctx *ctx);

@@ -1342,33 +1342,17 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
     // with the mid kernel's LDS would not be placed -- the pass, the Gram statistics and the tail:
     // n + 2 launches instead of 3 n.  "pca_sweep_ticket" = 0 (VMP_PCA_SWEEP_TICKET=0): three per sweep;
     // so does a state block that is not 16-byte aligned (the mid kernel loads it 16 bytes at a time).
-    // "pca_sweep_wide" = 0 (VMP_PCA_SWEEP_WIDE=0): phase B of the mid kernel runs the tail and head
-    // bodies of the three-launch sweep instead of the wide ones (the same bits).  "pca_sweep_stamps" = 1:
-    // the stamped build of the mid kernel, a measurement (tools/sweep_stamps.py).
+    // The two sweeps leave the same bits: the three-launch one is scalar code of its own and the
+    // reference the mid kernel is tested against.  "pca_sweep_stamps" = 1: the stamped build of the mid
+    // kernel, a measurement (tools/sweep_stamps.py).
     const bool ticket = n > 1 && ((uintptr_t)state % 16) == 0 &&
                         vmp_tune_get("pca_sweep_ticket", env_int("VMP_PCA_SWEEP_TICKET", 1, 0, 1));
-    // "pca_sweep_local_pxx" = 0 (VMP_PCA_SWEEP_LOCAL_PXX=0), with the wide bodies: phase A stores its
-    // partial block of sum <x><x>^T and the tail adds the blocks, instead of the tail forming the sum
-    // from the A and the Syx rows it holds in LDS (the same bits).
-    int wide = vmp_tune_get("pca_sweep_wide", env_int("VMP_PCA_SWEEP_WIDE", 1, 0, 1)) ? 1 : 0;
-    if (wide && vmp_tune_get("pca_sweep_local_pxx", env_int("VMP_PCA_SWEEP_LOCAL_PXX", 1, 0, 1)))
-        wide = 2;
-    // "pca_sweep_defer" = 0 (VMP_PCA_SWEEP_DEFER=0), with both of the above: the tail computes <log tau>,
-    // <log alpha>, the bound, the ring slot and the stop rule before it hands over to the head, instead
-    // of one wavefront doing so beside the head's first inverse, and every special function anew each
-    // sweep instead of reading the sweep-invariant ones from ctx->sweep_sf (the same bits)
-    if (wide == 2 && vmp_tune_get("pca_sweep_defer", env_int("VMP_PCA_SWEEP_DEFER", 1, 0, 1)))
-        wide = 3;
-    // "pca_sweep_mfma" = 0 (VMP_PCA_SWEEP_MFMA=0), with all of the above: the chains of sum y<x>^T in
-    // phase A and of sum <x><x>^T in the tail are scalar fused multiply-adds fed from LDS instead of
-    // running on the matrix cores (the same bits: the fp64 matrix instructions add their products in
-    // ascending order of the k-slots, fused; tests/test_mfma_order_gpu.py)
-    const bool mfma = wide == 3 && vmp_tune_get("pca_sweep_mfma", env_int("VMP_PCA_SWEEP_MFMA", 1, 0, 1));
-    if (ticket && wide == 3) {
+    if (ticket) {
+        // the sweep-invariant special functions the side wavefront of the mid kernel reads
         rc = vmp_pca_sweep_constants(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha, b0_alpha);
         if (rc != VMP_OK) return rc;
     }
-    // "pca_sweep_stamps" = 2: the side wavefront of the deferred form stamps too
+    // "pca_sweep_stamps" = 2: the side wavefront stamps too
     const int stamp_level = ticket ? vmp_tune_get("pca_sweep_stamps", 0) : 0;
     const bool stamps = stamp_level != 0;
     if (stamps) {
@@ -1393,7 +1377,7 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
     // an earlier call in flight either it has the GPU to itself and takes the wide body (its LDS
     // would not be placed beside a running pass); otherwise pca_head_fast_kernel.
     // (a held pass is a description, not a launch; both heads leave the same bits)
-    bool head_wide = ticket && wide;
+    bool head_wide = ticket;
     if (head_wide && ctx->x_pending) {
         head_wide = hipEventQuery(ctx->ev_xdone) == hipSuccess;
         (void)hipGetLastError();        // ("not ready" is an answer, not an error of this call)
@@ -1425,7 +1409,7 @@ int32_t vmp_pca_sweeps(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, doub
         if (ticket && !last) {
             // Gram statistics, tail and the head of sweep i + 1 in one launch
             rc = vmp_pca_launch_sweep_mid(ctx, D, K, n_total, x_prec, a0_tau, b0_tau, a0_alpha,
-                                          b0_alpha, state, P, t, ctx->sweep_tickets + i, mfma ? 4 : wide,
+                                          b0_alpha, state, P, t, ctx->sweep_tickets + i,
                                           stamps ? ctx->sweep_stamps + (size_t)i * VMP_SWEEP_NSTAMP
                                                  : nullptr, stamp_level);
             if (rc != VMP_OK) return rc;
@@ -1491,8 +1475,8 @@ int32_t vmp_pca_gram_stats_form(vmp_ctx *ctx, int32_t D, int32_t K, double *stat
     VMP_REQUIRE(ctx, rc == VMP_OK, rc, "unsupported dims D=%d K=%d", D, K);
     double *P = reinterpret_cast<double *>(workspace);
     if (form == 0) return run_gram_stats(ctx, L, D, K, state, P, ctx->stream, nullptr, false);
-    VMP_REQUIRE(ctx, form >= 1 && form <= 3, VMP_ERR_INVALID, "form %d (0, 1, 2 or 3)", form);
-    return vmp_pca_launch_gram_fast(ctx, D, K, state, P, form - 1);
+    VMP_REQUIRE(ctx, form == 1, VMP_ERR_INVALID, "form %d (0 or 1)", form);
+    return vmp_pca_launch_gram_fast(ctx, D, K, state);
 }
 
 int32_t vmp_pca_last_pass_ms(vmp_ctx *ctx, double *ms_pass, double *ms_reduce)

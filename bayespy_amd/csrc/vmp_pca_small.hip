@@ -172,7 +172,7 @@ __device__ __forceinline__ void sweep_inverse(double *M, int n, double *logdet, 
 enum { SP_ENTRY = 0, SP_LDS_FILLED, SP_SYX, SP_PXX, SP_TICKET, SP_ACQUIRE,
        SP_T_PARTIALS, SP_T_LOADS, SP_T_PXX, SP_T_BLOCKSUMS, SP_T_TAU_ALPHA, SP_T_BOUND, SP_T_RING,
        SP_H_LAMBDA, SP_H_INV1, SP_H_W, SP_H_SWW, SP_H_INV2, SP_H_A, SP_COUNT,
-       // "pca_sweep_stamps" = 2, the deferred form: where the side wavefront stands (free words of the row)
+       // "pca_sweep_stamps" = 2: where the side wavefront stands (free words of the row)
        SP_S_STATE = SP_COUNT, SP_S_RING, SP_COUNT2 };
 static_assert(SP_COUNT2 <= VMP_SWEEP_NSTAMP, "stamp row length");
 struct stamps_off {
@@ -563,23 +563,16 @@ __device__ __forceinline__ v4f64 wave_tile_mma_acc(v4f64 acc, const double *As, 
 // back from global memory for the last product instead of waiting in registers, the inverses are
 // inlined (no call, no scratch) and the file is compiled with the VGPR form of the MFMAs (Makefile):
 // 25.6 KB, 96 VGPRs, no AGPRs, no scratch.
-//
-// The body is shared with pca_sweep_mid_kernel below, where the tail of the previous sweep has just
-// run in the same workgroup: HANDOFF = what that tail holds in LDS -- Cov_X in M, sum <x><x>^T in T,
-// <alpha> in alm and <tau> in tau_in, the very values it stored to the state -- is not loaded again.
-template <int KP, bool HANDOFF, class STAMP = stamps_off>
-__device__ __forceinline__ void pca_head_body(const small_args &a, double *st, double *Mh, double *Th,
-                                              double *almh, double tau_in, const STAMP &stamp = STAMP())
+template <int KP>
+__device__ __forceinline__ void pca_head_body(const small_args &a, double *st)
 {
     constexpr int LDM = KP + 1, E = KP * KP / NTF, RB = 32;
-    constexpr int OWN = HANDOFF ? 1 : KP * LDM;
-    __shared__ double Mo[OWN];              // Lambda_W -> Cov_W -> Lambda_X -> Cov_X
-    __shared__ double To[OWN];              // sum <x x^T> (shard sum) -> Sww
+    __shared__ double M[KP * LDM];          // Lambda_W -> Cov_W -> Lambda_X -> Cov_X
+    __shared__ double T[KP * LDM];          // sum <x x^T> (shard sum) -> Sww
     __shared__ double SWb[RB * LDM];        // one row block: Syx rows -> <W> rows
-    __shared__ double almo[HANDOFF ? 1 : KP];
+    __shared__ double alm[KP];
     __shared__ double logdet;
     __shared__ int bad;
-    double *M = HANDOFF ? Mh : Mo, *T = HANDOFF ? Th : To, *alm = HANDOFF ? almh : almo;
     constexpr int KT = KP / 16;
     constexpr int NB = FAST_D / RB;               // row blocks
     constexpr int NLB = RB * KP / NTF;            // loads per thread and row block
@@ -594,8 +587,8 @@ __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, d
     __builtin_amdgcn_s_setprio(3);   // latency-critical: win issue arbitration on a shared CU
     if (tid == 0) bad = 0;
     // ---- one batch of loads ------------------------------------------------------------
-    const double tau = HANDOFF ? tau_in : st[L.off_tau + 2];
-    if constexpr (!HANDOFF) {
+    const double tau = st[L.off_tau + 2];
+    {
         double cx[E], sx[E];
 #pragma unroll
         for (int m = 0; m < E; ++m) {
@@ -635,11 +628,9 @@ __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, d
             M[(e / KP) * LDM + (e % KP)] = lam[m];
         }
     }
-    stamp(SP_H_LAMBDA);
     asm volatile("" : "+v"(tid));     // nothing derived from the thread index stays live across the sweep
     sweep_inverse<KP>(M, K, &logdet, &bad);
     asm volatile("" : "+v"(tid));
-    stamp(SP_H_INV1);
 #pragma unroll
     for (int m = 0; m < E; ++m) {
         const int e = tid + m * NTF;
@@ -721,7 +712,6 @@ __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, d
         }
     }
     __syncthreads();
-    stamp(SP_H_SWW);     // (W and Sww share the row-block loop of this body: no stamp between them)
     // ---- X, replicated half: Lambda_X = x_prec I + <tau> Sww ; A = <tau> Cov_X W^T --------
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -737,7 +727,6 @@ __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, d
     asm volatile("" : "+v"(tid));
     sweep_inverse<KP>(M, K, &logdet, &bad);
     asm volatile("" : "+v"(tid));
-    stamp(SP_H_INV2);
     w = tid >> 6, l15 = tid & 15, l4 = (tid & 63) >> 4;
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -787,8 +776,6 @@ __device__ __forceinline__ void pca_head_body(const small_args &a, double *st, d
         st[L.off_scal + 1] = logdet;
         if (bad) st[L.off_scal + 3] = (double)VMP_ERR_NOT_POSDEF;
     }
-    stamp.drain();
-    stamp(SP_H_A);
 }
 
 template <int KP>
@@ -797,7 +784,7 @@ pca_head_fast_kernel(small_args a, double *st, const double *stop)
 {
     // batched sweeps (vmp_pca_sweeps): an earlier sweep of the batch has stopped the loop
     if (stop && stop[VMP_SWEEP_STOP] != 0.0) return;
-    pca_head_body<KP, false>(a, st, nullptr, nullptr, nullptr, 0.0);
+    pca_head_body<KP>(a, st);
 }
 
 // (tau.update(), alpha.update(), lower bound)
@@ -827,36 +814,17 @@ struct alignas(16) tail_lds {
 };
 // (a multiple of 16 bytes: the dynamic LDS behind it is accessed 16 bytes at a time)
 static_assert(sizeof(tail_lds<16>) % 16 == 0 && sizeof(tail_lds<32>) % 16 == 0, "tail_lds size");
-// WIDE (pca_sweep_mid_kernel only, where no plate pass shares the CU and the register budget of the
-// placement does not bind): every load of the tail is issued before the partial blocks are added, and
-// the rows of sum y<x>^T go on to the next head in SW (FAST_D x (KP+1) doubles of LDS, columns >= K and
-// rows >= D zero) instead of being loaded a second time there.  Same expressions, same order of sums.
-// LOCAL ("pca_sweep_local_pxx", a wide tail): no partial blocks were stored.  sum <x><x>^T is formed
-// here from the rows of sum y<x>^T in SW and from the A that phase A of this workgroup left in LDS
-// (AL, KP rows DP + 2 doubles apart) -- every group's partial by the chain of gram_phase_a_wide, the
-// partials added in the order of the loop below.  The stop word is not read a second time: the
-// launch read it at entry, and no workgroup of a launch writes it before the tail of that launch.
-// DEFER ("pca_sweep_defer", a local wide tail): the tail ends with what the next head reads -- resid,
-// tau's a, b and mean, the status condition on b, alpha's a, b and mean -- and leaves <log tau>,
-// <log alpha>, the bound, the ring slot and the stop rule to defer_side below, which one wavefront
-// runs beside the head's first inverse.  resid and trx wait in red[0] and red[1].
-template <int KP, int MODE, bool WIDE = false, class STAMP = stamps_off, bool LOCAL = false,
-          bool DEFER = false, bool MFMA = false>
+template <int KP, int MODE>
 __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, const vmp_sweep_tail *sw,
-                                              tail_lds<KP> &s, double *SW = nullptr,
-                                              const STAMP &stamp = STAMP(), const double *AL = nullptr)
+                                              tail_lds<KP> &s)
 {
-    static_assert(!WIDE || MODE == TAIL_SWEEP, "the wide tail is a sweep tail");
-    static_assert(!LOCAL || WIDE, "sum <x><x>^T is formed locally by the wide tail only");
-    static_assert(!DEFER || LOCAL, "the bound is deferred behind the local wide tail only");
-    static_assert(!MFMA || LOCAL, "sum <x><x>^T runs on the matrix cores in its local form only");
     constexpr bool GRAM = (MODE == TAIL_GRAM);
     constexpr int LDM = KP + 1, E = KP * KP / NTF;
     extern __shared__ __align__(16) double gl[];          // GRAM: A (KP x (DP+1)) | G batch (GB x (DP+1)) | S batch (GB x LDM)
     double *Sw = s.Sw, *Cx = s.Cx, *Sx = s.Sx, *al = s.al, *sc = s.sc, *red = s.red;
     const lay32 L(a.L);
     const int tid = threadIdx.x, D = a.D, K = a.K;
-    if constexpr (MODE == TAIL_SWEEP && !LOCAL) {
+    if constexpr (MODE == TAIL_SWEEP) {
         if (!sw->first && sw->ctl[VMP_SWEEP_STOP] != 0.0) {
             if (tid == 0) {
                 sw->slot[7] = 0.0;                     // not executed
@@ -870,58 +838,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
     double sxx[E];
 #pragma unroll
     for (int m = 0; m < E; ++m) sxx[m] = 0.0;
-    // WIDE: <W>, sum y<x>^T, Sww and Cov_X are requested here, ahead of the partial blocks
-    constexpr int NW = WIDE ? FAST_D * KP / NTF : 1;
-    double ww[NW], wy[NW], es0[WIDE ? E : 1], es1[WIDE ? E : 1];
-    if constexpr (WIDE) {
-        const int n = D * KP;
-#pragma unroll
-        for (int j = 0; j < NW; ++j) {
-            const int e = tid + j * NTF;
-            ww[j] = e < n ? st[L.off_W + e] : 0.0;
-            wy[j] = e < n ? st[L.off_S + e] : 0.0;
-        }
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            const int e = tid + m * NTF;
-            const int i = e / KP, j = e % KP;
-            const bool in = (i < K && j < K);
-            es0[m] = in ? st[L.off_Sww + i * KP + j] : 0.0;
-            es1[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
-        }
-    }
-    if constexpr (LOCAL) {
-        // (formed below, once the rows of sum y<x>^T are in SW)
-    } else if constexpr (WIDE) {
-        // sum <x><x>^T = sum_b P[b]: the adds of the loop below in the same order, from ONE batch of
-        // loads (nb <= FAST_D / 8) -- that loop waits for four loads at a time, nb / 4 round trips
-        // in a row for each of the E elements of a thread
-        constexpr int NBM = FAST_D / 8;
-        const int nb = sw->nb, nb4 = nb & ~3;
-        double pv[E][NBM];
-#pragma unroll
-        for (int m = 0; m < E; ++m)
-#pragma unroll
-            for (int b = 0; b < NBM; ++b)
-                pv[m][b] = b < nb ? sw->P[tid + m * NTF + b * (KP * KP)] : 0.0;
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll
-            for (int b = 0; b < NBM; b += 4)
-                if (b < nb4) {
-                    s0 += pv[m][b];
-                    s1 += pv[m][b + 1];
-                    s2 += pv[m][b + 2];
-                    s3 += pv[m][b + 3];
-                }
-#pragma unroll
-            for (int b = 0; b < NBM; ++b)
-                if (b >= nb4 && b < nb) s0 += pv[m][b];
-            sxx[m] = (s0 + s1) + (s2 + s3);
-            st[L.off_S + L.DP * KP + tid + m * NTF] = sxx[m];
-        }
-    } else if constexpr (MODE == TAIL_SWEEP) {
+    if constexpr (MODE == TAIL_SWEEP) {
         // sum <x><x>^T = sum_b P[b] in the order of reduce_partials_kernel (vmp_pca.hip): the same bits
         const int nb = sw->nb;
 #pragma unroll
@@ -941,7 +858,6 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             st[L.off_S + L.DP * KP + e] = sxx[m];
         }
     }
-    if constexpr (!LOCAL) stamp(SP_T_PARTIALS);
     if constexpr (GRAM) {
         const int DP = L.DP, LA = DP + 1;
         double *As = gl, *Gs = As + KP * LA, *Ss = Gs + GB * LA;
@@ -1001,13 +917,8 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             const int e = tid + m * NTF;
             const int i = e / KP, j = e % KP;
             const bool in = (i < K && j < K);
-            if constexpr (WIDE) {
-                v0[m] = es0[m];
-                v1[m] = es1[m];
-            } else {
-                v0[m] = in ? st[L.off_Sww + i * KP + j] : 0.0;
-                v1[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
-            }
+            v0[m] = in ? st[L.off_Sww + i * KP + j] : 0.0;
+            v1[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
             if constexpr (MODE != TAIL_PLAIN) v2[m] = in ? sxx[m] : 0.0;
             else v2[m] = in ? st[L.off_S + (L.DP + i) * KP + j] : 0.0;
         }
@@ -1022,23 +933,11 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             const int i = e / KP, j = e % KP;
             Sw[i * LDM + j] = v0[m];
             Cx[i * LDM + j] = v1[m];
-            if constexpr (!LOCAL) Sx[i * LDM + j] = v2[m];
+            Sx[i * LDM + j] = v2[m];
         }
     }
     // sum(W o Syx): padded entries of W are zero, so the D x KP blocks are walked linearly
-    if constexpr (WIDE) {
-        // the same products in the same order as the loop below, which runs whole passes of 8 per
-        // thread; the rows go to SW as the head would have loaded them (zero beyond D and K)
-        const int n = D * KP, jn = (n + 8 * NTF - 1) / (8 * NTF) * 8;
-        // (LOCAL: all DP rows, which the sum over the DP / 8 groups below walks)
-        const int nsw = LOCAL ? L.DP * KP : (D + 31) / 32 * 32 * KP;   // whole 32-row blocks, at most DP rows
-#pragma unroll
-        for (int j = 0; j < NW; ++j) {
-            const int e = tid + j * NTF;
-            if (j < jn) t1 += ww[j] * wy[j];
-            if (e < nsw) SW[(e / KP) * LDM + (e % KP)] = (e < n && e % KP < K) ? wy[j] : 0.0;
-        }
-    } else if constexpr (!GRAM) {
+    if constexpr (!GRAM) {
         const int n = D * KP;
 #pragma unroll 1
         for (int e0 = 0; e0 < n; e0 += 8 * NTF) {
@@ -1053,131 +952,7 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             for (int m = 0; m < 8; ++m) t1 += w[m] * y[m];
         }
     }
-    (void)ww; (void)wy; (void)es0; (void)es1;
     __syncthreads();
-    stamp(SP_T_LOADS);
-    if constexpr (LOCAL && MFMA) {
-        // The local form below on v_mfma_f64_16x16x4_f64 ("pca_sweep_mfma"): a wavefront owns a 16 x 16
-        // tile of outputs, a group's partial is two instructions from zero -- rows 0..3 of the group
-        // in the four k-slots, then rows 4..7, C carried -- and the instruction adds its four products
-        // to C as a chain of fused multiply-adds in ascending slot order (tests/test_mfma_order_gpu.py):
-        // the chain of 8 of the scalar form.  The partials are added as there.  Lane l: A operand
-        // A[16 ti + l % 16][8 b + 4 h + l / 16], B operand Syx[8 b + 4 h + l / 16][16 tj + l % 16],
-        // results (16 ti + l / 16 + 4 reg, 16 tj + l % 16).
-        constexpr int KT = KP / 16;
-        const int LA = L.DP + 2;
-        const int w = tid >> 6, l15 = tid & 15, l4 = (tid & 63) >> 4;
-        const int nb = sw->nb, nb4 = nb & ~3;
-        if (w < KT * KT) {
-            const int ti = w / KT, tj = w % KT;
-            const double *ar = AL + (16 * ti + l15) * LA + l4;
-            const double *sr = SW + l4 * LDM + 16 * tj + l15;
-            const auto group = [&](int b) {
-                v4f64 p = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int h = 0; h < GRA; h += 4)
-                    p = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[b * GRA + h], sr[(b * GRA + h) * LDM], p,
-                                                             0, 0, 0);
-                return p;
-            };
-            v4f64 acc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = v4f64{0.0, 0.0, 0.0, 0.0};
-#pragma unroll 1
-            for (int b = 0; b < nb4; b += 4) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] += group(b + q);
-            }
-#pragma unroll 1
-            for (int b = nb4; b < nb; ++b) acc[0] += group(b);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int k = 16 * ti + l4 + 4 * r, k2 = 16 * tj + l15;
-                const bool in = (k < K && k2 < K);
-                const double x = in ? (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]) : 0.0;
-                st[L.off_S + (L.DP + k) * KP + k2] = x;
-                Sx[k * LDM + k2] = x;
-            }
-        }
-        __syncthreads();
-        stamp(SP_T_PXX);
-    } else if constexpr (LOCAL) {
-        // sum <x><x>^T [k][k'] = sum_b Pxx_b[k][k'], Pxx_b[k][k'] = sum_{r in group b} A[k][r] Syx[r][k']:
-        // each partial its own chain of multiply-adds from zero over the 8 rows in ascending order
-        // (gram_phase_a_wide), the partials added four at a time as above (reduce_partials_kernel).
-        // A thread owns the outputs (ki + 16 i, ji + 16 j): at KP = 32 four multiply-adds share two
-        // 16-byte reads of A (4 rows per wavefront, 4 banks apart) and two reads of a row of SW.
-        constexpr int B = KP / 16;
-        const int LA = L.DP + 2;
-        const int ki = tid >> 4, ji = tid & 15;
-        const int nb = sw->nb, nb4 = nb & ~3;
-        const double *ar = AL + ki * LA, *sr = SW + ji;
-        double acc[4][B][B];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int i = 0; i < B; ++i)
-#pragma unroll
-                for (int j = 0; j < B; ++j) acc[q][i][j] = 0.0;
-        const auto group = [&](int b, double (&p)[B][B]) {
-#pragma unroll
-            for (int i = 0; i < B; ++i)
-#pragma unroll
-                for (int j = 0; j < B; ++j) p[i][j] = 0.0;
-#pragma unroll
-            for (int r = 0; r < GRA; r += 2) {
-                v2f64 x[B];
-                double y0[B], y1[B];
-#pragma unroll
-                for (int i = 0; i < B; ++i)
-                    x[i] = *reinterpret_cast<const v2f64 *>(ar + 16 * i * LA + b * GRA + r);
-#pragma unroll
-                for (int j = 0; j < B; ++j) {
-                    y0[j] = sr[(b * GRA + r) * LDM + 16 * j];
-                    y1[j] = sr[(b * GRA + r + 1) * LDM + 16 * j];
-                }
-#pragma unroll
-                for (int i = 0; i < B; ++i)
-#pragma unroll
-                    for (int j = 0; j < B; ++j) {
-                        p[i][j] = __builtin_fma(x[i][0], y0[j], p[i][j]);
-                        p[i][j] = __builtin_fma(x[i][1], y1[j], p[i][j]);
-                    }
-            }
-        };
-        double p[B][B];
-#pragma unroll 1
-        for (int b = 0; b < nb4; b += 4) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                group(b + q, p);
-#pragma unroll
-                for (int i = 0; i < B; ++i)
-#pragma unroll
-                    for (int j = 0; j < B; ++j) acc[q][i][j] += p[i][j];
-            }
-        }
-#pragma unroll 1
-        for (int b = nb4; b < nb; ++b) {
-            group(b, p);
-#pragma unroll
-            for (int i = 0; i < B; ++i)
-#pragma unroll
-                for (int j = 0; j < B; ++j) acc[0][i][j] += p[i][j];
-        }
-#pragma unroll
-        for (int i = 0; i < B; ++i)
-#pragma unroll
-            for (int j = 0; j < B; ++j) {
-                const int k = ki + 16 * i, k2 = ji + 16 * j;
-                const bool in = (k < K && k2 < K);
-                const double x = in ? (acc[0][i][j] + acc[1][i][j]) + (acc[2][i][j] + acc[3][i][j]) : 0.0;
-                st[L.off_S + (L.DP + k) * KP + k2] = x;
-                Sx[k * LDM + k2] = x;
-            }
-        __syncthreads();
-        stamp(SP_T_PXX);
-    }
     double t2 = 0.0, trx = 0.0;
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -1187,69 +962,11 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
         t2 += Sw[i * LDM + j] * sxx;
         if (i == j) trx += sxx;
     }
-    if constexpr (DEFER) {
-        // the three block_sums behind one barrier: the wave sums go to twelve words of their own (the
-        // <log alpha> quarter of al, which the deferred form does not use and nothing has touched
-        // since the barrier above) and every thread adds each four in the order of block_sum
-        double *r3 = al + 3 * KP;
-        static_assert(KP >= 3 * (NTF / 64), "twelve words");
-        t1 = wave_sum(t1);
-        t2 = wave_sum(t2);
-        trx = wave_sum(trx);
-        if ((tid & 63) == 0) {
-            r3[tid >> 6] = t1;
-            r3[NTF / 64 + (tid >> 6)] = t2;
-            r3[2 * (NTF / 64) + (tid >> 6)] = trx;
-        }
-        __syncthreads();
-        t1 = t2 = trx = 0.0;
-#pragma unroll
-        for (int i = 0; i < NTF / 64; ++i) {
-            t1 += r3[i];
-            t2 += r3[NTF / 64 + i];
-            trx += r3[2 * (NTF / 64) + i];
-        }
-    } else {
-        t1 = block_sum<NTF>(t1, red);
-        t2 = block_sum<NTF>(t2, red);
-        trx = block_sum<NTF>(trx, red);
-    }
-    stamp(SP_T_BLOCKSUMS);
+    t1 = block_sum<NTF>(t1, red);
+    t2 = block_sum<NTF>(t2, red);
+    trx = block_sum<NTF>(trx, red);
     // (dot.py:355 E1 and dot.py:403 E2 collapsed to traces)
     const double resid = sc[4] - 2.0 * t1 + t2;
-    if constexpr (DEFER) {
-        if (tid == 64) {
-            const double ta = a.a0t + 0.5 * (double)D * a.n_total;
-            const double tb = a.b0t + 0.5 * resid;
-            sc[0] = ta;
-            sc[1] = tb;
-            sc[2] = ta / tb;
-            red[0] = resid;
-            red[1] = trx;
-            st[L.off_tau + 0] = ta;
-            st[L.off_tau + 1] = tb;
-            st[L.off_tau + 2] = sc[2];
-            st[L.off_scal + 2] = resid;
-            if (!(tb > 0.0)) st[L.off_scal + 3] = (double)VMP_ERR_FLOATING;
-        }
-        if (tid < K) {
-            const double aa = a.a0a + 0.5 * (double)D;
-            const double ab = a.b0a + 0.5 * Sw[tid * LDM + tid];
-            const double am = aa / ab;
-            al[0 * KP + tid] = aa;
-            al[1 * KP + tid] = ab;
-            al[2 * KP + tid] = am;
-            st[L.off_alpha + 0 * KP + tid] = aa;
-            st[L.off_alpha + 1 * KP + tid] = ab;
-            st[L.off_alpha + 2 * KP + tid] = am;
-        }
-        // the critical path leaves the tail here: the three phases that follow it in the other
-        // forms are the side wavefront's now
-        stamp(SP_T_TAU_ALPHA);
-        stamp(SP_T_BOUND);
-        stamp(SP_T_RING);
-        return;
-    }
     // ---- tau (gamma.py:116-148 with the message gaussian.py:2363-2369), alpha -------------
     if (tid == 64) {
         const double ta = a.a0t + 0.5 * (double)D * a.n_total;
@@ -1293,7 +1010,6 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
     sla = block_sum<NTF>(sla, red);
     saw = block_sum<NTF>(saw, red);
     lal = block_sum<NTF>(lal, red);
-    stamp(SP_T_TAU_ALPHA);
     if (tid == 0) {
         const double tau = sc[2], logtau = sc[3];
         const double Dd = (double)D, Kd = (double)K;
@@ -1309,7 +1025,6 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
         st[L.off_L + 3] = Lt;
         st[L.off_L + 4] = lal;
         st[L.off_L + 5] = LY + LX + LW + Lt + lal;
-        stamp(SP_T_BOUND);
         if constexpr (MODE == TAIL_SWEEP) {
             const double status = sc[7];
             double *slot = sw->slot;
@@ -1336,7 +1051,6 @@ __device__ __forceinline__ void pca_tail_body(const small_args &a, double *st, c
             sw->ctl[VMP_SWEEP_L] = Lb;
             sw->ctl[VMP_SWEEP_EXECUTED] += 1.0;
         }
-        stamp(SP_T_RING);
     }
 }
 
@@ -1359,123 +1073,31 @@ pca_tail_sweep_kernel(small_args a, double *st, vmp_sweep_tail sw)
 // ---------------------------------------------------------------------------
 // One launch per held sweep (vmp_pca_sweeps, sweeps 1 .. n-1 of a chunk).
 //
-// Phase A, every workgroup: the Gram statistics of the sweep for one group of GRA rows of G, what
+// Phase A, every workgroup: the rows of sum y<x>^T of the sweep for one group of GRA rows of G, what
 // pca_gram_stats_kernel (vmp_pca.hip) computes and bit for bit the same -- every output is its own
-// chain of fused multiply-adds over d = 0 .. D-1 (Syx) or over the 8 rows of the group (Pxx), from
-// zero, in ascending order.  What differs is the bookkeeping: LDS is filled with 16-byte loads and
-// shifts instead of a division per element, and a thread owns a 2 x 2 block of (row, column)
-// outputs, so that four multiply-adds share four LDS reads instead of eight.
+// chain of fused multiply-adds over d = 0 .. D-1, from zero, in ascending order.  The partial blocks
+// of sum <x><x>^T that kernel also stores are not formed here: the tail of phase B forms the sum from
+// the A this phase leaves in LDS (sweep_tail_wide).
+// Every load of A and G is requested before the first LDS write; the rows of A are DP + 2 doubles
+// apart, so that they take 16-byte LDS writes; and every thread of the 8 x KP block of Syx owns one
+// output.  The 32 lanes of a half wavefront are 16 columns x 2 rows: 16 rows of A, 4 banks apart, and
+// two broadcast rows of G.
+// The chains run on v_mfma_f64_4x4x4_4b_f64, which adds its four products to C as a chain of fused
+// multiply-adds over the k-slots in ascending order (tests/test_mfma_order_gpu.py) -- so d = 4 q +
+// slot, C carried over q, is the scalar chain of every output bit for bit.  A wavefront owns 4 rows x
+// 16 columns, as four 4 x 4 blocks (lane x + 4 b + 16 s: row x of G and column 4 b + x of the 16, both
+// at d = 4 q + s; its result is row s, column 4 b + x).  Operands at d >= D are zero.
 // ---------------------------------------------------------------------------
-__host__ __device__ inline size_t gram_phase_a_lds(int KP, int DP)
-{
-    return ((size_t)KP * (DP + 1) + (size_t)GRA * DP + (size_t)GRA * (KP + 1)) * sizeof(double);
-}
-
-template <int KP, class STAMP = stamps_off>
-__device__ __forceinline__ void gram_phase_a(const vmp_pca_layout &L, int D, int K, double *st,
-                                             double *P, double *lds, int blk,
-                                             const STAMP &stamp = STAMP())
-{
-    constexpr int LDS_S = KP + 1, H = KP / 2, E = KP * KP / NTF;
-    const int DP = (int)L.DP, LA = DP + 1;
-    const int DP2 = DP >> 1, sh = __builtin_ctz(DP2);       // DP = 32, 64 or 128
-    double *As = lds;                    // KP x LA (rows >= K zero)
-    double *Gs = As + KP * LA;           // GRA x DP
-    double *Ss = Gs + GRA * DP;          // GRA x LDS_S
-    const int tid = threadIdx.x;
-    const int r0 = blk * GRA;
-    const double *A = st + L.off_A;
-    const double *G = st + L.off_G + (int64_t)r0 * DP;
-#pragma unroll 4
-    for (int e = tid; e < KP * DP2; e += NTF) {
-        const int k = e >> sh, c = (e & (DP2 - 1)) * 2;
-        v2f64 v = {0.0, 0.0};
-        if (k < K) v = *reinterpret_cast<const v2f64 *>(A + k * DP + c);
-        As[k * LA + c] = v[0];
-        As[k * LA + c + 1] = v[1];
-    }
-    for (int e = tid; e < GRA * DP2; e += NTF)
-        *reinterpret_cast<v2f64 *>(Gs + 2 * e) = *reinterpret_cast<const v2f64 *>(G + 2 * e);
-    __syncthreads();
-    stamp(SP_LDS_FILLED);
-    // Syx[r][k] = sum_d G[r][d] A[k][d]: rows (ra, ra + 4) x columns (k0, k0 + H) per thread
-    if (tid < 4 * H) {
-        const int k0 = tid % H, ra = tid / H;
-        const double *g0 = Gs + ra * DP, *g1 = Gs + (ra + 4) * DP;
-        const double *a0 = As + k0 * LA, *a1 = As + (k0 + H) * LA;
-        double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;
-#pragma unroll 4
-        for (int d = 0; d < D; ++d) {
-            const double x0 = g0[d], x1 = g1[d], y0 = a0[d], y1 = a1[d];
-            s00 = __builtin_fma(x0, y0, s00);
-            s01 = __builtin_fma(x0, y1, s01);
-            s10 = __builtin_fma(x1, y0, s10);
-            s11 = __builtin_fma(x1, y1, s11);
-        }
-        Ss[ra * LDS_S + k0] = s00;
-        Ss[ra * LDS_S + k0 + H] = s01;
-        Ss[(ra + 4) * LDS_S + k0] = s10;
-        Ss[(ra + 4) * LDS_S + k0 + H] = s11;
-        double *So = st + L.off_S;
-        if (r0 + ra < D) {
-            if (k0 < K) So[(r0 + ra) * KP + k0] = s00;
-            if (k0 + H < K) So[(r0 + ra) * KP + k0 + H] = s01;
-        }
-        if (r0 + ra + 4 < D) {
-            if (k0 < K) So[(r0 + ra + 4) * KP + k0] = s10;
-            if (k0 + H < K) So[(r0 + ra + 4) * KP + k0 + H] = s11;
-        }
-    }
-    __syncthreads();
-    stamp(SP_SYX);
-    // Pxx_b[k][k'] = sum_{r in group} A[k][r] Syx[r][k']  (added up in fixed order by the tail)
-    double *Pb = P + (int64_t)blk * KP * KP;
-#pragma unroll
-    for (int m = 0; m < E; ++m) {
-        const int e = tid + m * NTF;
-        const int k = e / KP, k2 = e % KP;
-        double s = 0.0;
-        if (k < K && k2 < K) {
-#pragma unroll
-            for (int r = 0; r < GRA; ++r) s = __builtin_fma(As[k * LA + r0 + r], Ss[r * LDS_S + k2], s);
-        }
-        Pb[e] = s;
-    }
-}
-
-// phase A alone (tests: bitwise against pca_gram_stats_kernel)
-template <int KP>
-__global__ void __launch_bounds__(NTF)
-pca_gram_fast_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
-{
-    extern __shared__ __align__(16) double gl[];
-    gram_phase_a<KP>(L, D, K, st, P, gl, blockIdx.x);
-}
-
-// Phase A as the one-launch sweep runs it when "pca_sweep_wide" is on: the same outputs by the same
-// chains, scheduled for a launch that has the GPU to itself.  Every load of A and G is requested
-// before the first LDS write (gram_phase_a waits for memory twice at KP = 32, DP = 128); the rows of A
-// are DP + 2 doubles apart, so that they take 16-byte LDS writes; and every thread of the 8 x KP
-// block of Syx owns one output, not 4 H threads a 2 x 2 block each.  The 32 lanes of a half
-// wavefront are 16 columns x 2 rows: 16 rows of A, 4 banks apart, and two broadcast rows of G.
 __host__ __device__ inline size_t gram_phase_a_wide_lds(int KP, int DP)
 {
     return ((size_t)KP * (DP + 2) + (size_t)GRA * DP + (size_t)GRA * (KP + 1)) * sizeof(double);
 }
 
-// PXX = false ("pca_sweep_local_pxx"): the phase ends with the Syx rows; A stays in LDS for the tail
-// MFMA ("pca_sweep_mfma"): the Syx chains run on v_mfma_f64_4x4x4_4b_f64, which adds its four products
-// to C as a chain of fused multiply-adds over the k-slots in ascending order
-// (tests/test_mfma_order_gpu.py) -- so d = 4 q + slot, C carried over q, is the scalar chain of every
-// output bit for bit.  A wavefront owns the same 4 rows x 16 columns as below, as four 4 x 4 blocks
-// (lane x + 4 b + 16 s: row x of G and column 4 b + x of the 16, both at d = 4 q + s; its result is
-// row s, column 4 b + x: the output the scalar form gives this lane).  Operands at d >= D are zero.
-template <int KP, class STAMP = stamps_off, bool PXX = true, bool MFMA = false>
+template <int KP, class STAMP = stamps_off>
 __device__ __forceinline__ void gram_phase_a_wide(const vmp_pca_layout &L, int D, int K, double *st,
-                                                  double *P, double *lds, int blk,
-                                                  const STAMP &stamp = STAMP())
+                                                  double *lds, int blk, const STAMP &stamp = STAMP())
 {
-    constexpr int LDS_S = KP + 1, KT = KP / 16, E = KP * KP / NTF;
+    constexpr int LDS_S = KP + 1, KT = KP / 16;
     constexpr int NA = KP * (FAST_D / 2) / NTF, NG = GRA * (FAST_D / 2) / NTF;
     const int DP = (int)L.DP, LA = DP + 2;
     const int DP2 = DP >> 1, sh = __builtin_ctz(DP2);       // DP = 32, 64 or 128
@@ -1519,73 +1141,53 @@ __device__ __forceinline__ void gram_phase_a_wide(const vmp_pca_layout &L, int D
         if (w < 2 * KT) {
             const int k = (l & 15) + 16 * (w % KT), r = (l >> 4) + 4 * (w / KT);
             double s = 0.0;
-            if constexpr (MFMA) {
-                // (r - l / 16 is the first of the wavefront's 4 rows, l / 16 this lane's k-slot)
-                const int sl = l >> 4;
-                const double *gx = Gs + (r - sl + (l & 3)) * DP + sl, *ax = As + k * LA + sl;
-                const int D4 = D & ~3;
-                int d = 0;
-                // eight k-steps at a time, their sixteen LDS reads requested before the first is used
-                for (; d + 32 <= D4; d += 32) {
-                    double gq[8], aq[8];
+            // (r - l / 16 is the first of the wavefront's 4 rows, l / 16 this lane's k-slot)
+            const int sl = l >> 4;
+            const double *gx = Gs + (r - sl + (l & 3)) * DP + sl, *ax = As + k * LA + sl;
+            const int D4 = D & ~3;
+            int d = 0;
+            // eight k-steps at a time, their sixteen LDS reads requested before the first is used
+            for (; d + 32 <= D4; d += 32) {
+                double gq[8], aq[8];
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        gq[q] = gx[d + 4 * q];
-                        aq[q] = ax[d + 4 * q];
-                    }
+                for (int q = 0; q < 8; ++q) {
+                    gq[q] = gx[d + 4 * q];
+                    aq[q] = ax[d + 4 * q];
+                }
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) s = __builtin_amdgcn_mfma_f64_4x4x4f64(gq[q], aq[q], s, 0, 0, 0);
-                }
-                for (; d < D4; d += 4) s = __builtin_amdgcn_mfma_f64_4x4x4f64(gx[d], ax[d], s, 0, 0, 0);
-                // D % 4 != 0: the last step, its k-slots at d >= D zero (read in bounds -- D4 + 3 < DP --
-                // and masked afterwards, not behind a branch)
-                if (D4 < D) {
-                    const double g4 = gx[D4], a4 = ax[D4];
-                    const bool in = D4 + sl < D;
-                    s = __builtin_amdgcn_mfma_f64_4x4x4f64(in ? g4 : 0.0, in ? a4 : 0.0, s, 0, 0, 0);
-                }
-            } else {
-                const double *g = Gs + r * DP, *ar = As + k * LA;
-#pragma unroll 16
-                for (int d = 0; d < D; ++d) s = __builtin_fma(g[d], ar[d], s);
+                for (int q = 0; q < 8; ++q) s = __builtin_amdgcn_mfma_f64_4x4x4f64(gq[q], aq[q], s, 0, 0, 0);
             }
+            for (; d < D4; d += 4) s = __builtin_amdgcn_mfma_f64_4x4x4f64(gx[d], ax[d], s, 0, 0, 0);
+            // D % 4 != 0: the last step, its k-slots at d >= D zero (read in bounds -- D4 + 3 < DP --
+            // and masked afterwards, not behind a branch)
+            if (D4 < D) {
+                const double g4 = gx[D4], a4 = ax[D4];
+                const bool in = D4 + sl < D;
+                s = __builtin_amdgcn_mfma_f64_4x4x4f64(in ? g4 : 0.0, in ? a4 : 0.0, s, 0, 0, 0);
+            }
+            // (the block also goes to Ss, which nothing reads since the partial blocks went: the store
+            // stays so that the mid kernels remain the instruction streams that were measured)
             Ss[r * LDS_S + k] = s;
             if (r0 + r < D && k < K) st[L.off_S + (r0 + r) * KP + k] = s;
         }
     }
     __syncthreads();
     stamp(SP_SYX);
-    if constexpr (PXX) {
-        // Pxx_b[k][k'] = sum_{r in group} A[k][r] Syx[r][k']  (added up in fixed order by the tail)
-        double *Pb = P + (int64_t)blk * KP * KP;
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            const int e = tid + m * NTF;
-            const int k = e / KP, k2 = e % KP;
-            double s = 0.0;
-            if (k < K && k2 < K) {
-#pragma unroll
-                for (int r = 0; r < GRA; ++r)
-                    s = __builtin_fma(As[k * LA + r0 + r], Ss[r * LDS_S + k2], s);
-            }
-            Pb[e] = s;
-        }
-    }
 }
 
-// that phase A alone (tests: bitwise against pca_gram_stats_kernel)
-template <int KP, bool MFMA = false>
+// phase A alone (tests: bitwise against pca_gram_stats_kernel)
+template <int KP>
 __global__ void __launch_bounds__(NTF)
-pca_gram_wide_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
+pca_gram_wide_kernel(vmp_pca_layout L, int D, int K, double *st)
 {
     extern __shared__ __align__(16) double gl[];
-    gram_phase_a_wide<KP, stamps_off, true, MFMA>(L, D, K, st, P, gl, blockIdx.x);
+    gram_phase_a_wide<KP>(L, D, K, st, gl, blockIdx.x);
 }
 
 // Phase B, the workgroup that draws the last ticket: the tail of this sweep and, unless that tail
 // stops the loop, the head of the next one.  The ticket is the counter form of the in-launch
 // reduction: every workgroup drains its stores, lane 0 releases at agent scope and draws; the one
-// that draws nb - 1 knows that every other workgroup's Syx rows and Pxx block are released, acquires
+// that draws nb - 1 knows that every other workgroup's Syx rows are released, acquires
 // once and reads them with plain loads.  A ticket is drawn once and nobody waits for anybody: the
 // other workgroups return, so there is no order of dispatch in which the launch cannot finish.
 // `ticket` is this sweep's own word, zero at the launch: vmp_pca_sweeps clears the words once, when
@@ -1595,20 +1197,205 @@ pca_gram_wide_kernel(vmp_pca_layout L, int D, int K, double *st, double *P)
 // order and each sees the stores of those before it, so it finds 0.  A launch that returns at
 // entry because the loop has stopped draws nothing and leaves the 0 it found.
 // This kernel never runs beside a latent pass (no pass is in flight during held sweeps), so the
-// placement budget of pca_head_fast_kernel does not bind it.
-// The head of the next sweep as phase B runs it when "pca_sweep_wide" is on: pca_head_body without
-// the placement budget.  The D x K operand -- the rows of sum y<x>^T the wide tail left in SW, then
-// the rows of <W> -- stays in LDS whole (whole 32-row blocks of it, as many as pca_head_body walks),
-// so W = tau Syx Cov_W, Sww and A = tau Cov_X W^T are one barrier-delimited phase each and nothing is
-// loaded from global memory.  Per output the MFMA sequence is the one of pca_head_body: over q for a
-// tile of W and A, over the rows in ascending order for a tile of Sww.  Stores are the same.
+// placement budget of pca_head_fast_kernel and pca_tail_sweep_kernel does not bind it.
 //
-// SIDE ("pca_sweep_defer", pca_sweep_mid_kernel only): what runs beside the FIRST inverse, and `stopw`,
-// the LDS word it leaves the stop decision in.  Every thread reads that word behind the inverse's
-// closing barrier and the workgroup returns on a stop before the head has stored anything: Lambda_W
-// and its inverse were computed for nothing, in LDS and registers only.
+// sweep_tail_wide is the tail of phase B: the values of pca_tail_body<KP, TAIL_SWEEP>, bit for bit, by
+// the same expressions and the same order of sums, scheduled for a workgroup that has the CU to itself.
+// Every load is issued at the start.  The rows of sum y<x>^T go on to the next head in SW (DP x (KP+1)
+// doubles of LDS, columns >= K and rows >= D zero) instead of being loaded a second time there.
+// No partial blocks of sum <x><x>^T were stored: the sum is formed here from the rows in SW and from
+// the A that phase A of this workgroup left in LDS (AL, KP rows DP + 2 doubles apart) -- every group's
+// partial a chain of fused multiply-adds from zero over its 8 rows in ascending order
+// (pca_gram_stats_kernel), the partials added four at a time in the order of reduce_partials_kernel.
+// The stop word is not read here: the launch read it at entry, and no workgroup of a launch writes it
+// before the tail of that launch.
+// The tail ends with what the next head reads -- resid, tau's a, b and mean, the status condition on
+// b, alpha's a, b and mean -- and leaves <log tau>, <log alpha>, the bound, the ring slot and the stop
+// rule to defer_side below, which one wavefront runs beside the head's first inverse.  resid and trx
+// wait in red[0] and red[1].
+template <int KP, class STAMP>
+__device__ __forceinline__ void sweep_tail_wide(const small_args &a, double *st, const vmp_sweep_tail &sw,
+                                                tail_lds<KP> &s, double *SW, const double *AL,
+                                                const STAMP &stamp)
+{
+    constexpr int LDM = KP + 1, E = KP * KP / NTF, NW = FAST_D * KP / NTF;
+    double *Sw = s.Sw, *Cx = s.Cx, *Sx = s.Sx, *al = s.al, *sc = s.sc, *red = s.red;
+    const lay32 L(a.L);
+    const int tid = threadIdx.x, D = a.D, K = a.K;
+    __builtin_amdgcn_s_setprio(3);   // latency-critical: win issue arbitration on a shared CU
+    double t1 = 0.0;
+    // ---- one batch of loads: <W>, sum y<x>^T, Sww, Cov_X and the scalars ------------------
+    double ww[NW], wy[NW], es0[E], es1[E];
+    {
+        const int n = D * KP;
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            const int e = tid + j * NTF;
+            ww[j] = e < n ? st[L.off_W + e] : 0.0;
+            wy[j] = e < n ? st[L.off_S + e] : 0.0;
+        }
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            const int e = tid + m * NTF;
+            const int i = e / KP, j = e % KP;
+            const bool in = (i < K && j < K);
+            es0[m] = in ? st[L.off_Sww + i * KP + j] : 0.0;
+            es1[m] = in ? st[L.off_CX + i * KP + j] : 0.0;
+        }
+    }
+    if (tid == 0) {
+        sc[4] = st[L.off_Syy];
+        sc[5] = st[L.off_scal + 0];
+        sc[6] = st[L.off_scal + 1];
+    }
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int e = tid + m * NTF;
+        const int i = e / KP, j = e % KP;
+        Sw[i * LDM + j] = es0[m];
+        Cx[i * LDM + j] = es1[m];
+    }
+    // sum(W o Syx): the products in the order of pca_tail_body's loop, which runs whole passes of 8
+    // per thread; all DP rows go to SW (zero beyond D and K), which the sum over the DP / 8 groups
+    // below walks and of which the head reads whole 32-row blocks
+    {
+        const int n = D * KP, jn = (n + 8 * NTF - 1) / (8 * NTF) * 8;
+        const int nsw = L.DP * KP;
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            const int e = tid + j * NTF;
+            if (j < jn) t1 += ww[j] * wy[j];
+            if (e < nsw) SW[(e / KP) * LDM + (e % KP)] = (e < n && e % KP < K) ? wy[j] : 0.0;
+        }
+    }
+    __syncthreads();
+    stamp(SP_T_LOADS);
+    // sum <x><x>^T on v_mfma_f64_16x16x4_f64: a wavefront owns a 16 x 16 tile of outputs, a group's
+    // partial is two instructions from zero -- rows 0..3 of the group in the four k-slots, then rows
+    // 4..7, C carried -- and the instruction adds its four products to C as a chain of fused
+    // multiply-adds in ascending slot order (tests/test_mfma_order_gpu.py): the chain of 8 of
+    // pca_gram_stats_kernel.  Lane l: A operand A[16 ti + l % 16][8 b + 4 h + l / 16], B operand
+    // Syx[8 b + 4 h + l / 16][16 tj + l % 16], results (16 ti + l / 16 + 4 reg, 16 tj + l % 16).
+    {
+        constexpr int KT = KP / 16;
+        const int LA = L.DP + 2;
+        const int w = tid >> 6, l15 = tid & 15, l4 = (tid & 63) >> 4;
+        const int nb = sw.nb, nb4 = nb & ~3;
+        if (w < KT * KT) {
+            const int ti = w / KT, tj = w % KT;
+            const double *ar = AL + (16 * ti + l15) * LA + l4;
+            const double *sr = SW + l4 * LDM + 16 * tj + l15;
+            const auto group = [&](int b) {
+                v4f64 p = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int h = 0; h < GRA; h += 4)
+                    p = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[b * GRA + h], sr[(b * GRA + h) * LDM], p,
+                                                             0, 0, 0);
+                return p;
+            };
+            v4f64 acc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = v4f64{0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+            for (int b = 0; b < nb4; b += 4) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[q] += group(b + q);
+            }
+#pragma unroll 1
+            for (int b = nb4; b < nb; ++b) acc[0] += group(b);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = 16 * ti + l4 + 4 * r, k2 = 16 * tj + l15;
+                const bool in = (k < K && k2 < K);
+                const double x = in ? (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]) : 0.0;
+                st[L.off_S + (L.DP + k) * KP + k2] = x;
+                Sx[k * LDM + k2] = x;
+            }
+        }
+    }
+    __syncthreads();
+    stamp(SP_T_PXX);
+    double t2 = 0.0, trx = 0.0;
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int e = tid + m * NTF;
+        const int i = e / KP, j = e % KP;
+        const double sxx = a.n_total * Cx[i * LDM + j] + 0.5 * (Sx[i * LDM + j] + Sx[j * LDM + i]);
+        t2 += Sw[i * LDM + j] * sxx;
+        if (i == j) trx += sxx;
+    }
+    {
+        // the three block_sums behind one barrier: the wave sums go to twelve words of their own (the
+        // <log alpha> quarter of al, which this tail does not use and nothing has touched since the
+        // barrier above) and every thread adds each four in the order of block_sum
+        double *r3 = al + 3 * KP;
+        static_assert(KP >= 3 * (NTF / 64), "twelve words");
+        t1 = wave_sum(t1);
+        t2 = wave_sum(t2);
+        trx = wave_sum(trx);
+        if ((tid & 63) == 0) {
+            r3[tid >> 6] = t1;
+            r3[NTF / 64 + (tid >> 6)] = t2;
+            r3[2 * (NTF / 64) + (tid >> 6)] = trx;
+        }
+        __syncthreads();
+        t1 = t2 = trx = 0.0;
+#pragma unroll
+        for (int i = 0; i < NTF / 64; ++i) {
+            t1 += r3[i];
+            t2 += r3[NTF / 64 + i];
+            trx += r3[2 * (NTF / 64) + i];
+        }
+    }
+    stamp(SP_T_BLOCKSUMS);
+    // (dot.py:355 E1 and dot.py:403 E2 collapsed to traces)
+    const double resid = sc[4] - 2.0 * t1 + t2;
+    // ---- tau (gamma.py:116-148 with the message gaussian.py:2363-2369) and alpha: the means ----
+    if (tid == 64) {
+        const double ta = a.a0t + 0.5 * (double)D * a.n_total;
+        const double tb = a.b0t + 0.5 * resid;
+        sc[0] = ta;
+        sc[1] = tb;
+        sc[2] = ta / tb;
+        red[0] = resid;
+        red[1] = trx;
+        st[L.off_tau + 0] = ta;
+        st[L.off_tau + 1] = tb;
+        st[L.off_tau + 2] = sc[2];
+        st[L.off_scal + 2] = resid;
+        if (!(tb > 0.0)) st[L.off_scal + 3] = (double)VMP_ERR_FLOATING;
+    }
+    if (tid < K) {
+        const double aa = a.a0a + 0.5 * (double)D;
+        const double ab = a.b0a + 0.5 * Sw[tid * LDM + tid];
+        const double am = aa / ab;
+        al[0 * KP + tid] = aa;
+        al[1 * KP + tid] = ab;
+        al[2 * KP + tid] = am;
+        st[L.off_alpha + 0 * KP + tid] = aa;
+        st[L.off_alpha + 1 * KP + tid] = ab;
+        st[L.off_alpha + 2 * KP + tid] = am;
+    }
+    // the critical path leaves the tail here: <log tau>, <log alpha>, the bound and the ring slot are
+    // the side wavefront's, so the three stamps that stand for them coincide
+    stamp(SP_T_TAU_ALPHA);
+    stamp(SP_T_BOUND);
+    stamp(SP_T_RING);
+}
+
+// pca_head_wide is the head of the next sweep as phase B runs it: pca_head_body without the placement
+// budget.  The D x K operand -- the rows of sum y<x>^T the tail left in SW, then the rows of <W> --
+// stays in LDS whole (whole 32-row blocks of it, as many as pca_head_body walks), so W = tau Syx Cov_W,
+// Sww and A = tau Cov_X W^T are one barrier-delimited phase each and nothing is loaded from global
+// memory.  Per output the MFMA sequence is the one of pca_head_body: over q for a tile of W and A,
+// over the rows in ascending order for a tile of Sww.  Stores are the same.
 //
-// defer_side is that work: the part of the deferred tail (pca_tail_body, DEFER) that no head reads.
+// SIDE (pca_sweep_mid_kernel only): what runs beside the FIRST inverse, and `stopw`, the LDS word it
+// leaves the stop decision in.  Every thread reads that word behind the inverse's closing barrier and
+// the workgroup returns on a stop before the head has stored anything: Lambda_W and its inverse were
+// computed for nothing, in LDS and registers only.
+//
+// defer_side is that work: the part of the tail that no head reads (see sweep_tail_wide).
 // Wavefront 1 runs it, wavefronts 2 and 3 idle.  Lanes < K take alpha's Gamma node k, the lanes from
 // K on tau's (lane 32 is the one whose values are used), through the same instructions: one sf_log
 // per lane, of b, which serves <log .> = digamma(a) - log b and the node's bound term.  Every other
@@ -1844,22 +1631,19 @@ __device__ __forceinline__ void pca_head_wide(const small_args &a, double *st, d
     stamp(SP_H_A);
 }
 
-// the dynamic LDS of the one-launch sweep with LOCAL: A (phase A, kept for the tail) | the G rows and
-// the Syx block of phase A, then the DP rows of SW | the ticket word, which gets 16 bytes of its own
-// so that A survives the draw
+// the dynamic LDS of the one-launch sweep: A (phase A, kept for the tail) | the G rows and the Syx
+// block of phase A, then the DP rows of SW | the ticket word, which gets 16 bytes of its own so that
+// A survives the draw
 __host__ __device__ inline size_t sweep_local_lds(int KP, int DP)
 {
     return ((size_t)KP * (DP + 2) + (size_t)DP * (KP + 1) + 2) * sizeof(double);
 }
 
-template <int KP, bool WIDE, bool LOCAL, bool DEFER, bool MFMA, class STAMP>
-__device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *st, double *P,
+template <int KP, class STAMP>
+__device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *st,
                                                    const vmp_sweep_tail &sw, unsigned int *ticket,
                                                    const double *sf, const STAMP &stamp)
 {
-    static_assert(!LOCAL || WIDE, "sum <x><x>^T is formed locally beside the wide bodies only");
-    static_assert(!DEFER || LOCAL, "the bound is deferred behind the local wide tail only");
-    static_assert(!MFMA || DEFER, "the matrix-core Gram products are built for the deferred form only");
     extern __shared__ __align__(16) double gl[];
     __shared__ tail_lds<KP> ts;
     const int tid = threadIdx.x;
@@ -1872,18 +1656,15 @@ __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *
         return;
     }
     stamp(SP_ENTRY);
-    if constexpr (WIDE)
-        gram_phase_a_wide<KP, STAMP, !LOCAL, MFMA>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
-    else
-        gram_phase_a<KP>(a.L, a.D, a.K, st, P, gl, blockIdx.x, stamp);
+    gram_phase_a_wide<KP, STAMP>(a.L, a.D, a.K, st, gl, blockIdx.x, stamp);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     stamp(SP_PXX);
-    // LOCAL: SW lies behind A, over the G rows and the Syx block of phase A, the ticket word behind SW
-    const int na = LOCAL ? KP * ((int)a.L.DP + 2) : 0;
+    // SW lies behind A, over the G rows and the Syx block of phase A, the ticket word behind SW
+    const int na = KP * ((int)a.L.DP + 2);
     double *SW = gl + na;
-    unsigned int *word = reinterpret_cast<unsigned int *>(LOCAL ? SW + (int)a.L.DP * (KP + 1) : gl);
-    if (tid == 0) {                                                // (phase A's LDS is free now)
+    unsigned int *word = reinterpret_cast<unsigned int *>(SW + (int)a.L.DP * (KP + 1));
+    if (tid == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         *word = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1900,43 +1681,31 @@ __device__ __forceinline__ void pca_sweep_mid_body(const small_args &a, double *
     }
     __syncthreads();
     stamp(SP_ACQUIRE);
-    // (every thread has read the ticket word: the dynamic region is free for SW)
-    pca_tail_body<KP, TAIL_SWEEP, WIDE, STAMP, LOCAL, DEFER, MFMA>(a, st, &sw, ts, SW, stamp, gl);
+    // (phase A's G rows and Syx block are read no more: their region is free for SW)
+    sweep_tail_wide<KP>(a, st, sw, ts, SW, gl, stamp);
     __syncthreads();
-    if constexpr (DEFER) {
-        // the rest of the tail, the stop rule included, runs beside the head's first inverse; the
-        // head reads ts.stop behind it, before its first store
-        const defer_side<KP, STAMP> side{a, st, sw, ts, sf, stamp};
-        pca_head_wide<KP>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], SW, stamp, side, &ts.stop);
-        return;
-    }
-    if (ts.stop != 0.0) return;
-    // Cov_X, sum <x><x>^T, <alpha> and <tau> go over in LDS.  WIDE: so do the Syx rows (in SW);
-    // otherwise the head loads them -- phase A wrote them, acquired above -- and reads back its own <W>
-    if constexpr (WIDE)
-        pca_head_wide<KP>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], SW, stamp);
-    else
-        pca_head_body<KP, true>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], stamp);
+    // the rest of the tail, the stop rule included, runs beside the head's first inverse; the head
+    // reads ts.stop behind it, before its first store.  Cov_X, sum <x><x>^T, <alpha>, <tau> and the
+    // Syx rows (in SW) go over in LDS
+    const defer_side<KP, STAMP> side{a, st, sw, ts, sf, stamp};
+    pca_head_wide<KP>(a, st, ts.Cx, ts.Sx, ts.al + 2 * KP, ts.sc[2], SW, stamp, side, &ts.stop);
 }
 
-// WIDE: phase B runs the wide tail and head ("pca_sweep_wide", default); false: pca_tail_body and
-// pca_head_body as the three-launch sweep runs them.  LOCAL ("pca_sweep_local_pxx", default, with
-// WIDE): no partial blocks of sum <x><x>^T are stored, the tail forms the sum from LDS.  DEFER
-// ("pca_sweep_defer", default, with LOCAL): the tail hands over as soon as the head's inputs are
-// ready and the bound, the ring slot and the stop rule run beside the head's first inverse, with the
-// sweep-invariant special functions read from `sf` (vmp_ctx::sweep_sf; not read otherwise).
-template <int KP, bool WIDE, bool LOCAL, bool DEFER = false, bool MFMA = false>
+// `sf`: the sweep-invariant special functions of the side wavefront (vmp_ctx::sweep_sf).  `P`, the
+// partial blocks of the three-launch sweep, is not used; it keeps the argument block of the launch
+// what it was.
+template <int KP>
 __global__ void __launch_bounds__(NTF)
 pca_sweep_mid_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw, unsigned int *ticket,
                      const double *sf)
 {
-    pca_sweep_mid_body<KP, WIDE, LOCAL, DEFER, MFMA>(a, st, P, sw, ticket, sf, stamps_off());
+    pca_sweep_mid_body<KP>(a, st, sw, ticket, sf, stamps_off());
 }
 
 // the same with wall_clock64 stamps ("pca_sweep_stamps"): `out` is this launch's row of
 // VMP_SWEEP_NSTAMP words, written by the workgroup that ran phase B; `level` the key's value (2: the
-// side wavefront of the deferred form stamps too)
-template <int KP, bool WIDE, bool LOCAL, bool DEFER = false, bool MFMA = false>
+// side wavefront stamps too)
+template <int KP>
 __global__ void __launch_bounds__(NTF)
 pca_sweep_mid_stamped_kernel(small_args a, double *st, double *P, vmp_sweep_tail sw,
                              unsigned int *ticket, const double *sf, unsigned long long *out, int level)
@@ -1945,13 +1714,13 @@ pca_sweep_mid_stamped_kernel(small_args a, double *st, double *P, vmp_sweep_tail
     if (threadIdx.x < VMP_SWEEP_NSTAMP) stl[threadIdx.x] = 0;
     __syncthreads();
     const stamps_on stamp{stl, level};
-    pca_sweep_mid_body<KP, WIDE, LOCAL, DEFER, MFMA>(a, st, P, sw, ticket, sf, stamp);
+    pca_sweep_mid_body<KP>(a, st, sw, ticket, sf, stamp);
     // (a workgroup that did not run phase B leaves no tail stamp)
     if (threadIdx.x == 0 && stl[SP_T_LOADS] != 0)
         for (int i = 0; i < VMP_SWEEP_NSTAMP; ++i) out[i] = stl[i];
 }
 
-// The first head of a chunk (vmp_pca_sweeps, "pca_sweep_wide" on, no latent pass in flight): the
+// The first head of a chunk (vmp_pca_sweeps, one-launch sweeps, no latent pass in flight): the
 // wide head body in a launch of its own.  What the tail of a mid launch hands over in LDS -- Cov_X,
 // sum <x><x>^T, <alpha>, <tau> and the rows of sum y<x>^T -- is loaded from the state, masked as
 // pca_head_body masks its loads.
@@ -2252,8 +2021,7 @@ static int32_t raise_lds_once(vmp_ctx *ctx, F *k16, F *k32, bool *raised)
     return VMP_OK;
 }
 
-int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state, double *P,
-                                 int32_t wide)
+int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *state)
 {
     vmp_pca_layout L;
     const int32_t rc = vmp_pca_get_layout(D, K, &L);
@@ -2261,100 +2029,61 @@ int32_t vmp_pca_launch_gram_fast(vmp_ctx *ctx, int32_t D, int32_t K, double *sta
     VMP_REQUIRE(ctx, L.KP <= 32 && D <= FAST_D, VMP_ERR_UNSUPPORTED,
                 "the fast Gram statistics cover K <= 32, D <= %d", FAST_D);
     VMP_REQUIRE(ctx, ((uintptr_t)state % 16) == 0, VMP_ERR_INVALID, "state must be 16-byte aligned");
-    static bool raised[2][64] = {{false}};
-    const int32_t rr = wide ? raise_lds_once(ctx, pca_gram_wide_kernel<16>, pca_gram_wide_kernel<32>,
-                                             raised[1])
-                            : raise_lds_once(ctx, pca_gram_fast_kernel<16>, pca_gram_fast_kernel<32>,
-                                             raised[0]);
+    static bool raised[64] = {false};
+    const int32_t rr = raise_lds_once(ctx, pca_gram_wide_kernel<16>, pca_gram_wide_kernel<32>, raised);
     if (rr != VMP_OK) return rr;
     const int nb = (int)(L.DP / GRA);
-    if (wide) {
-        const size_t ldw = gram_phase_a_wide_lds((int)L.KP, (int)L.DP);
-        if (wide == 2) {        // Syx on the matrix cores ("pca_sweep_mfma")
-            static bool raised_m[64] = {false};
-            const int32_t rm = raise_lds_once(ctx, pca_gram_wide_kernel<16, true>,
-                                              pca_gram_wide_kernel<32, true>, raised_m);
-            if (rm != VMP_OK) return rm;
-            if (L.KP == 16)
-                hipLaunchKernelGGL((pca_gram_wide_kernel<16, true>), dim3(nb), dim3(NTF), ldw, ctx->stream,
-                                   L, D, K, state, P);
-            else
-                hipLaunchKernelGGL((pca_gram_wide_kernel<32, true>), dim3(nb), dim3(NTF), ldw, ctx->stream,
-                                   L, D, K, state, P);
-        } else if (L.KP == 16)
-            hipLaunchKernelGGL(pca_gram_wide_kernel<16>, dim3(nb), dim3(NTF), ldw, ctx->stream, L, D, K,
-                               state, P);
-        else
-            hipLaunchKernelGGL(pca_gram_wide_kernel<32>, dim3(nb), dim3(NTF), ldw, ctx->stream, L, D, K,
-                               state, P);
-        VMP_HIP_CHECK(ctx, hipGetLastError());
-        return VMP_OK;
-    }
-    const size_t lds = gram_phase_a_lds((int)L.KP, (int)L.DP);
+    const size_t lds = gram_phase_a_wide_lds((int)L.KP, (int)L.DP);
     if (L.KP == 16)
-        hipLaunchKernelGGL(pca_gram_fast_kernel<16>, dim3(nb), dim3(NTF), lds, ctx->stream, L, D, K,
-                           state, P);
+        hipLaunchKernelGGL(pca_gram_wide_kernel<16>, dim3(nb), dim3(NTF), lds, ctx->stream, L, D, K,
+                           state);
     else
-        hipLaunchKernelGGL(pca_gram_fast_kernel<32>, dim3(nb), dim3(NTF), lds, ctx->stream, L, D, K,
-                           state, P);
+        hipLaunchKernelGGL(pca_gram_wide_kernel<32>, dim3(nb), dim3(NTF), lds, ctx->stream, L, D, K,
+                           state);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }
 
 // one instantiation of the one-launch sweep; `stamps` (null: the default kernel) is the launch's row
-template <int KP, bool WIDE, bool LOCAL, bool DEFER = false, bool MFMA = false>
+template <int KP>
 static int32_t launch_mid(vmp_ctx *ctx, const small_args &a, double *state, double *P,
                           const vmp_sweep_tail &t, unsigned int *ticket, unsigned long long *stamps,
                           int stamp_level)
 {
-    VMP_REQUIRE(ctx, !DEFER || ctx->sweep_sf, VMP_ERR_INVALID,
-                "the deferred sweep needs vmp_pca_sweep_constants first");
+    VMP_REQUIRE(ctx, ctx->sweep_sf, VMP_ERR_INVALID,
+                "the one-launch sweep needs vmp_pca_sweep_constants first");
     static bool raised[2][64] = {{false}};
     const int dev = ctx->device & 63, s = stamps ? 1 : 0;
     if (!raised[s][dev]) {
-        const void *f = stamps ? (const void *)pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL, DEFER, MFMA>
-                               : (const void *)pca_sweep_mid_kernel<KP, WIDE, LOCAL, DEFER, MFMA>;
+        const void *f = stamps ? (const void *)pca_sweep_mid_stamped_kernel<KP>
+                               : (const void *)pca_sweep_mid_kernel<KP>;
         VMP_HIP_CHECK(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                96 * 1024));
         raised[s][dev] = true;
     }
-    // (the rows of SW the wide bodies keep fit in phase A's region: DP (KP + 1) doubles at most;
-    // LOCAL keeps A beside them, 67 KB at KP = 32, DP = 128)
-    const size_t lds = LOCAL ? sweep_local_lds((int)a.L.KP, (int)a.L.DP)
-                       : WIDE ? gram_phase_a_wide_lds((int)a.L.KP, (int)a.L.DP)
-                              : gram_phase_a_lds((int)a.L.KP, (int)a.L.DP);
+    // (A beside the DP rows of SW: 67 KB at KP = 32, DP = 128)
+    const size_t lds = sweep_local_lds((int)a.L.KP, (int)a.L.DP);
     const dim3 nb((unsigned)(a.L.DP / GRA));
     if (stamps)
-        hipLaunchKernelGGL((pca_sweep_mid_stamped_kernel<KP, WIDE, LOCAL, DEFER, MFMA>), nb, dim3(NTF), lds,
-                           ctx->stream, a, state, P, t, ticket, (const double *)ctx->sweep_sf, stamps,
-                           stamp_level);
+        hipLaunchKernelGGL(pca_sweep_mid_stamped_kernel<KP>, nb, dim3(NTF), lds, ctx->stream, a, state,
+                           P, t, ticket, (const double *)ctx->sweep_sf, stamps, stamp_level);
     else
-        hipLaunchKernelGGL((pca_sweep_mid_kernel<KP, WIDE, LOCAL, DEFER, MFMA>), nb, dim3(NTF), lds, ctx->stream, a,
-                           state, P, t, ticket, (const double *)ctx->sweep_sf);
+        hipLaunchKernelGGL(pca_sweep_mid_kernel<KP>, nb, dim3(NTF), lds, ctx->stream, a, state, P, t,
+                           ticket, (const double *)ctx->sweep_sf);
     VMP_HIP_CHECK(ctx, hipGetLastError());
     return VMP_OK;
 }
 
 int32_t vmp_pca_launch_sweep_mid(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,
                                  double a0t, double b0t, double a0a, double b0a, double *state,
-                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket, int32_t wide,
+                                 double *P, const vmp_sweep_tail &t, unsigned int *ticket,
                                  unsigned long long *stamps, int32_t stamp_level)
 {
     small_args a;
     const int32_t rc = fill_small_args(ctx, a, D, K, n_total, x_prec, a0t, b0t, a0a, b0a);
     if (rc != VMP_OK) return rc;
-    const int sl = stamp_level;
-    if (a.L.KP == 16)
-        return wide == 4 ? launch_mid<16, true, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
-               : wide == 3 ? launch_mid<16, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
-               : wide == 2 ? launch_mid<16, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
-               : wide      ? launch_mid<16, true, false>(ctx, a, state, P, t, ticket, stamps, sl)
-                           : launch_mid<16, false, false>(ctx, a, state, P, t, ticket, stamps, sl);
-    return wide == 4 ? launch_mid<32, true, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
-           : wide == 3 ? launch_mid<32, true, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
-           : wide == 2 ? launch_mid<32, true, true>(ctx, a, state, P, t, ticket, stamps, sl)
-           : wide      ? launch_mid<32, true, false>(ctx, a, state, P, t, ticket, stamps, sl)
-                       : launch_mid<32, false, false>(ctx, a, state, P, t, ticket, stamps, sl);
+    if (a.L.KP == 16) return launch_mid<16>(ctx, a, state, P, t, ticket, stamps, stamp_level);
+    return launch_mid<32>(ctx, a, state, P, t, ticket, stamps, stamp_level);
 }
 
 int32_t vmp_pca_sweep_constants(vmp_ctx *ctx, int32_t D, int32_t K, int64_t n_total, double x_prec,

@@ -255,34 +255,27 @@ int32_t vmp_pca_sweep_counts(vmp_ctx *ctx, int64_t *enqueued, int64_t *executed,
  * error: this count is where that shows.  Launches of that kernel on this context since it was
  * created (no device read). */
 int32_t vmp_pca_sweep_mid_count(vmp_ctx *ctx, int64_t *launches);
-/* Phase B of that launch runs wide forms of the tail and the head -- every load of the tail in one
- * batch, the D x K operand of the head whole in LDS, built for a workgroup that has the GPU to
- * itself -- unless tune key "pca_sweep_wide" / VMP_PCA_SWEEP_WIDE (default 1) is 0, which selects the
- * bodies of the three-launch sweep inside the launch.  The two agree bitwise.  With the wide bodies
- * and tune key "pca_sweep_local_pxx" / VMP_PCA_SWEEP_LOCAL_PXX (default 1) the workgroups store no
- * partial blocks of sum <x><x>^T: the workgroup that runs phase B forms the sum from the A and the rows
- * of sum y<x>^T it holds in LDS, by the same chains added in the same order (bitwise the same; 0: the
- * blocks travel through memory).  The first head of a batch runs the wide head too, in a launch of
- * its own, unless a latent pass is still in flight.
- * With both of these and tune key "pca_sweep_defer" / VMP_PCA_SWEEP_DEFER (default 1) the tail hands
- * over to the head as soon as <tau>, <alpha>, Cov_X and sum <x><x>^T are ready.  <log tau>, <log alpha>,
- * the bound, the ring slot and the stop rule are formed by one wavefront beside the head's first
- * inverse; a stop is read behind that inverse, before the head's first store, so a stopped loop leaves
- * what it left before.  The special functions whose arguments do not change from sweep to sweep
+/* That launch is built for a GPU it has to itself.  Its workgroups form the rows of sum y<x>^T on the
+ * matrix cores (v_mfma_f64_4x4x4_4b_f64) and store no partial blocks of sum <x><x>^T: the workgroup
+ * that runs phase B loads everything its tail needs in one batch and forms that sum from the A and the
+ * rows of sum y<x>^T it holds in LDS (v_mfma_f64_16x16x4_f64), the partials added in the order of the
+ * three-launch sweep.  Both instructions add their four products to C in ascending order of the
+ * k-slots, every step fused (vmp_mfma_order_probe below), so every chain keeps the bits of the scalar
+ * chains of the three-launch sweep.  The tail hands over to the head, which keeps its D x K operand
+ * whole in LDS, as soon as <tau>, <alpha>, Cov_X and sum <x><x>^T are ready; <log tau>, <log alpha>, the
+ * bound, the ring slot and the stop rule are formed by one wavefront beside the head's first inverse.
+ * A stop is read behind that inverse, before the head's first store, so a stopped loop leaves what
+ * the three launches leave.  The special functions whose arguments do not change from sweep to sweep
  * (digamma and lgamma of the two Gamma shapes, lgamma(a0), log(b0), log(2 pi), log(x_prec)) are
  * computed by one small launch when the priors, D, the plate size or x_prec differ from those of the
  * previous call on the context, and read from a buffer of the context (not the state block) after
- * that.  Bitwise the same as 0, where the tail computes all of it each sweep.
- * With all three and tune key "pca_sweep_mfma" / VMP_PCA_SWEEP_MFMA (default 1) the chains of
- * sum y<x>^T (phase A, v_mfma_f64_4x4x4_4b_f64) and of the partials of sum <x><x>^T (the tail,
- * v_mfma_f64_16x16x4_f64) run on the matrix cores instead of as scalar fused multiply-adds fed from
- * LDS.  Both instructions add their four products to C in ascending order of the k-slots, every
- * step fused (vmp_mfma_order_probe below), so every chain keeps its bits (0: the scalar chains).
+ * that.  The first head of a batch runs the same head body, in a launch of its own, unless a latent
+ * pass is still in flight.  The one launch and the three launches agree bitwise.
  *
  * Measurement: while tune key "pca_sweep_stamps" is 1, vmp_pca_sweeps launches a stamped build of that
  * kernel, in which one lane records wall_clock64() (a constant 100 MHz counter) at the boundaries of
  * its phases: VMP_PCA_SWEEP_NSTAMP words per launch of the latest batch, 0 where a boundary was not
- * passed (order: csrc/vmp_pca_small.hip, enum SP_*).  At 2 the deferred form also records, in words 19
+ * passed (order: csrc/vmp_pca_small.hip, enum SP_*).  At 2 the launch also records, in words 19
  * and 20, where its side wavefront has stored the tau / alpha state and where it has written the ring
  * slot and the stop word.  This call waits for the stream and copies up to
  * max_rows rows out.  The buffer belongs to the context and exists only once the key has been on:
@@ -290,12 +283,11 @@ int32_t vmp_pca_sweep_mid_count(vmp_ctx *ctx, int64_t *launches);
 #define VMP_PCA_SWEEP_NSTAMP 24
 int32_t vmp_pca_sweep_stamps(vmp_ctx *ctx, uint64_t *out, int32_t max_rows, int32_t *rows,
                              int32_t *allocated);
-/* The Gram statistics of one sweep alone, from the A and G of the state block: rows of sum y<x>^T
- * into the state, the DP / 8 partial blocks of sum <x><x>^T into the workspace (not added up).
- * form 0: the kernel every other path uses; form 1: the body of the one-launch sweep with
- * "pca_sweep_wide" = 0, form 2: its body with "pca_sweep_wide" = 1, form 3: that body with the chains of
- * sum y<x>^T on the matrix cores, "pca_sweep_mfma" = 1 (all three K <= 32, D <= 128, 16-byte aligned
- * state).  The four agree bitwise. */
+/* The Gram statistics of one sweep alone, from the A and G of the state block.
+ * form 0: the kernel of the three-launch sweep -- the rows of sum y<x>^T into the state, the DP / 8
+ * partial blocks of sum <x><x>^T into the workspace (not added up).  form 1: phase A of the one-launch
+ * sweep (K <= 32, D <= 128, 16-byte aligned state) -- the rows of sum y<x>^T into the state and nothing
+ * else: it does not write the workspace.  The rows agree bitwise.  Any other form: VMP_ERR_INVALID. */
 int32_t vmp_pca_gram_stats_form(vmp_ctx *ctx, int32_t D, int32_t K, double *state, void *workspace,
                                 int32_t form);
 /* Test entry: D = A B + C by ONE fp64 matrix instruction per tile, one wavefront, `ntiles` tiles in

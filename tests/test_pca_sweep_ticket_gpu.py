@@ -213,10 +213,14 @@ def test_early_stop_inside_a_chunk(D, K):
         assert np.array_equal(one['state'][off:off + n], loop['state'][off:off + n]), off
 
 
-@pytest.mark.parametrize('D,K', DKS)
-def test_gram_statistics_body_alone_equals_the_old_kernel(D, K):
-    """Phase A of the one-launch sweep through its stand-alone entry against pca_gram_stats_kernel
-    on random A and G (padding included): Syx rows and the partial blocks, bit for bit."""
+def phase_a_alone(D, K, seed):
+    """Phase A of the one-launch sweep through its stand-alone entry (form 1 of
+    vmp_pca_gram_stats_form) against pca_gram_stats_kernel (form 0) on random A and G, padding
+    included (so a chain that read a padded column or kept a padded row would show): the whole
+    state block, with the Syx rows in it, bit for bit.  Form 0 also leaves the DP / 8 partial blocks
+    of sum <x><x>^T in the workspace and nothing behind them; form 1 forms no partial blocks and must
+    leave the workspace, filled with NaN here, untouched.  Returns the layout, the host block the
+    two started from and the state form 1 left."""
     from bayespy_amd.device import get_runtime, ptr
     from bayespy_amd.inference.plans.pca import HIPKernels
     rt = get_runtime()
@@ -224,7 +228,7 @@ def test_gram_statistics_body_alone_equals_the_old_kernel(D, K):
     L = k.layout(D, K)
     DP, KP = int(L.DP), int(L.KP)
     nb = DP // 8
-    rng = np.random.default_rng(7 * D + K)
+    rng = np.random.default_rng(seed)
     host = np.zeros(int(L.total))
     host[L.off_A:L.off_A + KP * DP] = rng.standard_normal(KP * DP)
     host[L.off_G:L.off_G + DP * DP] = rng.standard_normal(DP * DP)
@@ -237,14 +241,36 @@ def test_gram_statistics_body_alone_equals_the_old_kernel(D, K):
         rt.sync_stream()
         rt.check(rt.lib.vmp_pca_gram_stats_form(k.ctx, D, K, ptr(st), ptr(ws), form))
         rt.sync_stream()
-        got.append((st.cpu().numpy().copy(), ws[:nb * KP * KP + 64].cpu().numpy().copy()))
+        got.append((st.cpu().numpy().copy(), ws.cpu().numpy().copy()))
     (s0, p0), (s1, p1) = got
     assert np.array_equal(s0, s1)
-    assert np.array_equal(p0, p1, equal_nan=True)
-    assert not np.isnan(p1[:nb * KP * KP]).any() and np.isnan(p1[nb * KP * KP:]).all()
-    # (and the statistics are what they say: Syx = G A^T on the unpadded block)
+    assert not np.isnan(p0[:nb * KP * KP]).any() and np.isnan(p0[nb * KP * KP:]).all()
+    assert np.isnan(p1).all()
+    syx = s1[L.off_S:L.off_S + DP * KP].reshape(DP, KP)[:D, :K]
+    assert np.any(syx != 0.0)
+    return L, host, s1
+
+
+@pytest.mark.parametrize('D,K', DKS)
+def test_gram_statistics_body_alone_equals_the_old_kernel(D, K):
+    """Forms 1 and 0 of vmp_pca_gram_stats_form bit for bit (phase_a_alone), and the statistics are
+    what they say: Syx = G A^T on the unpadded block."""
+    L, host, s1 = phase_a_alone(D, K, 7 * D + K)
+    DP, KP = int(L.DP), int(L.KP)
     A = host[L.off_A:L.off_A + KP * DP].reshape(KP, DP)
     G = host[L.off_G:L.off_G + DP * DP].reshape(DP, DP)
     want = G[:D, :D] @ A[:K, :D].T
     np.testing.assert_allclose(s1[L.off_S:L.off_S + DP * KP].reshape(DP, KP)[:D, :K], want,
                                rtol=0, atol=1e-12 * D * np.abs(want).max())
+
+
+def test_gram_statistics_form_out_of_range_is_an_error():
+    from bayespy_amd._lib import VMP_ERR_INVALID
+    from bayespy_amd.device import get_runtime, ptr
+    from bayespy_amd.inference.plans.pca import HIPKernels
+    rt = get_runtime()
+    k = HIPKernels(rt)
+    st = rt.zeros(int(k.layout(8, 3).total))
+    ws = rt.zeros(int(k.workspace_doubles(8, 3)))
+    for form in (-1, 2, 3):
+        assert rt.lib.vmp_pca_gram_stats_form(k.ctx, 8, 3, ptr(st), ptr(ws), form) == VMP_ERR_INVALID

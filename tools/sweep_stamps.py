@@ -2,28 +2,23 @@
 """Where the time goes inside one launch of pca_sweep_mid_kernel: per-phase medians from the
 wall_clock64 stamps of the stamped build (tune key "pca_sweep_stamps").
 
-    python tools/sweep_stamps.py [--wide 0|1] [--local 0|1] [--defer 0|1] [--D 128] [--K 32] [--N 4096]
-                                 [--chunks 5]
+    python tools/sweep_stamps.py [--D 128] [--K 32] [--N 4096] [--chunks 5]
 
 Runs chunks of 32 sweeps (31 mid launches each) of the PCA demo model at the headline's (D, K) with a
 small N, reads the stamps of each chunk and prints the median over all launches of every phase, in
 microseconds.  wall_clock64 counts a constant 100 MHz clock, so one tick is 10 ns and a phase of a
 few microseconds is resolved to a few per cent.  A stamp is one clock read and one store to LDS by
 one lane; that this costs well under a tick is assumed, not measured (the stamped kernel's own
-duration has not been set against the default kernel's).  --wide 0 selects the tail and head bodies of the three-launch sweep
-inside the launch ("pca_sweep_wide" = 0), which share one loop for W and Sww: that row reads 0.
---local 0 ("pca_sweep_local_pxx" = 0) has the partial blocks of sum <x><x>^T stored by phase A and added
-by the tail ('tail: partials summed'); with --local 1 the tail forms the sum from LDS after its loads
-have landed ('tail: Pxx formed') and the other boundary is not passed.  A boundary that is not passed
-prints '-'.
---defer 1 ("pca_sweep_defer" = 1, with --wide 1 --local 1) hands over to the head once the means of tau
-and alpha are ready: the three boundaries behind 'tail: block sums done' are stamped together there, and
-the stamped build runs at "pca_sweep_stamps" = 2, where the side wavefront -- which forms the bound, the
-ring slot and the stop word beside the head's first inverse -- stamps too.  Its two boundaries are
-printed since kernel entry, with whether the side work ends before 'head: inverse 1 done'.
---mfma 0 ("pca_sweep_mfma" = 0, with all of the above on) runs the chains of 'Syx done' and 'tail: Pxx
-formed' as scalar fused multiply-adds instead of on the matrix cores.  The last column is the least and
-the greatest length of each phase over the launches.
+duration has not been set against the default kernel's).
+The rows are those of enum SP_*, which keeps the boundaries of forms the kernel no longer has so that
+earlier records stay comparable: the tail forms sum <x><x>^T from LDS after its loads have landed
+('tail: Pxx formed') and adds no stored partial blocks, so 'tail: partials summed' is not passed and
+prints '-'; 'A: Pxx stored' is the end of phase A.  The tail hands over to the head once the means of
+tau and alpha are ready: the three boundaries behind 'tail: block sums done' are stamped together
+there.  The stamped build runs at "pca_sweep_stamps" = 2, where the side wavefront -- which forms the
+bound, the ring slot and the stop word beside the head's first inverse -- stamps too.  Its two
+boundaries are printed since kernel entry, with whether the side work ends before 'head: inverse 1
+done'.  The last column is the least and the greatest length of each phase over the launches.
 """
 import argparse
 import os
@@ -46,10 +41,6 @@ SIDE = ['side: tau/alpha state stored', 'side: ring and stop written']      # wo
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--wide', type=int, default=1)
-    ap.add_argument('--local', type=int, default=1)
-    ap.add_argument('--defer', type=int, default=1)
-    ap.add_argument('--mfma', type=int, default=1)
     ap.add_argument('--D', type=int, default=128)
     ap.add_argument('--K', type=int, default=32)
     ap.add_argument('--N', type=int, default=4096)
@@ -59,13 +50,7 @@ def main():
     from bayespy_amd.device import get_runtime
     from bayespy_amd.inference import VB
     rt = get_runtime()
-    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_wide', a.wide))
-    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_local_pxx', a.local))
-    defer = 1 if (a.wide and a.local and a.defer) else 0
-    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_defer', defer))
-    mfma = 1 if (defer and a.mfma) else 0
-    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_mfma', mfma))
-    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_stamps', 2 if defer else 1))
+    rt.check(rt.lib.vmp_tune_set(b'pca_sweep_stamps', 2))
     rng = np.random.default_rng(0)
     y = rng.standard_normal((a.D, a.K)) @ rng.standard_normal((a.K, a.N)) \
         + 0.1 * rng.standard_normal((a.D, a.N))
@@ -89,9 +74,7 @@ def main():
         assert allocated and r.shape[0] == 31, r.shape
         rows.append(r[:, :len(NAMES) + len(SIDE)].astype(np.int64))
     t = np.concatenate(rows[1:])                       # (the first chunk warms up)
-    print('pca_sweep_mid_kernel stamps: D=%d K=%d N=%d, pca_sweep_wide=%d, pca_sweep_local_pxx=%d, '
-          'pca_sweep_defer=%d, pca_sweep_mfma=%d, %d launches'
-          % (a.D, a.K, a.N, a.wide, a.local if a.wide else 0, defer, mfma, t.shape[0]))
+    print('pca_sweep_mid_kernel stamps: D=%d K=%d N=%d, %d launches' % (a.D, a.K, a.N, t.shape[0]))
     print('wall_clock64 at a constant 100 MHz: 1 tick = 0.01 us; medians over the launches')
     print('%-28s %10s %12s %14s' % ('boundary', 'phase_us', 'since_entry', 'phase min-max'))
     prev = t[:, 0]
@@ -113,14 +96,13 @@ def main():
                    t[:, ix['head: A stored']] - t[:, ix['tail: ring written']])))
     total = (t[:, ix['head: A stored']] - t[:, 0]) * TICK_US
     print('entry -> A stored %.2f us (min %.2f, max %.2f)' % (np.median(total), total.min(), total.max()))
-    if defer:
-        inv1 = t[:, ix['head: inverse 1 done']]
-        for i, name in enumerate(SIDE):
-            print('%-28s %10s %12.2f' % (name, '', np.median(t[:, len(NAMES) + i] - t[:, 0]) * TICK_US))
-        slack = inv1 - t[:, len(NAMES) + 1]
-        print("side work ends before 'head: inverse 1 done' in %d of %d launches; slack median %.2f, "
-              'min %.2f us' % (int((slack >= 0).sum()), slack.size, np.median(slack) * TICK_US,
-                               slack.min() * TICK_US))
+    inv1 = t[:, ix['head: inverse 1 done']]
+    for i, name in enumerate(SIDE):
+        print('%-28s %10s %12.2f' % (name, '', np.median(t[:, len(NAMES) + i] - t[:, 0]) * TICK_US))
+    slack = inv1 - t[:, len(NAMES) + 1]
+    print("side work ends before 'head: inverse 1 done' in %d of %d launches; slack median %.2f, "
+          'min %.2f us' % (int((slack >= 0).sum()), slack.size, np.median(slack) * TICK_US,
+                           slack.min() * TICK_US))
 
 
 if __name__ == '__main__':
