@@ -234,6 +234,11 @@ SIGNATURES = {
     'vmp_lda_dirichlet_step': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_f64, c_f64,
                                        c_vp, c_vp, c_vp, c_vp]),
     'vmp_lda_dot': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    'vmp_lda_wide_limits': (c_i32, [P(c_i32), P(c_i32), P(c_i32)]),
+    'vmp_lda_wide_plan': (c_i32, [c_i64, c_i32, P(c_i32), P(c_i32), P(c_i64)]),
+    'vmp_lda_wide_token_pass': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp]),
     'vmp_bmm_limits': (c_i32, [P(c_i32), P(c_i32)]),
     'vmp_bmm_plan': (c_i32, [c_i64, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_bmm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),

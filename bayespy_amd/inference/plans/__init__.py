@@ -9,6 +9,7 @@ from .gmm import GMMPlan, GMMSVIPlan
 from .lssm import LSSMPlan
 from .lssm_masked import MaskedLSSMPlan
 from .lda import LDAPlan, LDASVIPlan
+from .lda_wide import WideLDAPlan
 from .bmm import BernoulliMixturePlan, BernoulliMixtureSVIPlan
 from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
@@ -63,6 +64,10 @@ OPT_IN_BATCHES = {BernoulliMixturePlan: [BernoulliMixtureSVIPlan],
 # 'fused' and 'fused+batches' do not try these forms and keep raising for such a model
 OPT_IN_GAUSSIAN_BATCHES = {DiagGaussianMixturePlan: [DiagGaussianMixtureSVIPlan],
                            MaskedDiagGaussianMixturePlan: [MaskedDiagGaussianMixtureSVIPlan]}
+# engine='fused+topics': the form of the LDA block for 65 to 1024 topics (plans/lda_wide.py), a plan
+# class of its own, tried right after that block (which declines K > 64 with a reason).  Everything
+# else is engine='fused'; every other engine value does not try this form and keeps its answer
+OPT_IN_TOPICS = {LDAPlan: [WideLDAPlan]}
 
 
 def _with_masked(types):
@@ -78,6 +83,13 @@ def _with_batches(types):
 def _with_gaussian_batches(types):
     """``types`` with the plan classes of ``OPT_IN_GAUSSIAN_BATCHES`` inserted after their block."""
     return [Q for P in types for Q in [P] + OPT_IN_GAUSSIAN_BATCHES.get(P, [])]
+
+
+def _with_topics(types):
+    """``types`` with the plan classes of ``OPT_IN_TOPICS`` inserted after their block (or after
+    the opt-in form that stands in its place)."""
+    after = {OPT_IN_FORMS.get(P, P): v for P, v in OPT_IN_TOPICS.items()}
+    return [Q for P in types for Q in [P] + after.get(P, [])]
 
 
 def opt_in_types():
@@ -112,6 +124,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or any(type(p) in v for v in OPT_IN_MASKED.values())
                                  or type(p) in OPT_IN_LAST or type(p) in OPT_IN_COUNTS
                                  or type(p) in OPT_IN_VECTORS or type(p) in OPT_IN_TRIALS
+                                 or any(type(p) in v for v in OPT_IN_TOPICS.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -149,9 +162,13 @@ def compile_model(nodes, engine=None, **options):
         engine = os.environ.get('BAYESPY_AMD_ENGINE', 'auto')
     gaussian = engine == 'fused+batches+gaussian'
     batches = gaussian or engine == 'fused+batches'
-    if batches:
+    topics = engine == 'fused+topics'
+    if batches or topics:
         engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
+    if kept is not None and not topics \
+            and any(type(p) in v for p in kept for v in OPT_IN_TOPICS.values()):
+        kept = None             # the wide-topic form is kept only where it is asked for
     if kept is not None and not batches \
             and any(type(p) in v for p in kept for v in OPT_IN_BATCHES.values()):
         kept = None             # a mini-batch form is kept only where it is asked for
@@ -180,6 +197,8 @@ def compile_model(nodes, engine=None, **options):
         types = _with_batches(types)
     if gaussian:
         types = _with_gaussian_batches(types)
+    if topics:
+        types = _with_topics(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

@@ -120,10 +120,17 @@ def _batch_multiplier(words, topics, p_word, p_topic):
     return None
 
 
-def _match(nodes, why, multiplier_rule):
+def _narrow_topics(K):
+    if K > LDA_MAX_K:
+        return 'n_topics = %d exceeds the limit of the block (K <= %d)' % (K, LDA_MAX_K)
+    return None
+
+
+def _match(nodes, why, multiplier_rule, label='fused LDA block', topics_rule=_narrow_topics):
     """The roles of the first latent-Dirichlet-allocation structure among ``nodes`` that meets
     every condition of the block, or None; ``multiplier_rule`` says what plate multipliers may
-    be there (a reason, or None)."""
+    be there and ``topics_rule`` what numbers of topics (a reason, or None); ``label`` opens
+    every reason."""
     for words in nodes:
         r = _structure(words)
         if r is None:
@@ -131,8 +138,7 @@ def _match(nodes, why, multiplier_rule):
 
         def no(msg, words=words):
             if why is not None:
-                why.append('fused LDA block, observed node %s: %s'
-                           % (words.name or '<unnamed>', msg))
+                why.append('%s, observed node %s: %s' % (label, words.name or '<unnamed>', msg))
         topics, p_word, p_topic = r['topics'], r['p_word'], r['p_topic']
         g1, g2, idx = r['gate_topic'], r['gate_word'], r['document_indices']
         four = (words, topics, p_word, p_topic)
@@ -165,8 +171,9 @@ def _match(nodes, why, multiplier_rule):
                 or p_word.plates != (K,) or idx.value.shape != (n,) or words.plates != (n,):
             no('plates of p_topic / p_word / indices are not (D,), (K,), (n,)')
             continue
-        if K > LDA_MAX_K:
-            no('n_topics = %d exceeds the limit of the block (K <= %d)' % (K, LDA_MAX_K))
+        bad = topics_rule(K)
+        if bad:
+            no(bad)
             continue
         kids = ((p_topic, [g1]), (g1, [topics]), (topics, [g2]), (p_word, [g2]),
                 (g2, [words]), (words, []))
@@ -492,12 +499,16 @@ class LDAPlan:
     # -- persistence -----------------------------------------------------------------------------------
     _SAVED = ('alpha_theta', 'alpha_beta_t', 'elog_theta', 'elog_beta_t', 'used_theta',
               'used_beta_t', 'Ndk', 'Nvk', 'scal')
+    _KIND = 'lda'           # names the form in a checkpoint
+    _OTHER_KINDS = {'lda': 'the fused LDA block (K <= %d)' % LDA_MAX_K,
+                    'lda_wide': "the wide-topic form of the fused LDA block "
+                                "(engine='fused+topics', K > %d)" % LDA_MAX_K}
 
     def save_state(self, put, nodes, index):
         self._materialize()
         base = 'plans/%d/' % index
         _delta.save(put, base, self._delta)
-        put(base + 'kind', np.array([ord(c) for c in 'lda'], dtype=np.uint8))
+        put(base + 'kind', np.array([ord(c) for c in self._KIND], dtype=np.uint8))
         put(base + 'dims', np.array([self.n, self.D, self.V, self.K], dtype=np.int64))
         put(base + 'flags', np.array([1 if self.has_word_term else 0,
                                       1 if self.labels is not None else 0], dtype=np.int64))
@@ -509,8 +520,12 @@ class LDAPlan:
     def load_state(self, reader, nodes, index):
         self._materialize()
         base = 'plans/%d/' % index
-        if not reader.has(base + 'kind') or bytes(np.asarray(reader.get(base + 'kind'),
-                                                             dtype=np.uint8)) != b'lda':
+        kind = bytes(np.asarray(reader.get(base + 'kind'), dtype=np.uint8)).decode() \
+            if reader.has(base + 'kind') else None
+        if kind != self._KIND:
+            if kind in self._OTHER_KINDS:
+                raise Exception("File holds the state of %s, this model runs on %s"
+                                % (self._OTHER_KINDS[kind], self._OTHER_KINDS[self._KIND]))
             raise Exception("File does not contain the state of the fused LDA block")
         dims = tuple(int(v) for v in reader.get(base + 'dims'))
         if dims != (self.n, self.D, self.V, self.K):

@@ -990,6 +990,31 @@ int32_t vmp_lda_dirichlet_step(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t
 int32_t vmp_lda_dot(vmp_ctx *ctx, int64_t m, const double *a, const double *b, double *ws,
                     double *out);
 
+/* Latent Dirichlet allocation with 65 .. 1024 topics: the wide-topic token pass (details:
+ * bayespy_amd/csrc/vmp_lda_wide.hip, vmp_lda_wide_dev.h).  One wavefront walks a chunk of tokens,
+ * lane j holds the topics j + 64 r in R registers; the Dirichlet rows and dot products are those of
+ * the block above (vmp_lda_dirichlet, vmp_lda_dot), which are general in K.
+ *   vmp_lda_wide_limits (host only): *min_K = 65, *max_K = 1024, *max_chunk = 256.
+ *   vmp_lda_wide_plan (host only): for (n, K) the registers per lane *regs (the smallest of 2, 4, 8,
+ *     16 with 64 * regs >= K), the tokens per chunk *chunk (a function of n alone) and the scratch
+ *     *workspace_doubles of the pass.  K < 65, K > 1024 or n >= 2^31: VMP_ERR_UNSUPPORTED; null
+ *     pointers or negative n: VMP_ERR_INVALID.
+ *   vmp_lda_wide_token_pass: the arguments, outputs, layouts, `phases`, -inf / NaN behaviour and
+ *     error codes of vmp_lda_token_pass, for 65 <= K <= 1024 (other K: VMP_ERR_UNSUPPORTED).  ws:
+ *     vmp_lda_wide_plan's doubles.  No atomics: the bits of every output depend on (inputs, n, K,
+ *     layouts) only. */
+int32_t vmp_lda_wide_limits(int32_t *min_K, int32_t *max_K, int32_t *max_chunk);
+int32_t vmp_lda_wide_plan(int64_t n, int32_t K, int32_t *regs, int32_t *chunk,
+                          int64_t *workspace_doubles);
+int32_t vmp_lda_wide_token_pass(vmp_ctx *ctx, int64_t n, int64_t D, int64_t V, int32_t K,
+                                const int32_t *doc_d, const int32_t *word_d,
+                                const int64_t *doc_off, const int32_t *word_w,
+                                const int32_t *doc_w, const int32_t *pos_w,
+                                const int64_t *word_off, const int32_t *labels,
+                                const double *elog_theta, const double *elog_beta_t,
+                                int32_t phases, double *lse, double *ws, double *Ndk, double *Nvk,
+                                double *scal, const int32_t *orig, double *phi);
+
 /* Bernoulli mixture: the plate pass of the fused block (doc/source/examples/bmm.rst; details:
  * bayespy_amd/csrc/vmp_bmm.hip, vmp_bmm_dev.h).  N rows of D binary observations, K clusters; x is
  * kept as bits, no (N, D, K) or (N, K) array exists.

@@ -19,6 +19,18 @@ parts of the token pass are timed one by one through the ``phases`` argument of
   hbm_fraction            bytes_per_token * tokens / (ms_pass_doc + ms_pass_word) / peak bandwidth
   generic_ms_per_sweep    engine='generic' on the same model (--generic-max-tokens bounds its size)
 
+    python tools/bench_lda.py --tokens 2000000 --documents 20000 --vocabulary 20000 \
+        --topics 256 --engine fused+topics          # the wide-topic form (65 .. 1024 topics)
+
+With more than 64 topics on ``--engine fused+topics`` the table rows are the traffic (a row of 8 K
+bytes is gathered per token and pass; the row indexed by the segment stays in registers), so the JSON
+line also carries
+
+  algorithmic_bytes_per_token   2 * 8 K (one gathered row per pass) + 36 (indices and lse)
+  gb_per_sweep                  algorithmic_bytes_per_token * tokens / 1e9
+  stream_fraction               gb_per_sweep / (ms_pass_doc + ms_pass_word) / 6.3 TB/s, the rate a
+                                streaming kernel reaches on this chip
+
     python tools/bench_lda.py --svi                 # stochastic VI: the mini-batch form of the block
 
 ``--svi`` times whole SVI steps (``observe`` and ``set_value`` of a new batch that lives on the
@@ -44,6 +56,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_BYTES_PER_S = 8.0e12           # MI355X peak HBM3E bandwidth
+STREAM_BYTES_PER_S = 6.3e12        # what a streaming kernel reaches of it
 BYTES_PER_TOKEN = 4 + 4 + 8 + 12 + 8
 
 
@@ -99,21 +112,38 @@ def time_phases(plan, steps):
     return out
 
 
-def run(n, D, V, K, warmup, steps, generic):
+def run(n, D, V, K, warmup, steps, generic, engine=None):
     import torch
     from bayespy_amd.inference.plans.lda import LDAPlan
     rs = np.random.RandomState(12345)
     docs = rs.randint(D, size=n)
     corpus = (rs.zipf(1.2, size=n) - 1) % V
-    Q = build(n, D, V, K, docs, corpus)
+    if engine == 'generic':
+        Q = build(n, D, V, K, docs, corpus, engine='generic')
+        med, best = time_sweeps(Q, warmup, steps)
+        res = dict(tokens=n, documents=D, vocabulary=V, topics=K, engine=engine,
+                   generic_ms_per_sweep=med, generic_ms_per_sweep_min=best,
+                   generic_L=float(Q.L[Q.iter - 1]),
+                   peak_memory_mb=torch.cuda.max_memory_allocated() / 1e6)
+        print(json.dumps(res), flush=True)
+        return res
+    Q = build(n, D, V, K, docs, corpus, engine=engine)
     assert isinstance(Q.plans[0], LDAPlan)
     med, best = time_sweeps(Q, warmup, steps)
     res = dict(tokens=n, documents=D, vocabulary=V, topics=K, ms_per_sweep=med,
                ms_per_sweep_min=best, L=float(Q.L[Q.iter - 1]))
+    if engine is not None:
+        res['engine'] = engine
+        res['plan'] = type(Q.plans[0]).__name__
     res.update(time_phases(Q.plans[0], steps))
     res['bytes_per_token'] = BYTES_PER_TOKEN
     t = (res['ms_pass_doc'] + res['ms_pass_word']) * 1e-3
     res['hbm_fraction'] = BYTES_PER_TOKEN * n / t / HBM_BYTES_PER_S if t > 0 else None
+    if K > 64:
+        alg = 2 * 8 * K + BYTES_PER_TOKEN
+        res['algorithmic_bytes_per_token'] = alg
+        res['gb_per_sweep'] = alg * n / 1e9
+        res['stream_fraction'] = alg * n / t / STREAM_BYTES_PER_S if t > 0 else None
     res['peak_memory_mb'] = torch.cuda.max_memory_allocated() / 1e6
     del Q
     if generic:
@@ -251,7 +281,11 @@ def main():
     ap.add_argument('--tokens', type=int)
     ap.add_argument('--documents', type=int)
     ap.add_argument('--vocabulary', type=int)
-    ap.add_argument('--topics', type=int)
+    ap.add_argument('--topics', type=int,
+                    help='number of topics; above 64 needs --engine fused+topics (or generic)')
+    ap.add_argument('--engine', default=None,
+                    help="engine of the timed VB (default: the default engine; 'fused+topics' for "
+                         "65 .. 1024 topics; 'generic' times the generic engine alone)")
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--generic', action='store_true', help='also time engine="generic"')
@@ -273,7 +307,8 @@ def main():
             run_step_kernel(100000, K, a.warmup, steps)
         return
     if a.tokens:
-        run(a.tokens, a.documents, a.vocabulary, a.topics, a.warmup, a.steps, a.generic)
+        run(a.tokens, a.documents, a.vocabulary, a.topics, a.warmup, a.steps, a.generic,
+            engine=a.engine)
         return
     # the doc example's size, a size the generic engine still holds (its tokens x V fp64 arrays:
     # 2e5 x 2e3 x 8 B = 3.2 GB each), and corpus scale
