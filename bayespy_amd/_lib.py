@@ -239,6 +239,10 @@ SIGNATURES = {
     'vmp_lda_wide_token_pass': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp,
                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                         c_vp, c_vp, c_vp, c_vp]),
+    'vmp_lda_concentration_stats_workspace': (c_i32, [c_i64, c_i64, c_i64, c_i64, P(c_i64)]),
+    'vmp_lda_concentration_stats': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp]),
+    'vmp_lda_prior_fill': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
     'vmp_bmm_limits': (c_i32, [P(c_i32), P(c_i32)]),
     'vmp_bmm_plan': (c_i32, [c_i64, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_bmm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),

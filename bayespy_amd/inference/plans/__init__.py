@@ -10,6 +10,7 @@ from .lssm import LSSMPlan
 from .lssm_masked import MaskedLSSMPlan
 from .lda import LDAPlan, LDASVIPlan
 from .lda_wide import WideLDAPlan
+from .lda_hyper import HyperLDAPlan, WideHyperLDAPlan
 from .bmm import BernoulliMixturePlan, BernoulliMixtureSVIPlan
 from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
@@ -68,6 +69,12 @@ OPT_IN_GAUSSIAN_BATCHES = {DiagGaussianMixturePlan: [DiagGaussianMixtureSVIPlan]
 # class of its own, tried right after that block (which declines K > 64 with a reason).  Everything
 # else is engine='fused'; every other engine value does not try this form and keeps its answer
 OPT_IN_TOPICS = {LDAPlan: [WideLDAPlan]}
+# engine='fused+hyper' / 'fused+topics+hyper': the forms of the LDA block and of its wide-topic form
+# with learnt concentrations (plans/lda_hyper.py), each a plan class of its own, tried right after
+# its form (which declines a Concentration parent with a reason).  'fused+hyper' is engine='fused'
+# plus HyperLDAPlan, 'fused+topics+hyper' is engine='fused+topics' plus both; every other engine
+# value does not try these forms and keeps its answer
+OPT_IN_HYPER = {LDAPlan: [HyperLDAPlan], WideLDAPlan: [WideHyperLDAPlan]}
 
 
 def _with_masked(types):
@@ -89,6 +96,13 @@ def _with_topics(types):
     """``types`` with the plan classes of ``OPT_IN_TOPICS`` inserted after their block (or after
     the opt-in form that stands in its place)."""
     after = {OPT_IN_FORMS.get(P, P): v for P, v in OPT_IN_TOPICS.items()}
+    return [Q for P in types for Q in [P] + after.get(P, [])]
+
+
+def _with_hyper(types):
+    """``types`` with the plan classes of ``OPT_IN_HYPER`` inserted after their form (or after the
+    opt-in form that stands in its place), where that form is among ``types``."""
+    after = {OPT_IN_FORMS.get(P, P): v for P, v in OPT_IN_HYPER.items()}
     return [Q for P in types for Q in [P] + after.get(P, [])]
 
 
@@ -125,6 +139,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or type(p) in OPT_IN_LAST or type(p) in OPT_IN_COUNTS
                                  or type(p) in OPT_IN_VECTORS or type(p) in OPT_IN_TRIALS
                                  or any(type(p) in v for v in OPT_IN_TOPICS.values())
+                                 or any(type(p) in v for v in OPT_IN_HYPER.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -162,13 +177,17 @@ def compile_model(nodes, engine=None, **options):
         engine = os.environ.get('BAYESPY_AMD_ENGINE', 'auto')
     gaussian = engine == 'fused+batches+gaussian'
     batches = gaussian or engine == 'fused+batches'
-    topics = engine == 'fused+topics'
-    if batches or topics:
+    hyper = engine in ('fused+hyper', 'fused+topics+hyper')
+    topics = engine in ('fused+topics', 'fused+topics+hyper')
+    if batches or topics or hyper:
         engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
     if kept is not None and not topics \
             and any(type(p) in v for p in kept for v in OPT_IN_TOPICS.values()):
         kept = None             # the wide-topic form is kept only where it is asked for
+    if kept is not None and not hyper \
+            and any(type(p) in v for p in kept for v in OPT_IN_HYPER.values()):
+        kept = None             # a form with learnt concentrations is kept only where it is asked for
     if kept is not None and not batches \
             and any(type(p) in v for p in kept for v in OPT_IN_BATCHES.values()):
         kept = None             # a mini-batch form is kept only where it is asked for
@@ -199,6 +218,8 @@ def compile_model(nodes, engine=None, **options):
         types = _with_gaussian_batches(types)
     if topics:
         types = _with_topics(types)
+    if hyper:
+        types = _with_hyper(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

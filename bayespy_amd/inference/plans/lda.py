@@ -126,10 +126,21 @@ def _narrow_topics(K):
     return None
 
 
-def _match(nodes, why, multiplier_rule, label='fused LDA block', topics_rule=_narrow_topics):
+def _constant_parents(p_topic, p_word, nodes):
+    """(reason or None, further roles): both concentrations are constants."""
+    bad = [n for n in (p_topic, p_word) if not isinstance(n.parents[0], Constant)]
+    if bad:
+        return ('the concentration of %s is a node (%s), not a constant'
+                % (bad[0].name, type(bad[0].parents[0]).__name__)), None
+    return None, {}
+
+
+def _match(nodes, why, multiplier_rule, label='fused LDA block', topics_rule=_narrow_topics,
+           parent_rule=_constant_parents):
     """The roles of the first latent-Dirichlet-allocation structure among ``nodes`` that meets
     every condition of the block, or None; ``multiplier_rule`` says what plate multipliers may
-    be there and ``topics_rule`` what numbers of topics (a reason, or None); ``label`` opens
+    be there, ``topics_rule`` what numbers of topics (a reason, or None) and ``parent_rule`` what
+    parents the Dirichlets may have (a reason or None, and the roles it adds); ``label`` opens
     every reason."""
     for words in nodes:
         r = _structure(words)
@@ -157,10 +168,9 @@ def _match(nodes, why, multiplier_rule, label='fused LDA block', topics_rule=_na
         if words._mask is not True:
             no('it has a mask')
             continue
-        bad = [n for n in (p_topic, p_word) if not isinstance(n.parents[0], Constant)]
+        bad, extra = parent_rule(p_topic, p_word, nodes)
         if bad:
-            no('the concentration of %s is a node (%s), not a constant'
-               % (bad[0].name, type(bad[0].parents[0]).__name__))
+            no(bad)
             continue
         if len(topics.plates) != 1 or idx.value.ndim != 1:
             no('it needs one token plate axis, topics has plates %s and the indices have '
@@ -191,7 +201,7 @@ def _match(nodes, why, multiplier_rule, label='fused LDA block', topics_rule=_na
                for n in (p_topic, p_word)):
             no('a Dirichlet is initialised from parameters')
             continue
-        return r
+        return dict(r, **extra)
     return None
 
 
@@ -330,6 +340,10 @@ class LDAPlan:
         self.orig = order.to(i32)
         self._layout_stale = False
 
+    def _prior_table(self, node, shape):
+        """The concentration of a Dirichlet at set-up, broadcast to ``shape`` (host)."""
+        return prior_table(node, shape)
+
     def _init_dirichlet(self, node, prior):
         """Initial <log> table of a Dirichlet: from the prior (device), or the log of a value /
         of a draw from the prior (host, set-up only)."""
@@ -359,8 +373,8 @@ class LDAPlan:
         rt.sync_stream()
         self.group, self.chunk, wsd = k.plan(n, K)
         self._build_layouts()
-        pt = prior_table(self.p_topic, (D, K))
-        pw = prior_table(self.p_word, (K, V))
+        pt = self._prior_table(self.p_topic, (D, K))
+        pw = self._prior_table(self.p_word, (K, V))
         up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order='C')).to(rt.device)  # noqa: E731
         self.prior_theta, self.prior_beta_t = up(pt), up(pw.T)
         self.alpha_theta, self.alpha_beta_t = rt.empty(D, K), rt.empty(V, K)
@@ -502,7 +516,12 @@ class LDAPlan:
     _KIND = 'lda'           # names the form in a checkpoint
     _OTHER_KINDS = {'lda': 'the fused LDA block (K <= %d)' % LDA_MAX_K,
                     'lda_wide': "the wide-topic form of the fused LDA block "
-                                "(engine='fused+topics', K > %d)" % LDA_MAX_K}
+                                "(engine='fused+topics', K > %d)" % LDA_MAX_K,
+                    'lda_hyper': "the fused LDA block with learnt concentrations "
+                                 "(engine='fused+hyper', K <= %d)" % LDA_MAX_K,
+                    'lda_wide_hyper': "the wide-topic form of the fused LDA block with learnt "
+                                      "concentrations (engine='fused+topics+hyper', K > %d)"
+                                      % LDA_MAX_K}
 
     def save_state(self, put, nodes, index):
         self._materialize()

@@ -1015,6 +1015,28 @@ int32_t vmp_lda_wide_token_pass(vmp_ctx *ctx, int64_t n, int64_t D, int64_t V, i
                                 int32_t phases, double *lse, double *ws, double *Ndk, double *Nvk,
                                 double *scal, const int32_t *orig, double *phi);
 
+/* Latent Dirichlet allocation with a learnt concentration: the plate-sized step between the
+ * Dirichlet tables of the block and vmp_ml_concentration (details: bayespy_amd/csrc/vmp_lda_hyper.hip,
+ * vmp_lda_hyper_dev.h).  Tables in the stride convention of vmp_lda_dirichlet, in one of two forms:
+ * row-major (col_stride == 1, row_stride == cols, cols <= 1024) or transposed (row_stride == 1,
+ * col_stride == rows, rows <= 1024); other strides: VMP_ERR_UNSUPPORTED.
+ *   vmp_lda_concentration_stats: one pass over alpha and elog leaves S[c] = sum_rows elog[r, c]
+ *     (cols doubles; the message m0 of the Dirichlets to their concentration, m1 = rows) and
+ *     *qterm = sum_rows ( lgamma(sum_c alpha_rc) - sum_c lgamma(alpha_rc) + sum_c (alpha_rc - 1)
+ *     elog_rc ), the part of the Dirichlets' lower-bound term that does not depend on the prior.
+ *     No atomics: chunk partials and a combine in a fixed order, the bits of both outputs depend on
+ *     the inputs and the shape only.  rows == 0: zeros.  A NaN in a table reaches *qterm (and S where
+ *     it stands in elog).  Null / negative arguments: VMP_ERR_INVALID.
+ *   vmp_lda_concentration_stats_workspace (host only): the doubles of `ws` that call needs.
+ *   vmp_lda_prior_fill: prior[r * row_stride + c * col_stride] = a[c] for every row r (any strides). */
+int32_t vmp_lda_concentration_stats_workspace(int64_t rows, int64_t cols, int64_t row_stride,
+                                              int64_t col_stride, int64_t *workspace_doubles);
+int32_t vmp_lda_concentration_stats(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t row_stride,
+                                    int64_t col_stride, const double *alpha, const double *elog,
+                                    double *ws, double *S, double *qterm);
+int32_t vmp_lda_prior_fill(vmp_ctx *ctx, int64_t rows, int64_t cols, int64_t row_stride,
+                           int64_t col_stride, const double *a, double *prior);
+
 /* Bernoulli mixture: the plate pass of the fused block (doc/source/examples/bmm.rst; details:
  * bayespy_amd/csrc/vmp_bmm.hip, vmp_bmm_dev.h).  N rows of D binary observations, K clusters; x is
  * kept as bits, no (N, D, K) or (N, K) array exists.

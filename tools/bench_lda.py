@@ -22,6 +22,10 @@ parts of the token pass are timed one by one through the ``phases`` argument of
     python tools/bench_lda.py --tokens 2000000 --documents 20000 --vocabulary 20000 \
         --topics 256 --engine fused+topics          # the wide-topic form (65 .. 1024 topics)
 
+``--concentrations`` times the model with both concentrations learnt (DirichletConcentration
+parents, ``engine='fused+topics+hyper'``) beside the same model with constant concentrations in the
+same process, and the statistics pass, the prior fill and a whole concentration update alone.
+
 With more than 64 topics on ``--engine fused+topics`` the table rows are the traffic (a row of 8 K
 bytes is gathered per token and pass; the row indexed by the segment stays in registers), so the JSON
 line also carries
@@ -110,6 +114,82 @@ def time_phases(plan, steps):
                 ms.append(a.elapsed_time(b))
         out[name] = float(np.median(ms))
     return out
+
+
+def build_learnt(n, D, V, K, docs, corpus, engine):
+    """The model of ``build`` with both concentrations learnt (DirichletConcentration parents)."""
+    from bayespy_amd import nodes
+    from bayespy_amd.inference import VB
+    a = nodes.DirichletConcentration(K, name='conc_topic')
+    b = nodes.DirichletConcentration(V, name='conc_word')
+    p_topic = nodes.Dirichlet(a, plates=(D,), name='p_topic')
+    p_word = nodes.Dirichlet(b, plates=(K,), name='p_word')
+    topics = nodes.Categorical(nodes.Gate(docs, p_topic), plates=(n,), name='topics')
+    words = nodes.Categorical(nodes.Gate(topics, p_word), name='words')
+    words.observe(corpus)
+    np.random.seed(1)
+    p_topic.initialize_from_random()
+    p_word.initialize_from_random()
+    Q = VB(words, topics, p_word, p_topic, a, b, engine=engine)
+    Q.ignore_bound_checks = True
+    return Q
+
+
+def time_calls(fn, steps):
+    """Median milliseconds of ``fn()`` between two events, after two untimed calls."""
+    import torch
+    ms = []
+    for i in range(steps + 2):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(torch.cuda.current_stream())
+        fn()
+        b.record(torch.cuda.current_stream())
+        b.synchronize()
+        if i >= 2:
+            ms.append(a.elapsed_time(b))
+    return float(np.median(ms))
+
+
+def run_concentrations(n, D, V, K, warmup, steps):
+    """Sweeps with both concentrations learnt beside the same tree with constant concentrations,
+    and the statistics pass alone against the two table reads it must make."""
+    import torch
+    rs = np.random.RandomState(12345)
+    docs = rs.randint(D, size=n)
+    corpus = (rs.zipf(1.2, size=n) - 1) % V
+    engine = 'fused+topics+hyper'
+    res = dict(mode='concentrations', tokens=n, documents=D, vocabulary=V, topics=K, engine=engine)
+    Qc = build(n, D, V, K, docs, corpus, engine='fused+topics')
+    res['constant_plan'] = type(Qc.plans[0]).__name__
+    res['constant_ms_per_sweep'], res['constant_ms_per_sweep_min'] = time_sweeps(Qc, warmup, steps)
+    res.update({'constant_' + k: v for k, v in time_phases(Qc.plans[0], steps).items()})
+    del Qc
+    torch.cuda.empty_cache()
+    Q = build_learnt(n, D, V, K, docs, corpus, engine)
+    plan = Q.plans[0]
+    res['plan'] = type(plan).__name__
+    res['ms_per_sweep'], res['ms_per_sweep_min'] = time_sweeps(Q, warmup, steps)
+    res['L'] = float(Q.L[Q.iter - 1])
+    res.update(time_phases(plan, steps))
+    rt, k = plan.rt, plan.kernels
+    for key, name in (('conc_topic', 'topic'), ('conc_word', 'word')):
+        rows, cols, r_s, c_s, alpha, elog, prior = plan._table(key)
+        h = plan.hyper[key]
+        rt.sync_stream()
+        ms = time_calls(lambda: k.stats(rows, cols, r_s, c_s, alpha, elog, h['ws'], h['S'],
+                                        h['qterm']), steps)
+        res['ms_stats_' + name] = ms
+        res['stats_%s_gb_per_s' % name] = 2 * 8.0 * rows * cols / (ms * 1e-3) / 1e9
+        res['ms_fill_' + name] = time_calls(
+            lambda: k.prior_fill(rows, cols, r_s, c_s, h['a'], prior), steps)
+        node = plan.roles[key]
+        res['ms_update_' + name] = time_calls(lambda: plan.update(node), steps)
+        res['fixed_point_steps_' + name] = int(h['status'][2].item())
+    t = res['ms_pass_doc'] + res['ms_pass_word']
+    res['stats_over_token_pass'] = (res['ms_stats_topic'] + res['ms_stats_word']) / t
+    res['peak_memory_mb'] = torch.cuda.max_memory_allocated() / 1e6
+    print(json.dumps(res), flush=True)
+    return res
 
 
 def run(n, D, V, K, warmup, steps, generic, engine=None):
@@ -291,7 +371,18 @@ def main():
     ap.add_argument('--generic', action='store_true', help='also time engine="generic"')
     ap.add_argument('--generic-max-tokens', type=int, default=200000,
                     help='largest standard size at which the generic engine is timed too')
+    ap.add_argument('--concentrations', action='store_true',
+                    help="both concentrations learnt (engine 'fused+topics+hyper') beside the same "
+                         "model with constant concentrations; without sizes: 2e6 tokens, D = V = 2e4, "
+                         "K = 64 and 256")
     a = ap.parse_args()
+    if a.concentrations:
+        if a.tokens:
+            run_concentrations(a.tokens, a.documents, a.vocabulary, a.topics, a.warmup, a.steps)
+            return
+        for K in (64, 256):
+            run_concentrations(2000000, 20000, 20000, K, a.warmup, a.steps)
+        return
     if a.svi:
         steps = max(a.steps, 20)
         if a.tokens:
