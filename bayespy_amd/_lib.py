@@ -223,6 +223,10 @@ SIGNATURES = {
                                      c_vp, c_vp]),
     'vmp_chain_pair_stats_limits': (c_i32, [c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'vmp_chain_pair_stats': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    'vmp_chain_input_stats_limits': (c_i32, [c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                             c_vp]),
+    'vmp_chain_input_stats': (c_i32, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp, c_i64]),
     'vmp_lda_limits': (c_i32, [P(c_i32), P(c_i32)]),
     'vmp_lda_plan': (c_i32, [c_i64, c_i32, P(c_i32), P(c_i32), P(c_i64)]),
     'vmp_lda_token_pass': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -185,6 +185,10 @@ class GenericPlan(GraphIteration):
         if tv and any(getattr(n, '_shard_axis', None) is not None for n in self.all):
             raise NotImplementedError('Gaussian Markov chains with time-varying dynamics (%s) in a '
                                       'model sharded over ranks are not built' % ', '.join(tv))
+        driven = [n.name for n in self.all if getattr(n, 'K_inputs', 0)]
+        if driven and any(getattr(n, '_shard_axis', None) is not None for n in self.all):
+            raise NotImplementedError('Gaussian Markov chains with input signals (%s) in a model '
+                                      'sharded over ranks are not built' % ', '.join(driven))
         self._const_cache = {}
         self._masks_ready = False
         self._graph_init()

@@ -190,6 +190,10 @@ class LSSMPlan:
                       'one plate axis is needed)' % (type(X).__name__, tuple(X.plates)))
                 continue
             D, T = X.D, X.N
+            if getattr(X, 'K_inputs', 0):
+                no(Y, 'the chain %s has input signals (K = %d): input signals go through the generic '
+                      'engine' % (X.name or 'X', X.K_inputs))
+                continue
             mu, Lam, A, nu = X.parents
             if getattr(X, 'time_varying', False):
                 no(Y, 'the chain %s has a time plate (N-1 = %d) on its dynamics A or its innovation '

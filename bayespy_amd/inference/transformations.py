@@ -253,7 +253,8 @@ class RotateGaussianMarkovChain:
         self.A_rotator = args[0]
         mu, Lam, A, nu = X.parents[:4]
         if len(X.parents) > 4:
-            raise NotImplementedError('input signals of the chain are not built')
+            raise NotImplementedError('RotateGaussianMarkovChain: the chain %s has input signals '
+                                      '(a fifth parent); its rotation is not built' % X.name)
         if getattr(X, 'time_varying', False):
             raise NotImplementedError('RotateGaussianMarkovChain: a chain with a time plate on its '
                                       'dynamics A or its innovation precision nu is not built')

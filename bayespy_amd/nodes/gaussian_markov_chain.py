@@ -9,7 +9,10 @@ shape (D,) whose LAST plate (D) indexes the rows of A; ``nu`` has last plate D. 
 change at every transition: a second-to-last plate of N-1 on ``A`` (plates (..., N-1, D), or an
 (..., N-1, D, D) array) or on ``nu`` (plates (..., N-1, D)) is the time axis, a unit or missing
 one means constant dynamics; ``n`` is inferred from such a plate when it is not given
-(reference :768-778, :839-857).  Input signals (``inputs=``) are not built.  A chain used as a
+(reference :768-778, :839-857).  With input signals (``inputs=``: a Gaussian-like node or an array
+of shape (K,) with plates (..., N-1) or (..., 1)) the chain is driven,
+x_n ~ N(A x_{n-1} + B u_n, diag(nu)^-1): ``A`` then has shape (D+K,) and holds [A | B] row by row, and
+the inputs are the fifth parent (reference :821-870).  A chain used as a
 Gaussian parent (e.g. of SumMultiply) is seen through :class:`MarkovChainToGaussian`,
 which turns the time axis into the last plate (reference :1988-2098).
 """
@@ -22,10 +25,24 @@ from ..utils.shapes import broadcasted_shape
 class GaussianMarkovChain(Stochastic):
 
     def __init__(self, mu, Lambda, A, nu, n=None, inputs=None, plates=None, name=None):
+        if isinstance(inputs, GaussianMarkovChain):
+            inputs = inputs.as_gaussian()
+        more = () if inputs is None else (inputs,)
+        super().__init__(mu, Lambda, A, nu, *more, plates=(), dims=((), (), ()), name=name)
+        mu_n, L_n, A_n, nu_n = self.parents[:4]
+        # the input signals: K-dimensional, their last plate is the time axis (:821-838, :887-889)
+        K, inpl = 0, None
         if inputs is not None:
-            raise NotImplementedError('input signals of GaussianMarkovChain are not built')
-        super().__init__(mu, Lambda, A, nu, plates=(), dims=((), (), ()), name=name)
-        mu_n, L_n, A_n, nu_n = self.parents
+            u_n = self.parents[4]
+            if isinstance(u_n, Constant):
+                if u_n.value.ndim < 1:
+                    raise ValueError("Input signals have wrong dimensionality")
+                K, inpl = u_n.value.shape[-1], u_n.value.shape[:-1]
+            else:
+                if len(u_n.dims) < 2 or len(u_n.dims[0]) != 1 \
+                        or tuple(u_n.dims[1]) != tuple(u_n.dims[0]) * 2:
+                    raise ValueError("Input signals have wrong dimensionality")
+                K, inpl = u_n.dims[0][0], tuple(u_n.plates)
         if isinstance(L_n, Constant):
             if L_n.value.ndim < 2 or L_n.value.shape[-1] != L_n.value.shape[-2]:
                 raise Exception("Initial state parameters have wrong dimensionality")
@@ -41,19 +58,20 @@ class GaussianMarkovChain(Stochastic):
                 raise Exception("Initial state parameters have wrong dimensionality")
             mupl = mu_n.plates
         if isinstance(A_n, Constant):
-            if A_n.value.shape[-2:] != (D, D):
-                raise Exception("Dynamics matrix has wrong dimensionality")
+            if A_n.value.shape[-2:] != (D, D + K):
+                raise _wrong_dynamics(A_n.value.shape[-1:] if A_n.value.ndim else (), D, K)
             Apl = A_n.value.shape[:-1]
         else:
-            if A_n.dims[0] != (D,):
-                raise Exception("Dynamics matrix has wrong dimensionality")
+            if A_n.dims[0] != (D + K,):
+                raise _wrong_dynamics(A_n.dims[0], D, K)
             Apl = A_n.plates
         nupl = nu_n.value.shape if isinstance(nu_n, Constant) else nu_n.plates
         for pl in (Apl, nupl):
             if len(pl) == 0 or pl[-1] != D:
                 raise Exception("Dynamics matrix should have a last plate equal to the "
                                 "dimensionality of the system.")
-        # time instances the parents give (:839-857): the second-to-last plate of A and nu
+        # time instances the parents give (:834-857): the second-to-last plate of A and nu, the
+        # last plate of the inputs
         n_parents = 1
         for pl in (Apl, nupl):
             if len(pl) >= 2 and pl[-2] != 1:
@@ -61,6 +79,11 @@ class GaussianMarkovChain(Stochastic):
                     raise Exception("Plates of parents are giving different number of time "
                                     "instances")
                 n_parents = pl[-2]
+        n_dynamics = n_parents
+        if inpl is not None and len(inpl) >= 1 and inpl[-1] != 1:
+            if n_parents != 1 and inpl[-1] != n_parents:
+                raise Exception("Plates of parents are giving different number of time instances")
+            n_parents = inpl[-1]
         if n is None:
             if n_parents == 1:
                 raise Exception("The number of time instances could not be determined "
@@ -71,10 +94,13 @@ class GaussianMarkovChain(Stochastic):
                             "of parents: %d != %d+1" % (n, n_parents))
         self.N, self.D = int(n), int(D)
         # the dynamics or the innovation precision change along the chain
-        self.time_varying = n_parents != 1
+        self.time_varying = n_dynamics != 1
+        # dimensionality of the input signals (0: the chain is not driven)
+        self.K_inputs = int(K)
         self.dims = ((self.N, D), (self.N, D, D), (self.N - 1, D, D))
         given = tuple(plates) if plates is not None else ()
-        self.plates = broadcasted_shape(given, mupl, Lpl, Apl[:-2], nupl[:-2])
+        self.plates = broadcasted_shape(given, mupl, Lpl, Apl[:-2], nupl[:-2],
+                                        *(() if inpl is None else (inpl[:-1],)))
         if plates is not None and self.plates != given:
             raise ValueError('Plates of the parents do not broadcast to plates %s' % (given,))
 
@@ -93,6 +119,19 @@ class GaussianMarkovChain(Stochastic):
         if not hasattr(self, '_as_gaussian'):
             self._as_gaussian = MarkovChainToGaussian(self)
         return self._as_gaussian
+
+
+def _wrong_dynamics(row, D, K):
+    """The reference's error for a dynamics matrix whose rows are not D + K long (:873-874).  A
+    plain D-column matrix next to input signals is the one form that reads as a request -- inputs
+    whose gain B is neither given nor learned -- so it is refused as not built, and told what the
+    constructor takes instead; the text begins with the reference's."""
+    if K and tuple(row) == (D,):
+        return NotImplementedError(
+            "Dynamics matrix has wrong dimensionality: input signals of dimension %d without their "
+            "gain are not built; give [A | B] row by row, %d + %d columns, as the dynamics matrix"
+            % (K, D, K))
+    return Exception("Dynamics matrix has wrong dimensionality")
 
 
 class MarkovChainToGaussian(Node):

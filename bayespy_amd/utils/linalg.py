@@ -260,3 +260,49 @@ def chain_pair_stats(x):
         rt.ctx, ny, N, D, ptr(x.t), ptr(Sxx.t), ptr(Sxp.t), ptr(work.t), nwork))
     PAIR_STATS_LAUNCHES[0] += 1
     return Sxx, Sxp
+
+
+def chain_input_stats_limits(ny=0, zrows=1, N=2, D=1, K=1):
+    """(largest state dimension, largest input dimension ``vmp_chain_input_stats`` has an instance
+    for, whether the tune key ``chain_input_stats`` leaves it on, doubles of scratch the call needs
+    for (ny, zrows, N, D, K))."""
+    rt = get_runtime()
+    max_d, max_k, on = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    work = ctypes.c_int64(0)
+    rc = rt.lib.vmp_chain_input_stats_limits(int(ny), int(zrows), int(N), int(D), int(K),
+                                             ctypes.byref(max_d), ctypes.byref(max_k),
+                                             ctypes.byref(on), ctypes.byref(work))
+    if rc not in (_lib.VMP_OK, _lib.VMP_ERR_UNSUPPORTED):
+        rt.check(rc)
+    return int(max_d.value), int(max_k.value), bool(on.value), int(work.value)
+
+
+# calls of vmp_chain_input_stats made by this process (each is the two launches of the entry point)
+INPUT_STATS_LAUNCHES = [0]
+
+
+def chain_input_stats(x, z, with_zz=True):
+    """Sums over the sequences of the outer products of a driven chain's means with the means of its
+    inputs: x (..., N, D), z (..., N-1, K) with the plates of ``x`` or none ->
+    (sum_b x_{t+1} z_t^T (N-1, D, K), sum_b x_t z_t^T (N-1, D, K), sum_b z_t z_t^T (N-1, K, K) or
+    None without ``with_zz``).  One read of ``x`` and ``z`` (``vmp_chain_input_stats``), the same
+    bits on every call."""
+    rt = get_runtime()
+    x, z = contiguous(asdarray(x)), contiguous(asdarray(z))
+    N, D, K = x.shape[-2], x.shape[-1], z.shape[-1]
+    ny = int(np.prod(x.shape[:-2])) if x.ndim > 2 else 1
+    zrows = int(np.prod(z.shape[:-2])) if z.ndim > 2 else 1
+    if z.shape[-2] != N - 1 or zrows not in (1, ny):
+        raise ValueError('inputs of shape %s do not match states of shape %s' % (z.shape, x.shape))
+    _, _, _, nwork = chain_input_stats_limits(ny, zrows, N, D, K)
+    Snz = DArray.empty((N - 1, D, K))
+    Spz = DArray.empty((N - 1, D, K))
+    Szz = DArray.empty((N - 1, K, K)) if with_zz else None
+    work = DArray.empty((max(nwork, 1),))
+    rt.sync_stream()
+    rt.note_reads([x, z])
+    rt.check(rt.lib.vmp_chain_input_stats(
+        rt.ctx, ny, zrows, N, D, K, ptr(x.t), ptr(z.t), ptr(Snz.t), ptr(Spz.t),
+        ptr(Szz.t) if with_zz else None, ptr(work.t), nwork))
+    INPUT_STATS_LAUNCHES[0] += 1
+    return Snz, Spz, Szz

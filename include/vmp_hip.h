@@ -925,6 +925,26 @@ int32_t vmp_chain_pair_stats_limits(int64_t ny, int32_t N, int32_t D, int32_t *m
 int32_t vmp_chain_pair_stats(vmp_ctx *ctx, int64_t ny, int32_t N, int32_t D, const double *x,
                              double *Sxx, double *Sxp, double *work, int64_t work_doubles);
 
+/* Plate sums of the input cross terms in a driven Gaussian Markov chain's messages to [A | B] and nu
+ * shared by ny sequences (gaussian_markov_chain.py:485-498; details: bayespy_amd/csrc/vmp_chain_in.hip).
+ *   vmp_chain_input_stats: x (ny, N, D) and z (zrows, N-1, K) row-major, zrows = ny or 1 (1: every
+ *     sequence has the same inputs)  ->  Snz (N-1, D, K) = sum_b x_{b,t+1} z_{b,t}^T,
+ *     Spz (N-1, D, K) = sum_b x_{b,t} z_{b,t}^T  and, unless Szz is NULL,
+ *     Szz (N-1, K, K) = sum_b z_{b,t} z_{b,t}^T.  x and z are read once; no atomics: two calls on the
+ *     same input give the same bits.  ny = 0 is legal (zeros).  `work`: scratch of at least the
+ *     `work_doubles` the limits query reports for (ny, zrows, N, D, K).
+ *     D or K above the limit: VMP_ERR_UNSUPPORTED; null / negative arguments, zrows not in {1, ny},
+ *     N < 2 or a short workspace: VMP_ERR_INVALID.
+ *   vmp_chain_input_stats_limits (host only): *max_d, *max_k = the largest D and K with an instance
+ *     (16, 16), *enabled = the tune key "chain_input_stats" (default 1; 0 keeps callers on the
+ *     general operations), *work_doubles = the scratch the call needs. */
+int32_t vmp_chain_input_stats_limits(int64_t ny, int64_t zrows, int32_t N, int32_t D, int32_t K,
+                                     int32_t *max_d, int32_t *max_k, int32_t *enabled,
+                                     int64_t *work_doubles);
+int32_t vmp_chain_input_stats(vmp_ctx *ctx, int64_t ny, int64_t zrows, int32_t N, int32_t D,
+                              int32_t K, const double *x, const double *z, double *Snz,
+                              double *Spz, double *Szz, double *work, int64_t work_doubles);
+
 /* Latent Dirichlet allocation: the token pass and the Dirichlet rows of the fused block
  * (doc/source/examples/lda.rst; details: bayespy_amd/csrc/vmp_lda.hip, vmp_lda_dev.h).  n tokens, D
  * documents, V vocabulary entries, K topics; no tokens x K, tokens x V or tokens x D array exists.
