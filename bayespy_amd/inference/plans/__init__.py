@@ -14,6 +14,7 @@ from .lda_hyper import HyperLDAPlan, WideHyperLDAPlan
 from .bmm import BernoulliMixturePlan, BernoulliMixtureSVIPlan
 from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
+from .hmm_wide import WideHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
 from .dgmm_svi import DiagGaussianMixtureSVIPlan, MaskedDiagGaussianMixtureSVIPlan
@@ -75,6 +76,11 @@ OPT_IN_TOPICS = {LDAPlan: [WideLDAPlan]}
 # plus HyperLDAPlan, 'fused+topics+hyper' is engine='fused+topics' plus both; every other engine
 # value does not try these forms and keeps its answer
 OPT_IN_HYPER = {LDAPlan: [HyperLDAPlan], WideLDAPlan: [WideHyperLDAPlan]}
+# engine='fused+emissions': the form of the HMM block for Gaussian emissions of 9 to 32 dimensions
+# (plans/hmm_wide.py), a plan class of its own, tried right after that block (which declines D > 8
+# with a reason).  Everything else is engine='fused'; every other engine value does not try this
+# form and keeps its answer; it is not combined with the other '+' suffixes
+OPT_IN_WIDE_EMISSIONS = {HMMPlan: [WideHMMPlan]}
 
 
 def _with_masked(types):
@@ -97,6 +103,11 @@ def _with_topics(types):
     the opt-in form that stands in its place)."""
     after = {OPT_IN_FORMS.get(P, P): v for P, v in OPT_IN_TOPICS.items()}
     return [Q for P in types for Q in [P] + after.get(P, [])]
+
+
+def _with_wide_emissions(types):
+    """``types`` with the plan classes of ``OPT_IN_WIDE_EMISSIONS`` inserted after their block."""
+    return [Q for P in types for Q in [P] + OPT_IN_WIDE_EMISSIONS.get(P, [])]
 
 
 def _with_hyper(types):
@@ -140,6 +151,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or type(p) in OPT_IN_VECTORS or type(p) in OPT_IN_TRIALS
                                  or any(type(p) in v for v in OPT_IN_TOPICS.values())
                                  or any(type(p) in v for v in OPT_IN_HYPER.values())
+                                 or any(type(p) in v for v in OPT_IN_WIDE_EMISSIONS.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -179,12 +191,16 @@ def compile_model(nodes, engine=None, **options):
     batches = gaussian or engine == 'fused+batches'
     hyper = engine in ('fused+hyper', 'fused+topics+hyper')
     topics = engine in ('fused+topics', 'fused+topics+hyper')
-    if batches or topics or hyper:
+    emissions = engine == 'fused+emissions'
+    if batches or topics or hyper or emissions:
         engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
     if kept is not None and not topics \
             and any(type(p) in v for p in kept for v in OPT_IN_TOPICS.values()):
         kept = None             # the wide-topic form is kept only where it is asked for
+    if kept is not None and not emissions \
+            and any(type(p) in v for p in kept for v in OPT_IN_WIDE_EMISSIONS.values()):
+        kept = None             # the wide-emission form is kept only where it is asked for
     if kept is not None and not hyper \
             and any(type(p) in v for p in kept for v in OPT_IN_HYPER.values()):
         kept = None             # a form with learnt concentrations is kept only where it is asked for
@@ -220,6 +236,8 @@ def compile_model(nodes, engine=None, **options):
         types = _with_topics(types)
     if hyper:
         types = _with_hyper(types)
+    if emissions:
+        types = _with_wide_emissions(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

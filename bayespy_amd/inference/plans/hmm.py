@@ -59,7 +59,9 @@ from ...nodes.mixture import Mixture
 from .gmm import GMMKernels
 
 _LIMITS = []
-_KINDS = {'hmm': 'Gaussian', 'hmm_cat': 'categorical'}      # checkpoint kind -> emission family
+# checkpoint kind -> emission family (and form)
+_KINDS = {'hmm': 'Gaussian', 'hmm_cat': 'categorical',
+          'hmm_wide': 'Gaussian (the wide form, 9 <= D <= 32)'}
 
 
 def hmm_limits():
@@ -140,7 +142,21 @@ def _takes_mask(Y):
     return Y._mask is True or _mask_shape(Y._mask) == tuple(Y.plates)
 
 
-def _match(nodes, why):
+LABEL = 'fused hidden-Markov-model block'
+
+
+def _narrow_dims(D, K):
+    """What the pass of this block takes (a reason, or None)."""
+    max_K, max_D = hmm_limits()
+    if K > max_K or D > max_D:
+        return ('D = %d, K = %d exceed the limits of the block (D <= %d, K <= %d)'
+                % (D, K, max_D, max_K))
+    return None
+
+
+def _match(nodes, why, label=LABEL, dims_rule=_narrow_dims):
+    """``dims_rule`` says what (D, K) the form takes (a reason, or None); ``label`` opens every
+    reason (plans/hmm_wide.py has its own of both)."""
     for Y in nodes:
         if not isinstance(Y, Mixture) or not isinstance(Y.parents[0],
                                                         CategoricalMarkovChainToCategorical):
@@ -148,8 +164,7 @@ def _match(nodes, why):
 
         def no(msg, Y=Y):
             if why is not None:
-                why.append('fused hidden-Markov-model block, observed node %s: %s'
-                           % (Y.name or '<unnamed>', msg))
+                why.append('%s, observed node %s: %s' % (label, Y.name or '<unnamed>', msg))
         if Y.node_class is not Gaussian:
             no('the mixed distribution is %s, not Gaussian'
                % getattr(Y.node_class, '__name__', Y.node_class))
@@ -207,10 +222,9 @@ def _match(nodes, why):
             no('it needs plates (T,) or (B, T), Y has plates %s and Z has plates %s'
                % (Y.plates, Z.plates))
             continue
-        max_K, max_D = hmm_limits()
-        if K > max_K or D > max_D:
-            no('D = %d, K = %d exceed the limits of the block (D <= %d, K <= %d)'
-               % (D, K, max_D, max_K))
+        bad = dims_rule(D, K)
+        if bad:
+            no(bad)
             continue
         if learned:
             if any(any(m != 1 for m in n.plates_multiplier) for n in (mu, Lam)) \

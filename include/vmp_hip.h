@@ -1291,6 +1291,40 @@ int32_t vmp_hmm_fused_pass_masked(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D,
                                   double *z0sum, double *xisum, double *Tstat, double *scal,
                                   double *gamma, double *z0, double *zz);
 
+/* The same model with up to 32 dimensions: the wide-emission pass (details:
+ * bayespy_amd/csrc/vmp_hmm_wide.hip, vmp_hmm_wide_dev.h).  vmp_hmm_fused_pass forms the emission
+ * term inside the chain from NF = D (D + 1) / 2 + D + 1 features held in LDS, which stops at
+ * D = 8.  Here three kernels share the work: the emission table E[(b, t), k] = C_k . phi(y_bt)
+ * and the statistics Tstat = Gamma^T [1, y, y y^T] are plate-parallel products on the fp64 matrix
+ * cores, and the chain kernel keeps only the recursion (the lane mapping, the log-domain form and
+ * the order of the additions of vmp_hmm_fused_pass).
+ *   vmp_hmm_wide_limits (host only): *max_K = 64, *max_D = 32.
+ *   vmp_hmm_wide_plan (host only): for (B, T, D, K) the chains of a workgroup of the chain kernel
+ *     *chains_per_wg and the scratch *workspace_doubles: E (B T KP, KP = K rounded up to a power
+ *     of two >= 2), the forward state that becomes gamma (B T K), the partials of the chain kernel
+ *     and of the statistics kernel, 1024.  Functions of the shape alone.  T < 2, a negative size
+ *     or a null pointer: VMP_ERR_INVALID; K or D above the limits: VMP_ERR_UNSUPPORTED.
+ *   vmp_hmm_wide_pass: the arguments of vmp_hmm_fused_pass_masked in the same order and the same
+ *     contract -- Y, C (compact feature order, rows of stride ldc, NULL = the prior pass), labels
+ *     and mask (each may be NULL), the outputs z0sum, xisum, Tstat (K x (1 + D + D^2)),
+ *     scal[0..3] and the optional gamma, z0, zz, -inf tables, B = 0, the order of the argument
+ *     checks and their status codes are as documented above, for 1 <= D <= 32.  A masked row has
+ *     zeros in place of y before any product (NaN may stand there) and E = 0; a chain without an
+ *     observed step adds nothing to any sum.  A mask of ones gives the bits of a NULL mask.  No
+ *     atomics: every workgroup leaves one partial and one kernel adds them in workgroup order,
+ *     so the bits of every output depend on the inputs and (B, T, D, K) alone, with or without
+ *     the optional outputs.  The bits are not those of vmp_hmm_fused_pass at D <= 8 (the feature
+ *     sums run on the matrix cores); both stay within the same allowance of the long-double
+ *     result.  ws: vmp_hmm_wide_plan's doubles. */
+int32_t vmp_hmm_wide_limits(int32_t *max_K, int32_t *max_D);
+int32_t vmp_hmm_wide_plan(int64_t B, int32_t T, int32_t D, int32_t K, int64_t *chains_per_wg,
+                          int64_t *workspace_doubles);
+int32_t vmp_hmm_wide_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t K,
+                          const double *Y, const double *C, int32_t ldc, const double *elog_a0,
+                          const double *elog_A, const int32_t *labels, const uint8_t *mask,
+                          double *ws, double *z0sum, double *xisum, double *Tstat, double *scal,
+                          double *gamma, double *z0, double *zz);
+
 /* Hidden Markov model with categorical emissions (the discrete HMM of hmm.rst's first half): the
  * chain pass of the fused block (bayespy_amd/csrc/vmp_hmm_cat.hip, vmp_hmm_fused_dev.h).  B chains
  * of T time instances, words y_t in [0, M), K states.  The recursion, the lane mapping, the mask

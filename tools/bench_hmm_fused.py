@@ -23,6 +23,13 @@ tests/hmm_models.py, Z from fixed random labels):
            twice, the forward state written and read once; the <log P> rows come from L2).
            Without --out these lines go to profiles/hmm_fused/bench_hmm_cat.json.
 
+  wide     (--engine fused+emissions, 9 <= D <= 32) the same legs on the wide-emission form
+           (inference/plans/hmm_wide.py); the pass is ``vmp_hmm_wide_pass`` (16 D + 24 KP + 32 K bytes
+           per chain step: y read by the emission and the statistics kernel, E written once and
+           read twice, the forward state written and read and gamma written and read in its
+           place).  --wide-pass (any D <= 8, engine fused) times ``vmp_hmm_wide_pass`` on the state
+           of the narrow plan right after ``vmp_hmm_fused_pass``, in the same process.
+
     python tools/bench_hmm_fused.py [--legs fused,pass,generic] [--B 20000] [--T 1000] [--steps 5]
                                     [--warmup 2] [--out profiles/...json]
     python tools/bench_hmm_fused.py --legs pass --observed 1.0,0.7 --ragged
@@ -164,8 +171,12 @@ def main():
                     help='masked pass with sequence lengths uniform in 1 ... T')
     ap.add_argument('--emissions', default='gaussian', choices=('gaussian', 'categorical'))
     ap.add_argument('--M', type=int, default=16, help='words of the categorical legs')
+    ap.add_argument('--engine', default='fused', choices=('fused', 'fused+emissions'))
+    ap.add_argument('--wide-pass', action='store_true',
+                    help='also time vmp_hmm_wide_pass on the state of the narrow plan')
     a = ap.parse_args()
     import torch
+    from bayespy_amd.inference.plans.hmm import HMMPlan
     B, T, D, K = a.B, a.T, a.D, a.K
     cat = a.emissions == 'categorical'
     shape = dict(B=B, T=T, M=a.M, K=K, emissions='categorical') if cat else dict(B=B, T=T, D=D, K=K)
@@ -194,23 +205,37 @@ def main():
     if masks and a.out is None:
         a.out = os.path.join(ROOT, 'profiles', 'hmm_fused', 'bench_hmm_masked.json')
     if 'fused' in legs or 'pass' in legs:
-        Q = build(y, mu, z0, 'fused')
+        torch.cuda.reset_peak_memory_stats()
+        Q = build(y, mu, z0, a.engine)
         plan = Q.plans[0]
-        assert type(plan).__name__ == 'HMMPlan'
+        wide = type(plan).__name__ == 'WideHMMPlan'
+        assert wide == (a.engine == 'fused+emissions' and D > 8) and isinstance(plan, HMMPlan)
+        KP = max(2, 1 << (K - 1).bit_length())
+        step_bytes = 16 * D + 24 * KP + 32 * K if wide else 16 * D + 16 * K
         if 'fused' in legs:
             emit(dict(leg='fused', what='Q.update()',
                       **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
-            emit(dict(leg='fused_bound', L=float(Q.L[Q.iter - 1])))
+            emit(dict(leg='fused_bound', L=float(Q.L[Q.iter - 1]),
+                      peak_GB=torch.cuda.max_memory_allocated() / 1e9))
         else:
             Q.update(verbose=False)
-        if 'pass' in legs:
+
+        def pass_leg(leg, what, nbytes):
             r = timed(lambda: plan._run_pass(refresh=False), a.steps, a.warmup)
             steps_total = float(B) * T
             s = 1e-3 * r['ms_median']
-            emit(dict(leg='pass', what='vmp_hmm_fused_pass', bytes_per_chain_step=16 * D + 16 * K,
-                      GB_per_s=steps_total * (16 * D + 16 * K) / s / 1e9,
-                      exp_per_chain_step=(3 * K + 2) * K,
+            emit(dict(leg=leg, what=what, bytes_per_chain_step=nbytes,
+                      GB_per_s=steps_total * nbytes / s / 1e9, exp_per_chain_step=(3 * K + 2) * K,
                       Gexp_per_s=steps_total * (3 * K + 2) * K / s / 1e9, **r))
+        if 'pass' in legs:
+            pass_leg('pass', 'vmp_hmm_wide_pass' if wide else 'vmp_hmm_fused_pass', step_bytes)
+        if a.wide_pass and not wide:
+            from bayespy_amd.inference.plans.hmm_wide import WideHMMKernels
+            narrow_k, narrow_ws = plan._kernels, plan.ws
+            plan._kernels = WideHMMKernels(plan.rt)
+            plan.ws = plan.rt.empty(int(plan._kernels.plan(B, T, D, K)[1]))
+            pass_leg('pass_wide', 'vmp_hmm_wide_pass', 16 * D + 24 * KP + 32 * K)
+            plan._kernels, plan.ws = narrow_k, narrow_ws
         rs = np.random.RandomState(1)
         for name, frac in masks:
             if frac is None:
@@ -229,6 +254,7 @@ def main():
         torch.cuda.empty_cache()
     if 'generic' in legs:
         try:
+            torch.cuda.reset_peak_memory_stats()
             Q = build(y, mu, z0, 'generic')
             emit(dict(leg='generic', what='Q.update()',
                       **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
