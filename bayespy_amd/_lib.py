@@ -282,6 +282,10 @@ SIGNATURES = {
     'vmp_hmm_wide_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_hmm_wide_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'vmp_hmm_seg_limits': (c_i32, [P(c_i32), P(c_i32)]),
+    'vmp_hmm_seg_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32, P(c_i32), P(c_i64)]),
+    'vmp_hmm_seg_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,
+                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32]),
     'vmp_hmm_fused_cat_limits': (c_i32, [P(c_i32), P(c_i32)]),
     'vmp_hmm_fused_cat_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_hmm_fused_pass_categorical': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,

@@ -490,6 +490,40 @@ int32_t launch_stats(vmp_ctx *ctx, int64_t nwr, const HmmwStatsArgs &a)
 
 }  // namespace
 
+// ---- the plate-parallel stages as host calls (vmp_hmm_wide_dev.h): vmp_hmm_wide_pass below and
+// the segmented chain stage (vmp_hmm_seg.hip) launch the same instances --------------------------
+int32_t vmp_hmmw_emit(vmp_ctx *ctx, int64_t R, int D, int K, const double *Y, const double *C,
+                      int ldc, const uint8_t *mask, double *E)
+{
+    const int NT = (K + 15) / 16;
+    HmmwEmitArgs ea = {R, (R + 63) / 64, D, K, vmp_hmmf_kpad(K), vmp_hmmf_nfeat(D), ldc, Y, C, mask, E};
+    return NT == 1 ? launch_emit<1>(ctx, ea) : NT == 2 ? launch_emit<2>(ctx, ea)
+           : NT == 3 ? launch_emit<3>(ctx, ea) : launch_emit<4>(ctx, ea);
+}
+
+int32_t vmp_hmmw_stats(vmp_ctx *ctx, int64_t R, int D, int K, const double *Y, const double *gam,
+                       const uint8_t *mask, double *spart)
+{
+    const int NT = (K + 15) / 16;
+    const int64_t nwr = vmp_hmmw_row_wgs(R, D, K);
+    HmmwStatsArgs sa = {R, vmp_hmmw_rows_per_wg(R, D, K), D, K, vmp_hmmf_nfeat(D), Y, gam, mask, spart};
+    return NT == 1 ? launch_stats<1>(ctx, nwr, sa) : NT == 2 ? launch_stats<2>(ctx, nwr, sa)
+           : NT == 3 ? launch_stats<3>(ctx, nwr, sa) : launch_stats<4>(ctx, nwr, sa);
+}
+
+int32_t vmp_hmmw_combine(vmp_ctx *ctx, int64_t nwc, int64_t nwr, int D, int K, const double *cpart,
+                         const double *spart, const double *elog_a0, const double *elog_A,
+                         double *dot_ws, double *z0sum, double *xisum, double *Tstat, double *scal)
+{
+    const int64_t ne = vmp_hmmw_chain_partial_doubles(K) + (int64_t)K * vmp_hmmf_nfeat(D);
+    hipLaunchKernelGGL(hmmw_combine_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0,
+                       ctx->stream, nwc, nwr, D, K, cpart, spart, z0sum, xisum, Tstat, scal);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    const int32_t rc = vmp_lda_dot(ctx, K, z0sum, elog_a0, dot_ws, scal + 2);
+    if (rc != VMP_OK) return rc;
+    return vmp_lda_dot(ctx, (int64_t)K * K, xisum, elog_A, dot_ws, scal + 3);
+}
+
 extern "C" {
 
 int32_t vmp_hmm_wide_limits(int32_t *max_K, int32_t *max_D)
@@ -526,7 +560,7 @@ int32_t vmp_hmm_wide_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t
     VMP_REQUIRE(ctx, ctx && elog_a0 && elog_A && ws && z0sum && xisum && Tstat && scal
                      && (B == 0 || Y), VMP_ERR_INVALID, "null argument");
     VMP_FLUSH_SMALL(ctx);
-    const int KP = vmp_hmmf_kpad(K), NT = (K + 15) / 16;
+    const int KP = vmp_hmmf_kpad(K);
     const int64_t R = B * (int64_t)T;
     const int64_t nwc = vmp_hmmw_chain_wgs(B, K), nwr = vmp_hmmw_row_wgs(R, D, K);
     const int64_t per = vmp_hmmw_chain_partial_doubles(K);
@@ -536,9 +570,7 @@ int32_t vmp_hmm_wide_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t
     if (R > 0) {
         const bool emit = C && !labels;
         if (emit) {
-            HmmwEmitArgs ea = {R, (R + 63) / 64, D, K, KP, NF, ldc, Y, C, mask, E};
-            rc = NT == 1 ? launch_emit<1>(ctx, ea) : NT == 2 ? launch_emit<2>(ctx, ea)
-                 : NT == 3 ? launch_emit<3>(ctx, ea) : launch_emit<4>(ctx, ea);
+            rc = vmp_hmmw_emit(ctx, R, D, K, Y, C, ldc, mask, E);
             if (rc != VMP_OK) return rc;
         }
         HmmwChainArgs ca = {B, vmp_hmmw_chains_per_wg(B, K), T, K, emit ? E : nullptr, elog_a0,
@@ -552,18 +584,11 @@ int32_t vmp_hmm_wide_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t
         default: rc = launch_chain<64>(ctx, nwc, ca); break;
         }
         if (rc != VMP_OK) return rc;
-        HmmwStatsArgs sa = {R, vmp_hmmw_rows_per_wg(R, D, K), D, K, NF, Y, aw, mask, spart};
-        rc = NT == 1 ? launch_stats<1>(ctx, nwr, sa) : NT == 2 ? launch_stats<2>(ctx, nwr, sa)
-             : NT == 3 ? launch_stats<3>(ctx, nwr, sa) : launch_stats<4>(ctx, nwr, sa);
+        rc = vmp_hmmw_stats(ctx, R, D, K, Y, aw, mask, spart);
         if (rc != VMP_OK) return rc;
     }
-    const int64_t ne = per + (int64_t)K * NF;
-    hipLaunchKernelGGL(hmmw_combine_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0,
-                       ctx->stream, nwc, nwr, D, K, cpart, spart, z0sum, xisum, Tstat, scal);
-    VMP_HIP_CHECK(ctx, hipGetLastError());
-    rc = vmp_lda_dot(ctx, K, z0sum, elog_a0, dot_ws, scal + 2);
-    if (rc != VMP_OK) return rc;
-    return vmp_lda_dot(ctx, (int64_t)K * K, xisum, elog_A, dot_ws, scal + 3);
+    return vmp_hmmw_combine(ctx, nwc, nwr, D, K, cpart, spart, elog_a0, elog_A, dot_ws, z0sum,
+                            xisum, Tstat, scal);
 }
 
 }  // extern "C"

@@ -93,3 +93,20 @@ __host__ __device__ inline int64_t vmp_hmmw_workspace_doubles(int64_t B, int T, 
            + vmp_hmmw_chain_wgs(B, K) * vmp_hmmw_chain_partial_doubles(K)
            + vmp_hmmw_row_wgs(R, D, K) * (int64_t)K * vmp_hmmf_nfeat(D) + 1024;
 }
+
+#ifdef __HIPCC__
+// The plate-parallel stages as host calls (defined in vmp_hmm_wide.hip), for the passes that keep
+// kernel 1, kernel 3 and the combine kernel and bring a chain stage of their own
+// (vmp_hmm_seg.hip).  emit: E (R x KP) from Y, C and the mask; stats: vmp_hmmw_row_wgs(R, D, K)
+// partials from the in-place gamma; combine: adds nwc chain partials of
+// vmp_hmmw_chain_partial_doubles(K) doubles and the partials of stats in workgroup order, then
+// forms scal[2] and scal[3] with dot_ws (1024 doubles).
+struct vmp_ctx;
+int32_t vmp_hmmw_emit(vmp_ctx *ctx, int64_t R, int D, int K, const double *Y, const double *C,
+                      int ldc, const uint8_t *mask, double *E);
+int32_t vmp_hmmw_stats(vmp_ctx *ctx, int64_t R, int D, int K, const double *Y, const double *gam,
+                       const uint8_t *mask, double *spart);
+int32_t vmp_hmmw_combine(vmp_ctx *ctx, int64_t nwc, int64_t nwr, int D, int K, const double *cpart,
+                         const double *spart, const double *elog_a0, const double *elog_A,
+                         double *dot_ws, double *z0sum, double *xisum, double *Tstat, double *scal);
+#endif

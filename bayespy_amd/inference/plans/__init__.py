@@ -15,6 +15,7 @@ from .bmm import BernoulliMixturePlan, BernoulliMixtureSVIPlan
 from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
 from .hmm_wide import WideHMMPlan
+from .hmm_seg import SegmentedHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
 from .dgmm_svi import DiagGaussianMixtureSVIPlan, MaskedDiagGaussianMixtureSVIPlan
@@ -81,6 +82,11 @@ OPT_IN_HYPER = {LDAPlan: [HyperLDAPlan], WideLDAPlan: [WideHyperLDAPlan]}
 # with a reason).  Everything else is engine='fused'; every other engine value does not try this
 # form and keeps its answer; it is not combined with the other '+' suffixes
 OPT_IN_WIDE_EMISSIONS = {HMMPlan: [WideHMMPlan]}
+# engine='fused+chains': the form of the HMM block for few long chains (plans/hmm_seg.py: the chain
+# pass parallel over time, 1 <= D <= 32), a plan class of its own that stands in that block's place.
+# Everything else is engine='fused'; every other engine value does not try this form and keeps its
+# answer; it is not combined with the other '+' suffixes
+OPT_IN_LONG_CHAINS = {HMMPlan: SegmentedHMMPlan}
 
 
 def _with_masked(types):
@@ -152,6 +158,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or any(type(p) in v for v in OPT_IN_TOPICS.values())
                                  or any(type(p) in v for v in OPT_IN_HYPER.values())
                                  or any(type(p) in v for v in OPT_IN_WIDE_EMISSIONS.values())
+                                 or type(p) in OPT_IN_LONG_CHAINS.values()
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -192,7 +199,8 @@ def compile_model(nodes, engine=None, **options):
     hyper = engine in ('fused+hyper', 'fused+topics+hyper')
     topics = engine in ('fused+topics', 'fused+topics+hyper')
     emissions = engine == 'fused+emissions'
-    if batches or topics or hyper or emissions:
+    chains = engine == 'fused+chains'
+    if batches or topics or hyper or emissions or chains:
         engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
     if kept is not None and not topics \
@@ -201,6 +209,9 @@ def compile_model(nodes, engine=None, **options):
     if kept is not None and not emissions \
             and any(type(p) in v for p in kept for v in OPT_IN_WIDE_EMISSIONS.values()):
         kept = None             # the wide-emission form is kept only where it is asked for
+    if kept is not None and any(type(p) in (OPT_IN_LONG_CHAINS.values() if not chains
+                                            else OPT_IN_LONG_CHAINS) for p in kept):
+        kept = None             # the long-chain form is kept where it is asked for, and only there
     if kept is not None and not hyper \
             and any(type(p) in v for p in kept for v in OPT_IN_HYPER.values()):
         kept = None             # a form with learnt concentrations is kept only where it is asked for
@@ -238,6 +249,8 @@ def compile_model(nodes, engine=None, **options):
         types = _with_hyper(types)
     if emissions:
         types = _with_wide_emissions(types)
+    if chains:
+        types = [OPT_IN_LONG_CHAINS.get(P, P) for P in types]
     remaining = [n for n in nodes]
     plans = []
     progress = True

@@ -1325,6 +1325,42 @@ int32_t vmp_hmm_wide_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t
                           double *ws, double *z0sum, double *xisum, double *Tstat, double *scal,
                           double *gamma, double *z0, double *zz);
 
+/* The same pass, parallel over time: the segmented chain stage for few long chains (details:
+ * bayespy_amd/csrc/vmp_hmm_seg.hip, vmp_hmm_seg_dev.h).  vmp_hmm_wide_pass walks a chain with
+ * 2 (T - 1) dependent steps on one lane group.  Here the T - 1 transitions are cut into
+ * S = ceil((T - 1) / L) segments: one kernel forms, per entry and in the log domain, the K x K
+ * transfer log W_s of every segment from every start state; one lane group per chain carries la
+ * and lb across the S segment boundaries and forms log Z; one kernel runs the recursion of
+ * vmp_hmm_wide_pass inside every segment from those boundary values.  The emission table, the
+ * statistics and the combine kernel are those of vmp_hmm_wide_pass.
+ *   vmp_hmm_seg_limits (host only): *max_K = 64, *max_D = 32.
+ *   vmp_hmm_seg_plan (host only): for (B, T, D, K) and a requested seg_len the segment length in
+ *     use *seg_len_used and the scratch *workspace_doubles.  seg_len = 0 asks for the library's
+ *     choice, a function of (B, T, K) alone (the smallest power of two L >= 16 with 4 L^2 >= T),
+ *     or for the value of the tune key hmm_seg_len where one is set; any length is cut to T - 1,
+ *     which is one segment.  Workspace: that of vmp_hmm_wide_plan with the partials of the sweep
+ *     kernel in the place of the chain kernel's, plus B S (K KP + 2 KP + 2) + 2 B doubles, and
+ *     never below vmp_hmm_wide_plan's.  T < 2, a negative size or length or a null pointer:
+ *     VMP_ERR_INVALID; K or D above the limits: VMP_ERR_UNSUPPORTED.
+ *   vmp_hmm_seg_pass: the arguments and the contract of vmp_hmm_wide_pass, then seg_len as
+ *     vmp_hmm_seg_plan takes it (negative: VMP_ERR_INVALID with the shape); the same argument
+ *     checks in the same order with the same status codes.  ws: vmp_hmm_seg_plan's doubles for
+ *     the same seg_len.  With `labels` the call is vmp_hmm_wide_pass and has its bits.  Otherwise
+ *     every output is within the allowance of vmp_hmm_wide_pass of the long-double result, not
+ *     bit-equal to it (log Z is added per segment).  A start state from which a segment reaches
+ *     nothing (-inf tables) has a row of -inf in log W_s and gets 0.  No atomics: one partial per
+ *     workgroup, added in workgroup order, so the bits of every output depend on the inputs and
+ *     (B, T, D, K, L) alone, with or without the optional outputs; a mask of ones gives the bits
+ *     of a NULL mask. */
+int32_t vmp_hmm_seg_limits(int32_t *max_K, int32_t *max_D);
+int32_t vmp_hmm_seg_plan(int64_t B, int32_t T, int32_t D, int32_t K, int32_t seg_len,
+                         int32_t *seg_len_used, int64_t *workspace_doubles);
+int32_t vmp_hmm_seg_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t K,
+                         const double *Y, const double *C, int32_t ldc, const double *elog_a0,
+                         const double *elog_A, const int32_t *labels, const uint8_t *mask,
+                         double *ws, double *z0sum, double *xisum, double *Tstat, double *scal,
+                         double *gamma, double *z0, double *zz, int32_t seg_len);
+
 /* Hidden Markov model with categorical emissions (the discrete HMM of hmm.rst's first half): the
  * chain pass of the fused block (bayespy_amd/csrc/vmp_hmm_cat.hip, vmp_hmm_fused_dev.h).  B chains
  * of T time instances, words y_t in [0, M), K states.  The recursion, the lane mapping, the mask

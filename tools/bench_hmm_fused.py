@@ -30,6 +30,12 @@ tests/hmm_models.py, Z from fixed random labels):
            place).  --wide-pass (any D <= 8, engine fused) times ``vmp_hmm_wide_pass`` on the state
            of the narrow plan right after ``vmp_hmm_fused_pass``, in the same process.
 
+  chains   (--engine fused+chains, D <= 32) the same legs on the long-chain form
+           (inference/plans/hmm_seg.py); the pass is ``vmp_hmm_seg_pass``, one ``pass`` line per
+           value of --seg-len (comma-separated; 0 = the library's choice), each with the segment
+           length in use.  --wide-pass then times ``vmp_hmm_wide_pass``, the sequential chain
+           stage, on the same state in the same process.
+
     python tools/bench_hmm_fused.py [--legs fused,pass,generic] [--B 20000] [--T 1000] [--steps 5]
                                     [--warmup 2] [--out profiles/...json]
     python tools/bench_hmm_fused.py --legs pass --observed 1.0,0.7 --ragged
@@ -171,7 +177,10 @@ def main():
                     help='masked pass with sequence lengths uniform in 1 ... T')
     ap.add_argument('--emissions', default='gaussian', choices=('gaussian', 'categorical'))
     ap.add_argument('--M', type=int, default=16, help='words of the categorical legs')
-    ap.add_argument('--engine', default='fused', choices=('fused', 'fused+emissions'))
+    ap.add_argument('--engine', default='fused', choices=('fused', 'fused+emissions', 'fused+chains'))
+    ap.add_argument('--seg-len', default='0',
+                    help='fused+chains: comma-separated segment lengths of the pass legs (0 = the '
+                         "library's choice)")
     ap.add_argument('--wide-pass', action='store_true',
                     help='also time vmp_hmm_wide_pass on the state of the narrow plan')
     a = ap.parse_args()
@@ -209,9 +218,11 @@ def main():
         Q = build(y, mu, z0, a.engine)
         plan = Q.plans[0]
         wide = type(plan).__name__ == 'WideHMMPlan'
+        seg = type(plan).__name__ == 'SegmentedHMMPlan'
         assert wide == (a.engine == 'fused+emissions' and D > 8) and isinstance(plan, HMMPlan)
+        assert seg == (a.engine == 'fused+chains')
         KP = max(2, 1 << (K - 1).bit_length())
-        step_bytes = 16 * D + 24 * KP + 32 * K if wide else 16 * D + 16 * K
+        step_bytes = 16 * D + 24 * KP + 32 * K if wide or seg else 16 * D + 16 * K
         if 'fused' in legs:
             emit(dict(leg='fused', what='Q.update()',
                       **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
@@ -227,7 +238,13 @@ def main():
             emit(dict(leg=leg, what=what, bytes_per_chain_step=nbytes,
                       GB_per_s=steps_total * nbytes / s / 1e9, exp_per_chain_step=(3 * K + 2) * K,
                       Gexp_per_s=steps_total * (3 * K + 2) * K / s / 1e9, **r))
-        if 'pass' in legs:
+        if 'pass' in legs and seg:
+            for L in a.seg_len.split(','):
+                plan.seg_len = int(L)
+                shape['seg_len'] = plan.chains_per_wg
+                pass_leg('pass', 'vmp_hmm_seg_pass', step_bytes)
+            del shape['seg_len']
+        elif 'pass' in legs:
             pass_leg('pass', 'vmp_hmm_wide_pass' if wide else 'vmp_hmm_fused_pass', step_bytes)
         if a.wide_pass and not wide:
             from bayespy_amd.inference.plans.hmm_wide import WideHMMKernels
