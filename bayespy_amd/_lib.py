@@ -291,6 +291,10 @@ SIGNATURES = {
     'vmp_hmm_fused_pass_categorical': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                c_vp, c_vp, c_vp]),
+    'vmp_hmm_seg_cat_limits': (c_i32, [P(c_i32), P(c_i32)]),
+    'vmp_hmm_seg_cat_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32, P(c_i32), P(c_i64)]),
+    'vmp_hmm_seg_pass_categorical': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 14
+                                     + [c_i32]),
     'vmp_cmm_limits': (c_i32, [P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
     'vmp_cmm_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_cmm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),

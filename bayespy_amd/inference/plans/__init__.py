@@ -16,6 +16,7 @@ from .hmm import HMMPlan
 from .hmm_cat import CategoricalHMMPlan
 from .hmm_wide import WideHMMPlan
 from .hmm_seg import SegmentedHMMPlan
+from .hmm_seg_cat import SegmentedCategoricalHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
 from .dgmm_svi import DiagGaussianMixtureSVIPlan, MaskedDiagGaussianMixtureSVIPlan
@@ -82,11 +83,12 @@ OPT_IN_HYPER = {LDAPlan: [HyperLDAPlan], WideLDAPlan: [WideHyperLDAPlan]}
 # with a reason).  Everything else is engine='fused'; every other engine value does not try this
 # form and keeps its answer; it is not combined with the other '+' suffixes
 OPT_IN_WIDE_EMISSIONS = {HMMPlan: [WideHMMPlan]}
-# engine='fused+chains': the form of the HMM block for few long chains (plans/hmm_seg.py: the chain
-# pass parallel over time, 1 <= D <= 32), a plan class of its own that stands in that block's place.
-# Everything else is engine='fused'; every other engine value does not try this form and keeps its
-# answer; it is not combined with the other '+' suffixes
-OPT_IN_LONG_CHAINS = {HMMPlan: SegmentedHMMPlan}
+# engine='fused+chains': the forms of the HMM block for few long chains (plans/hmm_seg.py: the chain
+# pass parallel over time, 1 <= D <= 32; plans/hmm_seg_cat.py: the same for categorical emissions),
+# each a plan class of its own that stands in its block's place.  Everything else is
+# engine='fused'; every other engine value does not try these forms and keeps its answer; it is
+# not combined with the other '+' suffixes
+OPT_IN_LONG_CHAINS = {HMMPlan: SegmentedHMMPlan, CategoricalHMMPlan: SegmentedCategoricalHMMPlan}
 
 
 def _with_masked(types):

@@ -46,6 +46,7 @@ from ...nodes.categorical_markov_chain import (CategoricalMarkovChain,
                                                CategoricalMarkovChainToCategorical)
 from ...nodes.mixture import Mixture
 
+LABEL = 'fused hidden-Markov-model block with categorical emissions'
 _LIMITS = []
 
 
@@ -87,7 +88,7 @@ def _positive_constant(node, shape):
     return isinstance(node, Constant) and node.value.shape == shape and bool(np.all(node.value > 0))
 
 
-def _match(nodes, why):
+def _match(nodes, why, label=LABEL, limits=hmm_cat_limits):
     for Y in nodes:
         if not isinstance(Y, Mixture) or not isinstance(Y.parents[0],
                                                         CategoricalMarkovChainToCategorical):
@@ -97,8 +98,7 @@ def _match(nodes, why):
 
         def no(msg, Y=Y):
             if why is not None:
-                why.append('fused hidden-Markov-model block with categorical emissions, observed '
-                           'node %s: %s' % (Y.name or '<unnamed>', msg))
+                why.append('%s, observed node %s: %s' % (label, Y.name or '<unnamed>', msg))
         Zc = Y.parents[0]
         Z = Zc.parents[0]
         if type(Z) is not CategoricalMarkovChain or len(Y.parents) != 2:
@@ -167,7 +167,7 @@ def _match(nodes, why):
             no('it needs plates (T,) or (B, T), Y has plates %s and Z has plates %s'
                % (Y.plates, Z.plates))
             continue
-        max_K, max_M = hmm_cat_limits()
+        max_K, max_M = limits()
         if K > max_K or M > max_M:
             no('M = %d, K = %d exceed the limits of the block (M <= %d, K <= %d)'
                % (M, K, max_M, max_K))

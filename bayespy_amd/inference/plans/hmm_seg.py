@@ -16,8 +16,7 @@ update) is the number of transitions of a segment; any value of T - 1 or more is
 
 Opt-in: ``VB(..., engine='fused+chains')``, which is ``engine='fused'`` with the forms of
 ``plans.OPT_IN_LONG_CHAINS`` standing in their block's place.  Every other engine value keeps its
-answer and never keeps such a plan on reuse.  Categorical emissions stay on ``CategoricalHMMPlan``
-(the same chain stage under a table lookup is the obvious follow-up).
+answer and never keeps such a plan on reuse.  Categorical emissions: plans/hmm_seg_cat.py.
 """
 import ctypes
 

@@ -1397,6 +1397,39 @@ int32_t vmp_hmm_fused_pass_categorical(vmp_ctx *ctx, int64_t B, int32_t T, int32
                                        double *z0sum, double *xisum, double *S, double *scal,
                                        double *gamma, double *z0, double *zz);
 
+/* The same pass, parallel over time: the segmented chain pass of the discrete block for few long
+ * chains (details: bayespy_amd/csrc/vmp_hmm_seg_cat.hip, vmp_hmm_seg_cat_dev.h).  The segments, the
+ * transfer, the boundary scan and the sweep are those of vmp_hmm_seg_pass; the emission term is a
+ * lookup in the word-major table, which every workgroup keeps in LDS (no B T K emission array
+ * exists), the per-step shift is a lookup in a table of M maxima, and the counts S are formed by a
+ * kernel of their own from the in-place gamma.
+ *   vmp_hmm_seg_cat_limits (host only): *max_K = 64, *max_M = 128.
+ *   vmp_hmm_seg_cat_plan (host only): for (B, T, M, K) and a requested seg_len the segment length
+ *     in use *seg_len_used -- the rule of vmp_hmm_seg_plan for the same (B, T, K), tune key
+ *     hmm_seg_len included -- and the scratch *workspace_doubles: B T K, the partials of the sweep
+ *     and of the count kernel, 1024, B S (K KP + 2 KP + 2) + 2 B; never below
+ *     vmp_hmm_fused_cat_plan's.  T < 2, a size below 1 (B below 0), a negative length or a null
+ *     pointer: VMP_ERR_INVALID; K or M above the limits: VMP_ERR_UNSUPPORTED.
+ *   vmp_hmm_seg_pass_categorical: the arguments and the contract of
+ *     vmp_hmm_fused_pass_categorical (elogPt NULL = the prior pass; a masked step and a step whose
+ *     word is outside [0, M) have e = 0 and read neither word nor table; S word-major (M, K);
+ *     scal[0..3]), then seg_len as vmp_hmm_seg_cat_plan takes it (negative: VMP_ERR_INVALID with
+ *     the shape); the same argument checks in the same order with the same status codes.  ws:
+ *     vmp_hmm_seg_cat_plan's doubles for the same seg_len.  With `labels` the call is
+ *     vmp_hmm_fused_pass_categorical and has its bits.  Otherwise every output is within the
+ *     allowance of that pass of the long-double result, not bit-equal to it.  No atomics: the bits
+ *     of every output depend on the inputs and (B, T, M, K, L) alone, with or without the optional
+ *     outputs; a mask of ones gives the bits of a NULL mask.  B = 0 gives zeros. */
+int32_t vmp_hmm_seg_cat_limits(int32_t *max_K, int32_t *max_M);
+int32_t vmp_hmm_seg_cat_plan(int64_t B, int32_t T, int32_t M, int32_t K, int32_t seg_len,
+                             int32_t *seg_len_used, int64_t *workspace_doubles);
+int32_t vmp_hmm_seg_pass_categorical(vmp_ctx *ctx, int64_t B, int32_t T, int32_t M, int32_t K,
+                                     const int32_t *y, const double *elogPt, const double *elog_a0,
+                                     const double *elog_A, const int32_t *labels,
+                                     const uint8_t *mask, double *ws, double *z0sum, double *xisum,
+                                     double *S, double *scal, double *gamma, double *z0, double *zz,
+                                     int32_t seg_len);
+
 /* Categorical mixture (latent class model): the plate pass of the fused block
  *     R = Dirichlet(a);  Z = Categorical(R, plates=(N, 1))
  *     P = Dirichlet(conc, plates=(D, K));  X = Mixture(Z, Categorical, P);  X.observe(x[, mask])
