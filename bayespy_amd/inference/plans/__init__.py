@@ -17,6 +17,7 @@ from .hmm_cat import CategoricalHMMPlan
 from .hmm_wide import WideHMMPlan
 from .hmm_seg import SegmentedHMMPlan
 from .hmm_seg_cat import SegmentedCategoricalHMMPlan
+from .hmm_vocab import VocabCategoricalHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
 from .dgmm_svi import DiagGaussianMixtureSVIPlan, MaskedDiagGaussianMixtureSVIPlan
@@ -89,6 +90,11 @@ OPT_IN_WIDE_EMISSIONS = {HMMPlan: [WideHMMPlan]}
 # engine='fused'; every other engine value does not try these forms and keeps its answer; it is
 # not combined with the other '+' suffixes
 OPT_IN_LONG_CHAINS = {HMMPlan: SegmentedHMMPlan, CategoricalHMMPlan: SegmentedCategoricalHMMPlan}
+# engine='fused+words': the form of the discrete HMM block for vocabularies of 129 to 65536 words
+# (plans/hmm_vocab.py), a plan class of its own, tried right after that block (which declines
+# M > 128 with a reason).  Everything else is engine='fused'; every other engine value does not try
+# this form and keeps its answer; it is not combined with the other '+' suffixes
+OPT_IN_WORDS = {CategoricalHMMPlan: [VocabCategoricalHMMPlan]}
 
 
 def _with_masked(types):
@@ -116,6 +122,11 @@ def _with_topics(types):
 def _with_wide_emissions(types):
     """``types`` with the plan classes of ``OPT_IN_WIDE_EMISSIONS`` inserted after their block."""
     return [Q for P in types for Q in [P] + OPT_IN_WIDE_EMISSIONS.get(P, [])]
+
+
+def _with_words(types):
+    """``types`` with the plan classes of ``OPT_IN_WORDS`` inserted after their block."""
+    return [Q for P in types for Q in [P] + OPT_IN_WORDS.get(P, [])]
 
 
 def _with_hyper(types):
@@ -161,6 +172,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or any(type(p) in v for v in OPT_IN_HYPER.values())
                                  or any(type(p) in v for v in OPT_IN_WIDE_EMISSIONS.values())
                                  or type(p) in OPT_IN_LONG_CHAINS.values()
+                                 or any(type(p) in v for v in OPT_IN_WORDS.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -202,7 +214,8 @@ def compile_model(nodes, engine=None, **options):
     topics = engine in ('fused+topics', 'fused+topics+hyper')
     emissions = engine == 'fused+emissions'
     chains = engine == 'fused+chains'
-    if batches or topics or hyper or emissions or chains:
+    words = engine == 'fused+words'
+    if batches or topics or hyper or emissions or chains or words:
         engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
     if kept is not None and not topics \
@@ -214,6 +227,9 @@ def compile_model(nodes, engine=None, **options):
     if kept is not None and any(type(p) in (OPT_IN_LONG_CHAINS.values() if not chains
                                             else OPT_IN_LONG_CHAINS) for p in kept):
         kept = None             # the long-chain form is kept where it is asked for, and only there
+    if kept is not None and not words \
+            and any(type(p) in v for p in kept for v in OPT_IN_WORDS.values()):
+        kept = None             # the large-vocabulary form is kept only where it is asked for
     if kept is not None and not hyper \
             and any(type(p) in v for p in kept for v in OPT_IN_HYPER.values()):
         kept = None             # a form with learnt concentrations is kept only where it is asked for
@@ -253,6 +269,8 @@ def compile_model(nodes, engine=None, **options):
         types = _with_wide_emissions(types)
     if chains:
         types = [OPT_IN_LONG_CHAINS.get(P, P) for P in types]
+    if words:
+        types = _with_words(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

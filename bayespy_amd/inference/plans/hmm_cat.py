@@ -88,7 +88,8 @@ def _positive_constant(node, shape):
     return isinstance(node, Constant) and node.value.shape == shape and bool(np.all(node.value > 0))
 
 
-def _match(nodes, why, label=LABEL, limits=hmm_cat_limits):
+def _match(nodes, why, label=LABEL, limits=hmm_cat_limits, min_M=1, below=''):
+    """``min_M``, ``below``: the smallest vocabulary the form takes and what to say under it."""
     for Y in nodes:
         if not isinstance(Y, Mixture) or not isinstance(Y.parents[0],
                                                         CategoricalMarkovChainToCategorical):
@@ -171,6 +172,9 @@ def _match(nodes, why, label=LABEL, limits=hmm_cat_limits):
         if K > max_K or M > max_M:
             no('M = %d, K = %d exceed the limits of the block (M <= %d, K <= %d)'
                % (M, K, max_M, max_K))
+            continue
+        if M < min_M:
+            no('M = %d: %s' % (M, below))
             continue
         kids = [(Z, [Zc]), (Zc, [Y]), (Y, [])] \
             + [(n, [Z]) for n in (a0, A) if type(n) is Dirichlet] \

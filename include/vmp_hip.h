@@ -1430,6 +1430,48 @@ int32_t vmp_hmm_seg_pass_categorical(vmp_ctx *ctx, int64_t B, int32_t T, int32_t
                                      double *S, double *scal, double *gamma, double *z0, double *zz,
                                      int32_t seg_len);
 
+/* The same pass for large vocabularies, 1 <= M <= 65536 (details:
+ * bayespy_amd/csrc/vmp_hmm_vocab.hip, vmp_hmm_vocab_dev.h).  No workgroup keeps anything of size
+ * M: a chain kernel runs the recursion of vmp_hmm_fused_pass_categorical (same lane mapping, mask
+ * rules and order of additions), gathers e_t from the table ahead of the step that uses it and
+ * leaves gamma in place of the forward state; a count kernel forms S from that gamma as a segmented
+ * sum over a word-sorted layout of the observed steps; a third kernel adds the partials.
+ *   vmp_hmm_vocab_limits (host only): *max_K = 64, *max_M = 65536.  max_M is set by the int32
+ *     addressing of the table (M K doubles) and of word_offsets, and by the size of the table the
+ *     gather is served from: 32 MB at K = 64.
+ *   vmp_hmm_vocab_plan (host only): for (B, T, M, K) and n_obs entries of the layout the chains
+ *     of a workgroup *chains_per_wg, the entries of a chunk *chunk_entries (a power of two from 16
+ *     to 256, a function of (n_obs, K) alone) and the scratch *workspace_doubles: B T K, the
+ *     partials, K doubles of head and of tail per chunk, 1024; monotone in n_obs, so that the
+ *     doubles for n_obs = B T serve every mask.  B T >= 2^31, T < 2, a size below 1 (B below 0),
+ *     n_obs outside [0, B T] or a null pointer: VMP_ERR_INVALID; K or M above the limits:
+ *     VMP_ERR_UNSUPPORTED.
+ *   vmp_hmm_vocab_pass: the arguments, outputs (S word-major (M, K), scal[0..3]) and contract of
+ *     vmp_hmm_fused_pass_categorical, and the layout: n_obs, order (n_obs int32) and
+ *     word_offsets (M + 1 int32); both may be NULL when n_obs = 0.  PRECONDITION, not verified:
+ *     order holds the positions b T + t of exactly the steps that are observed (mask NULL or 1)
+ *     with a word in [0, M), each once, sorted by word and by ascending position inside a word;
+ *     word_offsets[m] is the index in order of the first entry of word m, word_offsets[0] = 0 and
+ *     word_offsets[M] = n_obs.  A layout that lists other steps gives another S; positions outside
+ *     [0, B T) must not occur.  ws: vmp_hmm_vocab_plan's doubles for an n_obs that is not
+ *     smaller.  S is never cleared beforehand: words without an entry are written as zeros.  With
+ *     `labels` gamma is the one-hot row and no recursion runs.  No atomics: the bits of every
+ *     output depend on the inputs, (B, T, M, K) and the layout alone, with or without the optional
+ *     outputs; a mask of ones gives the bits of a NULL mask.  B = 0 gives zeros.  The argument
+ *     checks, their order and the status codes are those of vmp_hmm_fused_pass_categorical, with
+ *     B T >= 2^31 and n_obs outside [0, B T] judged with the shape (VMP_ERR_INVALID).  Nothing is
+ *     launched after a refusal. */
+int32_t vmp_hmm_vocab_limits(int32_t *max_K, int32_t *max_M);
+int32_t vmp_hmm_vocab_plan(int64_t B, int32_t T, int32_t M, int32_t K, int64_t n_obs,
+                           int64_t *chains_per_wg, int32_t *chunk_entries,
+                           int64_t *workspace_doubles);
+int32_t vmp_hmm_vocab_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t M, int32_t K,
+                           const int32_t *y, const double *elogPt, const double *elog_a0,
+                           const double *elog_A, const int32_t *labels, const uint8_t *mask,
+                           int64_t n_obs, const int32_t *order, const int32_t *word_offsets,
+                           double *ws, double *z0sum, double *xisum, double *S, double *scal,
+                           double *gamma, double *z0, double *zz);
+
 /* Categorical mixture (latent class model): the plate pass of the fused block
  *     R = Dirichlet(a);  Z = Categorical(R, plates=(N, 1))
  *     P = Dirichlet(conc, plates=(D, K));  X = Mixture(Z, Categorical, P);  X.observe(x[, mask])

@@ -22,6 +22,10 @@ tests/hmm_models.py, Z from fixed random labels):
            pass is ``vmp_hmm_fused_pass_categorical`` (8 + 16 K bytes per chain step: the int32 word read
            twice, the forward state written and read once; the <log P> rows come from L2).
            Without --out these lines go to profiles/hmm_fused/bench_hmm_cat.json.
+           --engine fused+words (inference/plans/hmm_vocab.py) with --M 128,4096,65536: the legs once
+           per vocabulary in one process; the pass is ``vmp_hmm_vocab_pass`` above 128 words
+           (12 + 32 K bytes per chain step), and at 128 words or fewer both the sequential pass and
+           the vocabulary pass on the same state.
 
   wide     (--engine fused+emissions, 9 <= D <= 32) the same legs on the wide-emission form
            (inference/plans/hmm_wide.py); the pass is ``vmp_hmm_wide_pass`` (16 D + 24 KP + 32 K bytes
@@ -86,7 +90,9 @@ def make_words(B, T, M, K, seed=0):
     for t in range(1, T):                           # sticky chains
         z[:, t] = np.where(rs.rand(B) < 0.9, z[:, t - 1], rs.randint(K, size=B))
     u = rs.rand(B, T)
-    y = (u[..., None] > np.cumsum(P, axis=1)[z]).sum(-1).clip(0, M - 1)
+    y = np.empty((B, T), dtype=np.int64)
+    for k in range(K):                              # the number of cumulative sums below u
+        y[z == k] = np.searchsorted(np.cumsum(P[k]), u[z == k]).clip(0, M - 1)
     return y, rs.randint(K, size=(B, T))
 
 
@@ -106,16 +112,18 @@ def build_cat(y, z0, K, M, engine):
     return Q
 
 
-def categorical_legs(a, emit):
+def categorical_legs(a, emit, M):
     import torch
-    B, T, K, M = a.B, a.T, a.K, a.M
+    B, T, K = a.B, a.T, a.K
     y, z0 = make_words(B, T, M, K)
     legs = a.legs.split(',')
     if 'fused' in legs or 'pass' in legs:
         torch.cuda.reset_peak_memory_stats()
-        Q = build_cat(y, z0, K, M, 'fused')
+        Q = build_cat(y, z0, K, M, a.engine)
         plan = Q.plans[0]
-        assert type(plan).__name__ == 'CategoricalHMMPlan'
+        words = type(plan).__name__ == 'VocabCategoricalHMMPlan'
+        assert words == (a.engine == 'fused+words' and M > 128)
+        assert words or type(plan).__name__ == 'CategoricalHMMPlan'
         if 'fused' in legs:
             emit(dict(leg='fused', what='Q.update()',
                       **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
@@ -123,15 +131,31 @@ def categorical_legs(a, emit):
                       peak_GB=torch.cuda.max_memory_allocated() / 1e9))
         else:
             Q.update(verbose=False)
-        if 'pass' in legs:
+        def pass_leg(what, nbytes):
             r = timed(lambda: plan._run_pass(refresh=False), a.steps, a.warmup)
             steps_total = float(B) * T
             s = 1e-3 * r['ms_median']
-            emit(dict(leg='pass', what='vmp_hmm_fused_pass_categorical',
-                      bytes_per_chain_step=8 + 16 * K,
-                      GB_per_s=steps_total * (8 + 16 * K) / s / 1e9,
+            emit(dict(leg='pass', what=what, bytes_per_chain_step=nbytes,
+                      GB_per_s=steps_total * nbytes / s / 1e9,
                       exp_per_chain_step=(3 * K + 2) * K,
                       Gexp_per_s=steps_total * (3 * K + 2) * K / s / 1e9, **r))
+        # the vocabulary pass: the word read twice, la written and read, gamma written over it and
+        # read by the count kernel, 4 bytes of layout
+        vocab_bytes = 12 + 32 * K
+        if 'pass' in legs and words:
+            pass_leg('vmp_hmm_vocab_pass', vocab_bytes)
+        elif 'pass' in legs:
+            pass_leg('vmp_hmm_fused_pass_categorical', 8 + 16 * K)
+            if a.engine == 'fused+words':
+                # the vocabulary pass on the state of the sequential plan, in the same process
+                from bayespy_amd.inference.plans.hmm_vocab import VocabCatHMMKernels
+                seq_k, seq_ws = plan._kernels, plan.ws
+                from bayespy_amd.inference.plans.hmm_vocab import word_layout
+                plan._kernels = VocabCatHMMKernels(plan.rt)
+                plan._kernels.layout = word_layout(torch, plan.yd, plan.maskd, M)
+                plan.ws = plan.rt.empty(int(plan._kernels.plan(B, T, M, K)[1]))
+                pass_leg('vmp_hmm_vocab_pass', vocab_bytes)
+                plan._kernels, plan.ws = seq_k, seq_ws
         del Q, plan
         torch.cuda.empty_cache()
     if 'generic' in legs:
@@ -176,8 +200,11 @@ def main():
     ap.add_argument('--ragged', action='store_true',
                     help='masked pass with sequence lengths uniform in 1 ... T')
     ap.add_argument('--emissions', default='gaussian', choices=('gaussian', 'categorical'))
-    ap.add_argument('--M', type=int, default=16, help='words of the categorical legs')
-    ap.add_argument('--engine', default='fused', choices=('fused', 'fused+emissions', 'fused+chains'))
+    ap.add_argument('--M', default='16',
+                    help='words of the categorical legs; comma-separated: the legs once per value, '
+                         'in one process')
+    ap.add_argument('--engine', default='fused',
+                    choices=('fused', 'fused+emissions', 'fused+chains', 'fused+words'))
     ap.add_argument('--seg-len', default='0',
                     help='fused+chains: comma-separated segment lengths of the pass legs (0 = the '
                          "library's choice)")
@@ -188,7 +215,7 @@ def main():
     from bayespy_amd.inference.plans.hmm import HMMPlan
     B, T, D, K = a.B, a.T, a.D, a.K
     cat = a.emissions == 'categorical'
-    shape = dict(B=B, T=T, M=a.M, K=K, emissions='categorical') if cat else dict(B=B, T=T, D=D, K=K)
+    shape = dict(B=B, T=T, M=0, K=K, emissions='categorical') if cat else dict(B=B, T=T, D=D, K=K)
     lines = []
 
     def emit(rec):
@@ -199,7 +226,9 @@ def main():
     if cat:
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'hmm_fused', 'bench_hmm_cat.json')
-        categorical_legs(a, emit)
+        for M in a.M.split(','):
+            shape['M'] = int(M)
+            categorical_legs(a, emit, int(M))
         with open(a.out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
         return
