@@ -300,6 +300,9 @@ SIGNATURES = {
                                    P(c_i64)]),
     'vmp_hmm_vocab_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 6 + [c_i64]
                            + [c_vp] * 10),
+    'vmp_hmm_mult_limits': (c_i32, [P(c_i32), P(c_i32), P(c_i32)]),
+    'vmp_hmm_mult_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
+    'vmp_hmm_mult_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 14),
     'vmp_cmm_limits': (c_i32, [P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
     'vmp_cmm_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_cmm_pack': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),

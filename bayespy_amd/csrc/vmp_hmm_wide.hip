@@ -29,9 +29,6 @@ __device__ __forceinline__ int hmmw_pair(int D, int NF, int f)
     return pa | (pb << 8);
 }
 
-// LDS row stride of a 16 NT wide operand: rows 4 q + l4 of one matrix instruction in distinct banks
-__host__ __device__ constexpr int hmmw_stride(int NT) { return (NT * 16) % 32 == 0 ? NT * 16 + 16 : NT * 16; }
-
 // ---- kernel 1: the emission table -------------------------------------------------------------------
 struct HmmwEmitArgs {
     int64_t R, nblk;              // rows of the (b, t) plate, blocks of 64 rows
@@ -491,7 +488,8 @@ int32_t launch_stats(vmp_ctx *ctx, int64_t nwr, const HmmwStatsArgs &a)
 }  // namespace
 
 // ---- the plate-parallel stages as host calls (vmp_hmm_wide_dev.h): vmp_hmm_wide_pass below and
-// the segmented chain stage (vmp_hmm_seg.hip) launch the same instances --------------------------
+// the passes that bring another stage of their own (vmp_hmm_seg.hip, vmp_hmm_mult.hip) launch the
+// same instances ----------------------------------------------------------------------------------
 int32_t vmp_hmmw_emit(vmp_ctx *ctx, int64_t R, int D, int K, const double *Y, const double *C,
                       int ldc, const uint8_t *mask, double *E)
 {
@@ -499,6 +497,23 @@ int32_t vmp_hmmw_emit(vmp_ctx *ctx, int64_t R, int D, int K, const double *Y, co
     HmmwEmitArgs ea = {R, (R + 63) / 64, D, K, vmp_hmmf_kpad(K), vmp_hmmf_nfeat(D), ldc, Y, C, mask, E};
     return NT == 1 ? launch_emit<1>(ctx, ea) : NT == 2 ? launch_emit<2>(ctx, ea)
            : NT == 3 ? launch_emit<3>(ctx, ea) : launch_emit<4>(ctx, ea);
+}
+
+int32_t vmp_hmmw_chain(vmp_ctx *ctx, int64_t B, int T, int K, const double *E, const double *la0,
+                       const double *lA, const int32_t *labels, const uint8_t *mask, double *aw,
+                       double *cpart, double *gamma, double *z0, double *zz)
+{
+    const int64_t nwc = vmp_hmmw_chain_wgs(B, K);
+    HmmwChainArgs ca = {B, vmp_hmmw_chains_per_wg(B, K), T, K, E, la0, lA, labels, mask, aw, cpart,
+                        gamma, z0, zz};
+    switch (vmp_hmmf_kpad(K)) {
+    case 2: return launch_chain<2>(ctx, nwc, ca);
+    case 4: return launch_chain<4>(ctx, nwc, ca);
+    case 8: return launch_chain<8>(ctx, nwc, ca);
+    case 16: return launch_chain<16>(ctx, nwc, ca);
+    case 32: return launch_chain<32>(ctx, nwc, ca);
+    default: return launch_chain<64>(ctx, nwc, ca);
+    }
 }
 
 int32_t vmp_hmmw_stats(vmp_ctx *ctx, int64_t R, int D, int K, const double *Y, const double *gam,
@@ -573,16 +588,8 @@ int32_t vmp_hmm_wide_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t
             rc = vmp_hmmw_emit(ctx, R, D, K, Y, C, ldc, mask, E);
             if (rc != VMP_OK) return rc;
         }
-        HmmwChainArgs ca = {B, vmp_hmmw_chains_per_wg(B, K), T, K, emit ? E : nullptr, elog_a0,
-                            elog_A, labels, mask, aw, cpart, gamma, z0, zz};
-        switch (KP) {
-        case 2: rc = launch_chain<2>(ctx, nwc, ca); break;
-        case 4: rc = launch_chain<4>(ctx, nwc, ca); break;
-        case 8: rc = launch_chain<8>(ctx, nwc, ca); break;
-        case 16: rc = launch_chain<16>(ctx, nwc, ca); break;
-        case 32: rc = launch_chain<32>(ctx, nwc, ca); break;
-        default: rc = launch_chain<64>(ctx, nwc, ca); break;
-        }
+        rc = vmp_hmmw_chain(ctx, B, T, K, emit ? E : nullptr, elog_a0, elog_A, labels, mask, aw,
+                            cpart, gamma, z0, zz);
         if (rc != VMP_OK) return rc;
         rc = vmp_hmmw_stats(ctx, R, D, K, Y, aw, mask, spart);
         if (rc != VMP_OK) return rc;

@@ -35,6 +35,9 @@
 #define VMP_HMMW_SLAB_TILES 12    // 16-feature tiles of a slab: 4 wavefronts x 3 tiles
 #define VMP_HMMW_MAX_ROW_WGS 1024
 
+// LDS row stride of a 16 NT wide operand: rows 4 q + l4 of one matrix instruction in distinct banks
+__host__ __device__ constexpr int hmmw_stride(int NT) { return (NT * 16) % 32 == 0 ? NT * 16 + 16 : NT * 16; }
+
 // doubles the chain kernel leaves per workgroup: sum gamma_0, sum xi, sum log Z, sum gamma . e
 __host__ __device__ inline int64_t vmp_hmmw_chain_partial_doubles(int K)
 {
@@ -100,10 +103,15 @@ __host__ __device__ inline int64_t vmp_hmmw_workspace_doubles(int64_t B, int T, 
 // (vmp_hmm_seg.hip).  emit: E (R x KP) from Y, C and the mask; stats: vmp_hmmw_row_wgs(R, D, K)
 // partials from the in-place gamma; combine: adds nwc chain partials of
 // vmp_hmmw_chain_partial_doubles(K) doubles and the partials of stats in workgroup order, then
-// forms scal[2] and scal[3] with dot_ws (1024 doubles).
+// forms scal[2] and scal[3] with dot_ws (1024 doubles).  chain: the chain stage (kernel 2) alone,
+// for a pass with emission and statistics kernels of its own (vmp_hmm_mult.hip): E (B T x KP) or
+// null, gamma left in aw (B T x K), vmp_hmmw_chain_wgs(B, K) partials in cpart.
 struct vmp_ctx;
 int32_t vmp_hmmw_emit(vmp_ctx *ctx, int64_t R, int D, int K, const double *Y, const double *C,
                       int ldc, const uint8_t *mask, double *E);
+int32_t vmp_hmmw_chain(vmp_ctx *ctx, int64_t B, int T, int K, const double *E, const double *la0,
+                       const double *lA, const int32_t *labels, const uint8_t *mask, double *aw,
+                       double *cpart, double *gamma, double *z0, double *zz);
 int32_t vmp_hmmw_stats(vmp_ctx *ctx, int64_t R, int D, int K, const double *Y, const double *gam,
                        const uint8_t *mask, double *spart);
 int32_t vmp_hmmw_combine(vmp_ctx *ctx, int64_t nwc, int64_t nwr, int D, int K, const double *cpart,

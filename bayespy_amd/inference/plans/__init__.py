@@ -18,6 +18,7 @@ from .hmm_wide import WideHMMPlan
 from .hmm_seg import SegmentedHMMPlan
 from .hmm_seg_cat import SegmentedCategoricalHMMPlan
 from .hmm_vocab import VocabCategoricalHMMPlan
+from .hmm_mult import MultinomialHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
 from .dgmm_svi import DiagGaussianMixtureSVIPlan, MaskedDiagGaussianMixtureSVIPlan
@@ -95,6 +96,12 @@ OPT_IN_LONG_CHAINS = {HMMPlan: SegmentedHMMPlan, CategoricalHMMPlan: SegmentedCa
 # M > 128 with a reason).  Everything else is engine='fused'; every other engine value does not try
 # this form and keeps its answer; it is not combined with the other '+' suffixes
 OPT_IN_WORDS = {CategoricalHMMPlan: [VocabCategoricalHMMPlan]}
+# engine='fused+counts': the form of the discrete HMM block for multinomial emissions, a vector of
+# counts over M <= 1024 categories at every time step (plans/hmm_mult.py), a plan class of its
+# own, tried right after that block (which passes another emission family over).  Everything else
+# is engine='fused'; every other engine value does not try this form and keeps its answer; it is
+# not combined with the other '+' suffixes
+OPT_IN_COUNT_EMISSIONS = {CategoricalHMMPlan: [MultinomialHMMPlan]}
 
 
 def _with_masked(types):
@@ -127,6 +134,11 @@ def _with_wide_emissions(types):
 def _with_words(types):
     """``types`` with the plan classes of ``OPT_IN_WORDS`` inserted after their block."""
     return [Q for P in types for Q in [P] + OPT_IN_WORDS.get(P, [])]
+
+
+def _with_count_emissions(types):
+    """``types`` with the plan classes of ``OPT_IN_COUNT_EMISSIONS`` inserted after their block."""
+    return [Q for P in types for Q in [P] + OPT_IN_COUNT_EMISSIONS.get(P, [])]
 
 
 def _with_hyper(types):
@@ -173,6 +185,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or any(type(p) in v for v in OPT_IN_WIDE_EMISSIONS.values())
                                  or type(p) in OPT_IN_LONG_CHAINS.values()
                                  or any(type(p) in v for v in OPT_IN_WORDS.values())
+                                 or any(type(p) in v for v in OPT_IN_COUNT_EMISSIONS.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -215,7 +228,8 @@ def compile_model(nodes, engine=None, **options):
     emissions = engine == 'fused+emissions'
     chains = engine == 'fused+chains'
     words = engine == 'fused+words'
-    if batches or topics or hyper or emissions or chains or words:
+    counts = engine == 'fused+counts'
+    if batches or topics or hyper or emissions or chains or words or counts:
         engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
     if kept is not None and not topics \
@@ -230,6 +244,9 @@ def compile_model(nodes, engine=None, **options):
     if kept is not None and not words \
             and any(type(p) in v for p in kept for v in OPT_IN_WORDS.values()):
         kept = None             # the large-vocabulary form is kept only where it is asked for
+    if kept is not None and not counts \
+            and any(type(p) in v for p in kept for v in OPT_IN_COUNT_EMISSIONS.values()):
+        kept = None             # the multinomial-emission form is kept only where it is asked for
     if kept is not None and not hyper \
             and any(type(p) in v for p in kept for v in OPT_IN_HYPER.values()):
         kept = None             # a form with learnt concentrations is kept only where it is asked for
@@ -271,6 +288,8 @@ def compile_model(nodes, engine=None, **options):
         types = [OPT_IN_LONG_CHAINS.get(P, P) for P in types]
     if words:
         types = _with_words(types)
+    if counts:
+        types = _with_count_emissions(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

@@ -64,7 +64,8 @@ _KINDS = {'hmm': 'Gaussian', 'hmm_cat': 'categorical',
           'hmm_wide': 'Gaussian (the wide form, 9 <= D <= 32)',
           'hmm_seg': 'Gaussian (the long-chain form)',
           'hmm_seg_cat': 'categorical (the long-chain form)',
-          'hmm_vocab': 'categorical (the large-vocabulary form)'}
+          'hmm_vocab': 'categorical (the large-vocabulary form)',
+          'hmm_mult': 'multinomial'}
 
 
 def hmm_limits():

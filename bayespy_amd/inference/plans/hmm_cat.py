@@ -88,13 +88,15 @@ def _positive_constant(node, shape):
     return isinstance(node, Constant) and node.value.shape == shape and bool(np.all(node.value > 0))
 
 
-def _match(nodes, why, label=LABEL, limits=hmm_cat_limits, min_M=1, below=''):
-    """``min_M``, ``below``: the smallest vocabulary the form takes and what to say under it."""
+def _match(nodes, why, label=LABEL, limits=hmm_cat_limits, min_M=1, below='', family=Categorical,
+           extra=None):
+    """``min_M``, ``below``: the smallest vocabulary the form takes and what to say under it.
+    ``family``: the mixed distribution; ``extra(Y)``: a further reason of the form, or None."""
     for Y in nodes:
         if not isinstance(Y, Mixture) or not isinstance(Y.parents[0],
                                                         CategoricalMarkovChainToCategorical):
             continue
-        if Y.node_class is not Categorical:
+        if Y.node_class is not family:
             continue            # another emission family: plans/hmm.py gives its reason
 
         def no(msg, Y=Y):
@@ -175,6 +177,10 @@ def _match(nodes, why, label=LABEL, limits=hmm_cat_limits, min_M=1, below=''):
             continue
         if M < min_M:
             no('M = %d: %s' % (M, below))
+            continue
+        bad = extra(Y) if extra is not None else None
+        if bad:
+            no(bad)
             continue
         kids = [(Z, [Zc]), (Zc, [Y]), (Y, [])] \
             + [(n, [Z]) for n in (a0, A) if type(n) is Dirichlet] \
@@ -322,13 +328,17 @@ class CategoricalHMMPlan(HMMPlan):
             self.rt.sync_stream()
             self.kernels.dot(self.M * self.K, self.S, self.elogPt, self.ws_small, self.scal[4:5])
             s, chain = self._chain_terms()
-            t = dict(Y=float(s[4]), **chain)
+            t = dict(Y=self._y_term(s), **chain)
             if self.learnedP:
                 t['P'] = float(self.bndP.cpu().numpy()[0])
             t['total'] = sum(t.values())
             self._L = t
             self._L_version = self._version
         return _delta.bound_terms(self._L, self._delta)
+
+    def _y_term(self, s):
+        """<log p(Y)> from scal on the host: S . <log P>."""
+        return float(s[4])
 
     def get_moments(self, node):
         self._materialize()

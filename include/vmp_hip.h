@@ -1472,6 +1472,44 @@ int32_t vmp_hmm_vocab_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t M, int32_
                            double *ws, double *z0sum, double *xisum, double *S, double *scal,
                            double *gamma, double *z0, double *zz);
 
+/* Hidden Markov model with multinomial emissions: every time step carries a vector of counts over
+ * M categories (details: bayespy_amd/csrc/vmp_hmm_mult.hip, vmp_hmm_mult_dev.h)
+ *     Z = CategoricalMarkovChain(a0, A, states=T);  Y = Mixture(Z, Multinomial, n, P);  Y.observe(x)
+ * Three stages: E = X <log P>^T over the flattened (b, t) plate on the fp64 matrix cores, the chain
+ * kernel of vmp_hmm_wide_pass as it is (it reads E and leaves gamma in the workspace), and
+ * S = X^T Gamma on the matrix cores, split over word slabs and row ranges; a last kernel adds the
+ * partials.  A row of E is kept less its largest element, so that the recursion does not round at
+ * the magnitude of e (about -1000 for counts in the hundreds); the shifts are added back to
+ * scal[0] and scal[1] in a fixed order.  The categorical pass is the n = 1 case.
+ *   vmp_hmm_mult_limits (host only): *max_K = 64, *max_M = 1024, *max_count = 65534 (those of
+ *     vmp_mmm_pack, which writes x_packed).
+ *   vmp_hmm_mult_plan (host only): for (B, T, M, K) the chains of a workgroup of the chain kernel
+ *     *chains_per_wg and the scratch *workspace_doubles: E (B T KP, KP = K rounded up to a power
+ *     of two, at least 2), gamma (B T K), the partials, at most 16384 sums of row shifts, 1024.  T < 2 or a size below 1 (B below
+ *     0): VMP_ERR_INVALID; K or M above the limits: VMP_ERR_UNSUPPORTED; then a null pointer:
+ *     VMP_ERR_INVALID.
+ *   vmp_hmm_mult_pass: the contract of vmp_hmm_fused_pass_categorical, argument for argument, with
+ *     x_packed in the place of y: B T rows of M uint16 counts, dense and row-major, as vmp_mmm_pack
+ *     writes them.  e_t[k] = sum_m x_tm elogPt[m, k] at an observed step, 0 at a masked one, whose
+ *     row of x_packed is never used (anything may stand there); elogPt NULL: no emission term.
+ *     Out: z0sum, xisum, scal[0..3] as there; S (M, K) word-major = sum over the observed (b, t)
+ *     of x_{bt,m} gamma_{bt,k}; scal[1] = sum gamma . e; gamma, z0, zz on request.  With `labels`
+ *     gamma and xi are one-hot, scal[0] = scal[1] = 0.  A chain without an observed step adds
+ *     nothing to any sum.  ws: vmp_hmm_mult_plan's doubles.  x_packed must be 2-byte aligned (8
+ *     for the fast loads).  No atomics: one partial per workgroup, added in workgroup order, so
+ *     the bits of every output depend on the inputs and (B, T, M, K) alone, with or without the
+ *     optional outputs; a mask of ones gives the bits of a NULL mask.  B = 0 gives zeros.  The
+ *     argument checks, their order and the status codes are those of
+ *     vmp_hmm_fused_pass_categorical.  Nothing is launched after a refusal. */
+int32_t vmp_hmm_mult_limits(int32_t *max_K, int32_t *max_M, int32_t *max_count);
+int32_t vmp_hmm_mult_plan(int64_t B, int32_t T, int32_t M, int32_t K, int64_t *chains_per_wg,
+                          int64_t *workspace_doubles);
+int32_t vmp_hmm_mult_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t M, int32_t K,
+                          const uint16_t *x_packed, const double *elogPt, const double *elog_a0,
+                          const double *elog_A, const int32_t *labels, const uint8_t *mask,
+                          double *ws, double *z0sum, double *xisum, double *S, double *scal,
+                          double *gamma, double *z0, double *zz);
+
 /* Categorical mixture (latent class model): the plate pass of the fused block
  *     R = Dirichlet(a);  Z = Categorical(R, plates=(N, 1))
  *     P = Dirichlet(conc, plates=(D, K));  X = Mixture(Z, Categorical, P);  X.observe(x[, mask])

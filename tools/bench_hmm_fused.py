@@ -40,6 +40,14 @@ tests/hmm_models.py, Z from fixed random labels):
            length in use.  --wide-pass then times ``vmp_hmm_wide_pass``, the sequential chain
            stage, on the same state in the same process.
 
+  mult     (--emissions multinomial --engine fused+counts, --M 64,256,1024, --trials n) the legs
+           for the multinomial-emission form (inference/plans/hmm_mult.py): count vectors of n
+           trials drawn on the device, learned P, Z from fixed random labels; the pass is
+           ``vmp_hmm_mult_pass`` (4 M + 24 KP + 32 K bytes per chain step: the uint16 counts read by
+           the emission and the statistics kernel, E written once and read twice, the forward
+           state written and read and gamma written and read in its place); a ``kernels`` line
+           gives the device time of every kernel of one pass.
+
     python tools/bench_hmm_fused.py [--legs fused,pass,generic] [--B 20000] [--T 1000] [--steps 5]
                                     [--warmup 2] [--out profiles/...json]
     python tools/bench_hmm_fused.py --legs pass --observed 1.0,0.7 --ragged
@@ -50,6 +58,7 @@ reports the median and the extremes.
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -170,6 +179,91 @@ def categorical_legs(a, emit, M):
             emit(dict(leg='generic', error=str(exc)[:200]))
 
 
+def make_counts(B, T, M, K, n, seed=0):
+    """(x (B, T, M) uint8 on the device, z0): n trials per step from sticky chains."""
+    import torch
+    rs = np.random.RandomState(seed)
+    gen = torch.Generator(device='cuda').manual_seed(seed)
+    P = torch.from_numpy(rs.dirichlet(0.3 * np.ones(M), size=K)).cuda()
+    z = np.empty((B, T), dtype=np.int64)
+    z[:, 0] = rs.randint(K, size=B)
+    for t in range(1, T):                           # sticky chains
+        z[:, t] = np.where(rs.rand(B) < 0.9, z[:, t - 1], rs.randint(K, size=B))
+    zd = torch.from_numpy(z.reshape(-1)).cuda()
+    x = torch.zeros(B * T, M, dtype=torch.uint8, device='cuda')
+    for r0 in range(0, B * T, 1 << 18):             # in blocks of rows: the draws are int64
+        zr = zd[r0:r0 + (1 << 18)]
+        words = torch.multinomial(P, n * 64, replacement=True, generator=gen)     # K x (64 n)
+        pick = torch.randint(64, (zr.numel(), 1), device='cuda', generator=gen) * n \
+            + torch.arange(n, device='cuda')
+        idx = words[zr[:, None], pick]
+        cnt = torch.zeros(zr.numel(), M, dtype=torch.int32, device='cuda')
+        cnt.scatter_add_(1, idx, torch.ones_like(idx, dtype=torch.int32))
+        x[r0:r0 + (1 << 18)] = cnt.to(torch.uint8)
+    return x.reshape(B, T, M), rs.randint(K, size=(B, T))
+
+
+def multinomial_legs(a, emit, M):
+    import torch
+    import bayespy_amd.nodes as N_
+    from bayespy_amd.inference import VB
+    B, T, K, n = a.B, a.T, a.K, a.trials
+    assert n <= 255
+    x, z0 = make_counts(B, T, M, K, n)
+    legs = a.legs.split(',')
+    KP = max(2, 1 << (K - 1).bit_length())
+
+    def build_mult(engine):
+        a0 = N_.Dirichlet(1e-3 * np.ones(K), name='a0')
+        A = N_.Dirichlet(1e-3 * np.ones((K, K)), name='A')
+        P = N_.Dirichlet(np.ones((K, M)), name='P')
+        Z = N_.CategoricalMarkovChain(a0, A, states=T, plates=(B,), name='Z')
+        Y = N_.Mixture(Z, N_.Multinomial, n, P, name='Y')
+        Y.observe(x if engine != 'generic' else x.cpu().numpy())     # generic: host counts
+        Z.initialize_from_value(z0)
+        Q = VB(Y, P, A, a0, Z, engine=engine)
+        Q.ignore_bound_checks = True
+        return Q
+    if 'fused' in legs or 'pass' in legs:
+        torch.cuda.reset_peak_memory_stats()
+        Q = build_mult(a.engine)
+        plan = Q.plans[0]
+        assert type(plan).__name__ == 'MultinomialHMMPlan'
+        emit(dict(leg='fused', what='Q.update()',
+                  **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
+        emit(dict(leg='fused_bound', L=float(Q.L[Q.iter - 1]),
+                  peak_GB=torch.cuda.max_memory_allocated() / 1e9))
+        if 'pass' in legs:
+            r = timed(lambda: plan._run_pass(refresh=False), a.steps, a.warmup)
+            nbytes = 4 * M + 24 * KP + 32 * K
+            emit(dict(leg='pass', what='vmp_hmm_mult_pass', bytes_per_chain_step=nbytes,
+                      GB_per_s=float(B) * T * nbytes / (1e-3 * r['ms_median']) / 1e9,
+                      Gflop_per_s_each_product=2.0 * B * T * M * K / (1e-3 * r['ms_median']) / 1e9,
+                      **r))
+            from torch.profiler import profile, ProfilerActivity
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                plan._run_pass(refresh=False)
+                torch.cuda.synchronize()
+            ms = {}
+            for e in prof.key_averages():
+                name = re.search(r'\w+_kernel', e.key)
+                if name and e.device_time_total > 0:
+                    ms[name.group(0)] = ms.get(name.group(0), 0.0) + 1e-3 * e.device_time_total
+            emit(dict(leg='kernels', ms=ms))
+        del Q, plan
+        torch.cuda.empty_cache()
+    if 'generic' in legs:
+        try:
+            torch.cuda.reset_peak_memory_stats()
+            Q = build_mult('generic')
+            emit(dict(leg='generic', what='Q.update()',
+                      **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
+            emit(dict(leg='generic_bound', L=float(Q.L[Q.iter - 1]),
+                      peak_GB=torch.cuda.max_memory_allocated() / 1e9))
+        except (RuntimeError, MemoryError) as exc:         # out of memory at this size
+            emit(dict(leg='generic', error=str(exc)[:200]))
+
+
 def timed(fn, steps, warmup):
     import torch
     for _ in range(warmup):
@@ -199,12 +293,15 @@ def main():
                     help='comma-separated fractions of observed steps for the masked pass')
     ap.add_argument('--ragged', action='store_true',
                     help='masked pass with sequence lengths uniform in 1 ... T')
-    ap.add_argument('--emissions', default='gaussian', choices=('gaussian', 'categorical'))
+    ap.add_argument('--emissions', default='gaussian', choices=('gaussian', 'categorical', 'multinomial'))
+    ap.add_argument('--trials', type=int, default=50,
+                    help='multinomial legs: trials n of every step (at most 255)')
     ap.add_argument('--M', default='16',
                     help='words of the categorical legs; comma-separated: the legs once per value, '
                          'in one process')
     ap.add_argument('--engine', default='fused',
-                    choices=('fused', 'fused+emissions', 'fused+chains', 'fused+words'))
+                    choices=('fused', 'fused+emissions', 'fused+chains', 'fused+words',
+                             'fused+counts'))
     ap.add_argument('--seg-len', default='0',
                     help='fused+chains: comma-separated segment lengths of the pass legs (0 = the '
                          "library's choice)")
@@ -223,6 +320,16 @@ def main():
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
 
+    if a.emissions == 'multinomial':
+        shape = dict(B=B, T=T, M=0, K=K, emissions='multinomial', trials=a.trials)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'hmm_fused', 'bench_hmm_mult.json')
+        for M in a.M.split(','):
+            shape['M'] = int(M)
+            multinomial_legs(a, emit, int(M))
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        return
     if cat:
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'hmm_fused', 'bench_hmm_cat.json')
