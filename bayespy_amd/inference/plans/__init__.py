@@ -19,6 +19,7 @@ from .hmm_seg import SegmentedHMMPlan
 from .hmm_seg_cat import SegmentedCategoricalHMMPlan
 from .hmm_vocab import VocabCategoricalHMMPlan
 from .hmm_mult import MultinomialHMMPlan
+from .hmm_diag import DiagGaussianHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
 from .dgmm_svi import DiagGaussianMixtureSVIPlan, MaskedDiagGaussianMixtureSVIPlan
@@ -102,6 +103,12 @@ OPT_IN_WORDS = {CategoricalHMMPlan: [VocabCategoricalHMMPlan]}
 # is engine='fused'; every other engine value does not try this form and keeps its answer; it is
 # not combined with the other '+' suffixes
 OPT_IN_COUNT_EMISSIONS = {CategoricalHMMPlan: [MultinomialHMMPlan]}
+# engine='fused+diagonal': the form of the HMM block for diagonal-Gaussian emissions, one precision
+# per dimension and up to 1024 dimensions (plans/hmm_diag.py), a plan class of its own, tried right
+# after that block (which declines a mixed GaussianARD with a reason).  Everything else is
+# engine='fused'; every other engine value does not try this form and keeps its answer; it is
+# not combined with the other '+' suffixes
+OPT_IN_DIAGONAL_EMISSIONS = {HMMPlan: [DiagGaussianHMMPlan]}
 
 
 def _with_masked(types):
@@ -139,6 +146,11 @@ def _with_words(types):
 def _with_count_emissions(types):
     """``types`` with the plan classes of ``OPT_IN_COUNT_EMISSIONS`` inserted after their block."""
     return [Q for P in types for Q in [P] + OPT_IN_COUNT_EMISSIONS.get(P, [])]
+
+
+def _with_diagonal_emissions(types):
+    """``types`` with the plan classes of ``OPT_IN_DIAGONAL_EMISSIONS`` inserted after their block."""
+    return [Q for P in types for Q in [P] + OPT_IN_DIAGONAL_EMISSIONS.get(P, [])]
 
 
 def _with_hyper(types):
@@ -186,6 +198,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or type(p) in OPT_IN_LONG_CHAINS.values()
                                  or any(type(p) in v for v in OPT_IN_WORDS.values())
                                  or any(type(p) in v for v in OPT_IN_COUNT_EMISSIONS.values())
+                                 or any(type(p) in v for v in OPT_IN_DIAGONAL_EMISSIONS.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -229,7 +242,8 @@ def compile_model(nodes, engine=None, **options):
     chains = engine == 'fused+chains'
     words = engine == 'fused+words'
     counts = engine == 'fused+counts'
-    if batches or topics or hyper or emissions or chains or words or counts:
+    diagonal = engine == 'fused+diagonal'
+    if batches or topics or hyper or emissions or chains or words or counts or diagonal:
         engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
     if kept is not None and not topics \
@@ -247,6 +261,9 @@ def compile_model(nodes, engine=None, **options):
     if kept is not None and not counts \
             and any(type(p) in v for p in kept for v in OPT_IN_COUNT_EMISSIONS.values()):
         kept = None             # the multinomial-emission form is kept only where it is asked for
+    if kept is not None and not diagonal \
+            and any(type(p) in v for p in kept for v in OPT_IN_DIAGONAL_EMISSIONS.values()):
+        kept = None             # the diagonal-emission form is kept only where it is asked for
     if kept is not None and not hyper \
             and any(type(p) in v for p in kept for v in OPT_IN_HYPER.values()):
         kept = None             # a form with learnt concentrations is kept only where it is asked for
@@ -290,6 +307,8 @@ def compile_model(nodes, engine=None, **options):
         types = _with_words(types)
     if counts:
         types = _with_count_emissions(types)
+    if diagonal:
+        types = _with_diagonal_emissions(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

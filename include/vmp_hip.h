@@ -1510,6 +1510,47 @@ int32_t vmp_hmm_mult_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t M, int32_t
                           double *ws, double *z0sum, double *xisum, double *S, double *scal,
                           double *gamma, double *z0, double *zz);
 
+/* Hidden Markov model with diagonal-Gaussian emissions: every time step carries D real numbers with
+ * one precision per dimension (details: bayespy_amd/csrc/vmp_hmm_diag.hip, vmp_hmm_diag_dev.h)
+ *     Z = CategoricalMarkovChain(a0, A, states=T);  mu = GaussianARD(m0, beta0, shape=(D,), plates=(K,))
+ *     tau = Gamma(a0, b0, plates=(K, D));  Y = Mixture(Z, GaussianARD, mu, tau, 1);  Y.observe(y)
+ * The three stages of vmp_hmm_mult_pass with the tables of vmp_dgmm_tables: E = g + Y h + (Y o Y) q
+ * over the flattened (b, t) plate as one contraction of length 2 D on the fp64 matrix cores, the
+ * chain kernel of vmp_hmm_wide_pass as it is, and S1 = Y^T Gamma, S2 = (Y o Y)^T Gamma on the matrix
+ * cores, split over dimension slabs and row ranges; a last kernel adds the partials.  y is read
+ * once by each of the two plate kernels.  A row of E is kept less its largest element, so that the
+ * recursion does not round at the magnitude of e (1/2 tau y^2 reaches 1e5 for data far from 0); the
+ * shifts are added back to scal[0] and scal[1] in a fixed order.  The constant -1/2 log 2 pi per
+ * element is the same for every state and is left to the caller, as in vmp_dgmm_pass.
+ *   vmp_hmm_diag_limits (host only): *max_K = 64, *max_D = 1024.
+ *   vmp_hmm_diag_plan (host only): for (B, T, D, K) the chains of a workgroup of the chain kernel
+ *     *chains_per_wg and the scratch *workspace_doubles: E (B T KP, KP = K rounded up to a power
+ *     of two, at least 2), gamma (B T K), the partials, at most 16384 sums of row shifts, 1024.
+ *     T < 2 or a size below 1 (B below 0): VMP_ERR_INVALID; K or D above the limits:
+ *     VMP_ERR_UNSUPPORTED; then a null pointer: VMP_ERR_INVALID.
+ *   vmp_hmm_diag_pass: the contract of vmp_hmm_mult_pass with y (B T rows of D doubles, dense and
+ *     row-major) in the place of x_packed and the tables h, q (D x K, element (d, k) at d K + k)
+ *     and g (K) in the place of elogPt.  e_t[k] = g[k] + sum_d (y_td h[d, k] + y_td^2 q[d, k]) at an
+ *     observed step, 0 at a masked one, whose row of y is never loaded (NaN may stand there);
+ *     h NULL: no emission term (q and g are then not read; with h they are required).
+ *     Out: z0sum, xisum, scal[0..3] as there; S1, S2 (D x K, the layout vmp_dgmm_update reads) =
+ *     sum over the observed (b, t) of y_d gamma_k and of y_d^2 gamma_k; Nk (K) = sum over the
+ *     observed (b, t) of gamma_k; scal[1] = sum gamma . e; gamma, z0, zz on request.  With
+ *     `labels` gamma and xi are one-hot, scal[0] = scal[1] = 0.  A chain without an observed step
+ *     adds nothing to any sum.  ws: vmp_hmm_diag_plan's doubles.  No atomics: one partial per
+ *     workgroup, added in workgroup order, so the bits of every output depend on the inputs and
+ *     (B, T, D, K) alone, with or without the optional outputs; a mask of ones gives the bits of a
+ *     NULL mask.  B = 0 gives zeros.  The argument checks, their order and the status codes are
+ *     those of vmp_hmm_mult_pass.  Nothing is launched after a refusal. */
+int32_t vmp_hmm_diag_limits(int32_t *max_K, int32_t *max_D);
+int32_t vmp_hmm_diag_plan(int64_t B, int32_t T, int32_t D, int32_t K, int64_t *chains_per_wg,
+                          int64_t *workspace_doubles);
+int32_t vmp_hmm_diag_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t D, int32_t K, const double *y,
+                          const double *h, const double *q, const double *g, const double *elog_a0,
+                          const double *elog_A, const int32_t *labels, const uint8_t *mask,
+                          double *ws, double *z0sum, double *xisum, double *S1, double *S2,
+                          double *Nk, double *scal, double *gamma, double *z0, double *zz);
+
 /* Categorical mixture (latent class model): the plate pass of the fused block
  *     R = Dirichlet(a);  Z = Categorical(R, plates=(N, 1))
  *     P = Dirichlet(conc, plates=(D, K));  X = Mixture(Z, Categorical, P);  X.observe(x[, mask])

@@ -48,6 +48,16 @@ tests/hmm_models.py, Z from fixed random labels):
            state written and read and gamma written and read in its place); a ``kernels`` line
            gives the device time of every kernel of one pass.
 
+  diag     (--emissions diagonal --engine fused+diagonal, --dims 64,256,1024) the legs for the
+           diagonal-Gaussian-emission form (inference/plans/hmm_diag.py): y drawn on the device,
+           B capped so that y stays at or below 2^30 doubles, Z from fixed random labels; the pass
+           is ``vmp_hmm_diag_pass`` (16 D + 24 KP + 32 K bytes per chain step); a ``kernels`` line
+           gives the device time of every kernel of one pass and the rate of the two plate kernels
+           against one read of y, a ``kernels_mult`` line the kernels of ``vmp_hmm_mult_pass`` at
+           the same (B, T, K) in the same process (the chain stage is the same kernel); the
+           ``compare`` lines time ``Q.update()`` on this form and on the generic engine at
+           --generic-B chains, with peak memory above the resident y and the bound.
+
     python tools/bench_hmm_fused.py [--legs fused,pass,generic] [--B 20000] [--T 1000] [--steps 5]
                                     [--warmup 2] [--out profiles/...json]
     python tools/bench_hmm_fused.py --legs pass --observed 1.0,0.7 --ragged
@@ -264,6 +274,105 @@ def multinomial_legs(a, emit, M):
             emit(dict(leg='generic', error=str(exc)[:200]))
 
 
+def kernel_ms(fn):
+    """Device time per kernel of one call of ``fn`` (torch profiler), by kernel name."""
+    import torch
+    from torch.profiler import profile, ProfilerActivity
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    ms = {}
+    for e in prof.key_averages():
+        name = re.search(r'\w+_kernel', e.key)
+        if name and e.device_time_total > 0:
+            ms[name.group(0)] = ms.get(name.group(0), 0.0) + 1e-3 * e.device_time_total
+    return ms
+
+
+def diagonal_legs(a, emit, D):
+    import torch
+    import bayespy_amd.nodes as N_
+    from bayespy_amd.inference import VB
+    T, K = a.T, a.K
+    B = min(a.B, (1 << 30) // (T * D))              # y stays at or below 2^30 doubles
+    legs = a.legs.split(',')
+    KP = max(2, 1 << (K - 1).bit_length())
+    rs = np.random.RandomState(0)
+    gen = torch.Generator(device='cuda').manual_seed(0)
+    z = np.empty((B, T), dtype=np.int64)
+    z[:, 0] = rs.randint(K, size=B)
+    for t in range(1, T):                           # sticky chains
+        z[:, t] = np.where(rs.rand(B) < 0.9, z[:, t - 1], rs.randint(K, size=B))
+    means = 3.0 * torch.randn(K, D, dtype=torch.float64, device='cuda', generator=gen)
+    y = torch.randn(B, T, D, dtype=torch.float64, device='cuda', generator=gen)
+    y += means[torch.from_numpy(z).cuda()]
+    z0 = rs.randint(K, size=(B, T))
+
+    def build_diag(engine, Bm):
+        a0 = N_.Dirichlet(1e-3 * np.ones(K), name='a0')
+        A = N_.Dirichlet(1e-3 * np.ones((K, K)), name='A')
+        Z = N_.CategoricalMarkovChain(a0, A, states=T, plates=(Bm,), name='Z')
+        mu = N_.GaussianARD(0, 1e-3, shape=(D,), plates=(K,), name='mu')
+        tau = N_.Gamma(1e-3, 1e-3, plates=(K, D), name='tau')
+        Y = N_.Mixture(Z, N_.GaussianARD, mu, tau, 1, name='Y')
+        Y.observe(y[:Bm] if engine != 'generic' else y[:Bm].cpu().numpy())
+        Z.initialize_from_value(z0[:Bm])
+        Q = VB(Y, mu, tau, A, a0, Z, engine=engine)
+        Q.ignore_bound_checks = True
+        return Q
+    if 'fused' in legs or 'pass' in legs:
+        torch.cuda.reset_peak_memory_stats()
+        Q = build_diag(a.engine, B)
+        plan = Q.plans[0]
+        assert type(plan).__name__ == 'DiagGaussianHMMPlan'
+        emit(dict(B=B, leg='fused', what='Q.update()',
+                  **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
+        emit(dict(B=B, leg='fused_bound', L=float(Q.L[Q.iter - 1]),
+                  peak_GB=torch.cuda.max_memory_allocated() / 1e9))
+        if 'pass' in legs:
+            r = timed(lambda: plan._run_pass(refresh=False), a.steps, a.warmup)
+            nbytes = 16 * D + 24 * KP + 32 * K
+            emit(dict(B=B, leg='pass', what='vmp_hmm_diag_pass', bytes_per_chain_step=nbytes,
+                      GB_per_s=float(B) * T * nbytes / (1e-3 * r['ms_median']) / 1e9, **r))
+            ms = kernel_ms(lambda: plan._run_pass(refresh=False))
+            # each plate kernel reads y once: 8 B T D bytes; 4 B T D K flops (y and y^2)
+            floor = {k: dict(TB_per_s=8.0 * B * T * D / (1e-3 * v) / 1e12,
+                             Tflop_per_s=4.0 * B * T * D * K / (1e-3 * v) / 1e12)
+                     for k, v in ms.items() if k in ('hmmd_emit_kernel', 'hmmd_stats_kernel')}
+            emit(dict(B=B, leg='kernels', ms=ms, against_y_read_once=floor))
+            # the chain stage inside vmp_hmm_mult_pass at the same (B, T, K), in the same process
+            from bayespy_amd.inference.plans.hmm_mult import MultHMMKernels
+            mk, M = MultHMMKernels(plan.rt), 64
+            xp = torch.randint(0, 4, (B * T, M), device='cuda', generator=gen).to(torch.int16)
+            Pt = torch.log_softmax(torch.randn(K, M, dtype=torch.float64, device='cuda',
+                                               generator=gen), -1).T.contiguous()
+            ws = plan.rt.empty(int(mk.plan(B, T, M, K)[1]))
+            S = plan.rt.zeros(M, K)
+            run = lambda: mk.pass_(B, T, M, K, xp, Pt, plan.used_a0, plan.used_A, None, None, ws,  # noqa: E731
+                                   plan.rt.zeros(K), plan.rt.zeros(K, K), S, plan.rt.zeros(8))
+            timed(run, 1, a.warmup)
+            emit(dict(B=B, leg='kernels_mult', what='vmp_hmm_mult_pass, M = 64', ms=kernel_ms(run)))
+            del xp, ws
+        del Q, plan
+        torch.cuda.empty_cache()
+    if 'generic' in legs:
+        Bm = min(B, a.generic_B)
+        for engine in (a.engine, 'generic'):
+            try:
+                torch.cuda.empty_cache()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()        # y of the full B stays resident
+                Q = build_diag(engine, Bm)
+                emit(dict(B=Bm, leg='compare', engine=engine, what='Q.update()',
+                          **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
+                emit(dict(B=Bm, leg='compare_bound', engine=engine, iterations=int(Q.iter),
+                          L=float(Q.L[Q.iter - 1]),
+                          peak_GB_above_y=(torch.cuda.max_memory_allocated() - base) / 1e9))
+                del Q
+            except (RuntimeError, MemoryError, NotImplementedError) as exc:
+                emit(dict(B=Bm, leg='compare', engine=engine, error=str(exc)[:200]))
+
+
 def timed(fn, steps, warmup):
     import torch
     for _ in range(warmup):
@@ -293,7 +402,7 @@ def main():
                     help='comma-separated fractions of observed steps for the masked pass')
     ap.add_argument('--ragged', action='store_true',
                     help='masked pass with sequence lengths uniform in 1 ... T')
-    ap.add_argument('--emissions', default='gaussian', choices=('gaussian', 'categorical', 'multinomial'))
+    ap.add_argument('--emissions', default='gaussian', choices=('gaussian', 'categorical', 'multinomial', 'diagonal'))
     ap.add_argument('--trials', type=int, default=50,
                     help='multinomial legs: trials n of every step (at most 255)')
     ap.add_argument('--M', default='16',
@@ -301,7 +410,12 @@ def main():
                          'in one process')
     ap.add_argument('--engine', default='fused',
                     choices=('fused', 'fused+emissions', 'fused+chains', 'fused+words',
-                             'fused+counts'))
+                             'fused+counts', 'fused+diagonal'))
+    ap.add_argument('--dims', default='64,256,1024',
+                    help='diagonal legs: comma-separated D, the legs once per value; B is capped '
+                         'so that y stays at or below 2^30 doubles')
+    ap.add_argument('--generic-B', type=int, default=64,
+                    help='diagonal legs: chains of the comparison with the generic engine')
     ap.add_argument('--seg-len', default='0',
                     help='fused+chains: comma-separated segment lengths of the pass legs (0 = the '
                          "library's choice)")
@@ -320,6 +434,16 @@ def main():
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
 
+    if a.emissions == 'diagonal':
+        shape = dict(T=T, D=0, K=K, emissions='diagonal')
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'hmm_fused', 'bench_hmm_diag.json')
+        for D in a.dims.split(','):
+            shape['D'] = int(D)
+            diagonal_legs(a, emit, int(D))
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        return
     if a.emissions == 'multinomial':
         shape = dict(B=B, T=T, M=0, K=K, emissions='multinomial', trials=a.trials)
         if a.out is None:
