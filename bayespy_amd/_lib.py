@@ -303,6 +303,9 @@ SIGNATURES = {
     'vmp_hmm_mult_limits': (c_i32, [P(c_i32), P(c_i32), P(c_i32)]),
     'vmp_hmm_mult_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_hmm_mult_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 14),
+    'vmp_hmm_states_limits': (c_i32, [P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
+    'vmp_hmm_states_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
+    'vmp_hmm_states_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 14),
     'vmp_hmm_diag_limits': (c_i32, [P(c_i32), P(c_i32)]),
     'vmp_hmm_diag_plan': (c_i32, [c_i64, c_i32, c_i32, c_i32, P(c_i64), P(c_i64)]),
     'vmp_hmm_diag_pass': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32] + [c_vp] * 18),

@@ -303,6 +303,51 @@ int32_t launch_stats(vmp_ctx *ctx, int64_t nwr, const HmmmStatsArgs &a)
 
 }  // namespace
 
+// the stages around a chain stage (vmp_hmm_mult_dev.h); NT = 8 serves the wide-state pass
+int32_t vmp_hmmm_stages(vmp_ctx *ctx, int64_t B, int T, int M, int K, int64_t nwc,
+                        vmp_hmmm_chain_fn chain, const uint16_t *x_packed, const double *elogPt,
+                        const double *elog_a0, const double *elog_A, const int32_t *labels,
+                        const uint8_t *mask, double *ws, double *z0sum, double *xisum, double *S,
+                        double *scal, double *gamma, double *z0, double *zz)
+{
+    const int KP = vmp_hmmf_kpad(K), NT = vmp_hmmm_state_tiles(K);
+    const int64_t R = B * (int64_t)T;
+    const int64_t nwr = vmp_hmmm_row_wgs(R, M, K);
+    const int64_t per = vmp_hmmw_chain_partial_doubles(K);
+    double *E = ws, *aw = E + R * KP, *cpart = aw + R * K, *spart = cpart + nwc * per;
+    double *shift = spart + nwr * (int64_t)M * K, *dot_ws = shift + 4 * vmp_hmmm_emit_wgs(R);
+    const int fast = ((uintptr_t)x_packed & 7) == 0;
+    int32_t rc = VMP_OK;
+    const bool emit = R > 0 && elogPt && !labels;
+    if (R > 0) {
+        if (emit) {
+            HmmmEmitArgs ea = {R, (R + 63) / 64, M, K, KP, fast, x_packed, elogPt, mask, E, shift};
+            rc = NT == 1 ? launch_emit<1>(ctx, ea) : NT == 2 ? launch_emit<2>(ctx, ea)
+                 : NT == 4 ? launch_emit<4>(ctx, ea) : launch_emit<8>(ctx, ea);
+            if (rc != VMP_OK) return rc;
+        }
+        rc = chain(ctx, B, T, K, emit ? E : nullptr, elog_a0, elog_A, labels, mask, aw, cpart, gamma,
+                   z0, zz);
+        if (rc != VMP_OK) return rc;
+        HmmmStatsArgs sa = {R, vmp_hmmm_rows_per_wg(R, M, K), M, K, fast, x_packed, aw, mask, spart};
+        rc = NT == 1 ? launch_stats<1>(ctx, nwr, sa) : NT == 2 ? launch_stats<2>(ctx, nwr, sa)
+             : NT == 4 ? launch_stats<4>(ctx, nwr, sa) : launch_stats<8>(ctx, nwr, sa);
+        if (rc != VMP_OK) return rc;
+    }
+    const int64_t ne = per + (int64_t)M * K;
+    hipLaunchKernelGGL(hmmm_combine_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0,
+                       ctx->stream, nwc, nwr, M, K, cpart, spart, z0sum, xisum, S, scal);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    if (emit) {
+        hipLaunchKernelGGL(hmmm_shift_kernel, dim3(1), dim3(256), 0, ctx->stream,
+                           4 * vmp_hmmm_emit_wgs(R), shift, scal);
+        VMP_HIP_CHECK(ctx, hipGetLastError());
+    }
+    rc = vmp_lda_dot(ctx, K, z0sum, elog_a0, dot_ws, scal + 2);
+    if (rc != VMP_OK) return rc;
+    return vmp_lda_dot(ctx, (int64_t)K * K, xisum, elog_A, dot_ws, scal + 3);
+}
+
 extern "C" {
 
 int32_t vmp_hmm_mult_limits(int32_t *max_K, int32_t *max_M, int32_t *max_count)
@@ -338,42 +383,8 @@ int32_t vmp_hmm_mult_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t M, int32_t
     VMP_REQUIRE(ctx, ctx && elog_a0 && elog_A && ws && z0sum && xisum && S && scal
                      && (B == 0 || x_packed), VMP_ERR_INVALID, "null argument");
     VMP_FLUSH_SMALL(ctx);
-    const int KP = vmp_hmmf_kpad(K), NT = vmp_hmmm_state_tiles(K);
-    const int64_t R = B * (int64_t)T;
-    const int64_t nwc = vmp_hmmw_chain_wgs(B, K), nwr = vmp_hmmm_row_wgs(R, M, K);
-    const int64_t per = vmp_hmmw_chain_partial_doubles(K);
-    double *E = ws, *aw = E + R * KP, *cpart = aw + R * K, *spart = cpart + nwc * per;
-    double *shift = spart + nwr * (int64_t)M * K, *dot_ws = shift + 4 * vmp_hmmm_emit_wgs(R);
-    const int fast = ((uintptr_t)x_packed & 7) == 0;
-    int32_t rc = VMP_OK;
-    const bool emit = R > 0 && elogPt && !labels;
-    if (R > 0) {
-        if (emit) {
-            HmmmEmitArgs ea = {R, (R + 63) / 64, M, K, KP, fast, x_packed, elogPt, mask, E, shift};
-            rc = NT == 1 ? launch_emit<1>(ctx, ea) : NT == 2 ? launch_emit<2>(ctx, ea)
-                                                             : launch_emit<4>(ctx, ea);
-            if (rc != VMP_OK) return rc;
-        }
-        rc = vmp_hmmw_chain(ctx, B, T, K, emit ? E : nullptr, elog_a0, elog_A, labels, mask, aw,
-                            cpart, gamma, z0, zz);
-        if (rc != VMP_OK) return rc;
-        HmmmStatsArgs sa = {R, vmp_hmmm_rows_per_wg(R, M, K), M, K, fast, x_packed, aw, mask, spart};
-        rc = NT == 1 ? launch_stats<1>(ctx, nwr, sa) : NT == 2 ? launch_stats<2>(ctx, nwr, sa)
-                                                               : launch_stats<4>(ctx, nwr, sa);
-        if (rc != VMP_OK) return rc;
-    }
-    const int64_t ne = per + (int64_t)M * K;
-    hipLaunchKernelGGL(hmmm_combine_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0,
-                       ctx->stream, nwc, nwr, M, K, cpart, spart, z0sum, xisum, S, scal);
-    VMP_HIP_CHECK(ctx, hipGetLastError());
-    if (emit) {
-        hipLaunchKernelGGL(hmmm_shift_kernel, dim3(1), dim3(256), 0, ctx->stream,
-                           4 * vmp_hmmm_emit_wgs(R), shift, scal);
-        VMP_HIP_CHECK(ctx, hipGetLastError());
-    }
-    rc = vmp_lda_dot(ctx, K, z0sum, elog_a0, dot_ws, scal + 2);
-    if (rc != VMP_OK) return rc;
-    return vmp_lda_dot(ctx, (int64_t)K * K, xisum, elog_A, dot_ws, scal + 3);
+    return vmp_hmmm_stages(ctx, B, T, M, K, vmp_hmmw_chain_wgs(B, K), vmp_hmmw_chain, x_packed, elogPt,
+                           elog_a0, elog_A, labels, mask, ws, z0sum, xisum, S, scal, gamma, z0, zz);
 }
 
 }  // extern "C"

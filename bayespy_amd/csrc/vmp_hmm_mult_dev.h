@@ -84,3 +84,19 @@ __host__ __device__ inline int64_t vmp_hmmm_workspace_doubles(int64_t B, int T, 
            + vmp_hmmw_chain_wgs(B, K) * vmp_hmmw_chain_partial_doubles(K)
            + vmp_hmmm_row_wgs(R, M, K) * (int64_t)M * K + 4 * vmp_hmmm_emit_wgs(R) + 1024;
 }
+
+#ifdef __HIPCC__
+// The stages of the pass as one host call (defined in vmp_hmm_mult.hip) around a chain stage with
+// the arguments of vmp_hmmw_chain that leaves nwc partials: vmp_hmm_mult_pass gives
+// vmp_hmmw_chain, the wide-state pass (vmp_hmm_states.hip, K <= 128) its own.  The arguments are
+// checked by the caller; ws is laid out as E (R KP), gamma (R K), nwc chain partials, the
+// partials of S, the shifts, 1024 doubles.
+typedef int32_t (*vmp_hmmm_chain_fn)(vmp_ctx *, int64_t, int, int, const double *, const double *,
+                                     const double *, const int32_t *, const uint8_t *, double *,
+                                     double *, double *, double *, double *);
+int32_t vmp_hmmm_stages(vmp_ctx *ctx, int64_t B, int T, int M, int K, int64_t nwc,
+                        vmp_hmmm_chain_fn chain, const uint16_t *x_packed, const double *elogPt,
+                        const double *elog_a0, const double *elog_A, const int32_t *labels,
+                        const uint8_t *mask, double *ws, double *z0sum, double *xisum, double *S,
+                        double *scal, double *gamma, double *z0, double *zz);
+#endif

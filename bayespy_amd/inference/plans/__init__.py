@@ -20,6 +20,7 @@ from .hmm_seg_cat import SegmentedCategoricalHMMPlan
 from .hmm_vocab import VocabCategoricalHMMPlan
 from .hmm_mult import MultinomialHMMPlan
 from .hmm_diag import DiagGaussianHMMPlan
+from .hmm_states import WideStateMultinomialHMMPlan
 from .dgmm import DiagGaussianMixturePlan
 from .dgmm_masked import MaskedDiagGaussianMixturePlan
 from .dgmm_svi import DiagGaussianMixtureSVIPlan, MaskedDiagGaussianMixtureSVIPlan
@@ -109,6 +110,12 @@ OPT_IN_COUNT_EMISSIONS = {CategoricalHMMPlan: [MultinomialHMMPlan]}
 # engine='fused'; every other engine value does not try this form and keeps its answer; it is
 # not combined with the other '+' suffixes
 OPT_IN_DIAGONAL_EMISSIONS = {HMMPlan: [DiagGaussianHMMPlan]}
+# engine='fused+states': the form of the multinomial-emission HMM block for 65 to 128 states
+# (plans/hmm_states.py: the chain pass on the matrix cores), a plan class of its own, tried right
+# after that block (which declines K > 64 with a reason).  Everything else is
+# engine='fused+counts'; every other engine value does not try this form and keeps its answer; it
+# is not combined with the other '+' suffixes
+OPT_IN_WIDE_STATES = {MultinomialHMMPlan: [WideStateMultinomialHMMPlan]}
 
 
 def _with_masked(types):
@@ -151,6 +158,11 @@ def _with_count_emissions(types):
 def _with_diagonal_emissions(types):
     """``types`` with the plan classes of ``OPT_IN_DIAGONAL_EMISSIONS`` inserted after their block."""
     return [Q for P in types for Q in [P] + OPT_IN_DIAGONAL_EMISSIONS.get(P, [])]
+
+
+def _with_wide_states(types):
+    """``types`` with the plan classes of ``OPT_IN_WIDE_STATES`` inserted after their block."""
+    return [Q for P in types for Q in [P] + OPT_IN_WIDE_STATES.get(P, [])]
 
 
 def _with_hyper(types):
@@ -199,6 +211,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or any(type(p) in v for v in OPT_IN_WORDS.values())
                                  or any(type(p) in v for v in OPT_IN_COUNT_EMISSIONS.values())
                                  or any(type(p) in v for v in OPT_IN_DIAGONAL_EMISSIONS.values())
+                                 or any(type(p) in v for v in OPT_IN_WIDE_STATES.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -241,7 +254,8 @@ def compile_model(nodes, engine=None, **options):
     emissions = engine == 'fused+emissions'
     chains = engine == 'fused+chains'
     words = engine == 'fused+words'
-    counts = engine == 'fused+counts'
+    states = engine == 'fused+states'
+    counts = engine == 'fused+counts' or states
     diagonal = engine == 'fused+diagonal'
     if batches or topics or hyper or emissions or chains or words or counts or diagonal:
         engine = 'fused'
@@ -264,6 +278,9 @@ def compile_model(nodes, engine=None, **options):
     if kept is not None and not diagonal \
             and any(type(p) in v for p in kept for v in OPT_IN_DIAGONAL_EMISSIONS.values()):
         kept = None             # the diagonal-emission form is kept only where it is asked for
+    if kept is not None and not states \
+            and any(type(p) in v for p in kept for v in OPT_IN_WIDE_STATES.values()):
+        kept = None             # the wide-state form is kept only where it is asked for
     if kept is not None and not hyper \
             and any(type(p) in v for p in kept for v in OPT_IN_HYPER.values()):
         kept = None             # a form with learnt concentrations is kept only where it is asked for
@@ -309,6 +326,8 @@ def compile_model(nodes, engine=None, **options):
         types = _with_count_emissions(types)
     if diagonal:
         types = _with_diagonal_emissions(types)
+    if states:
+        types = _with_wide_states(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

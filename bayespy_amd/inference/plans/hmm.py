@@ -65,7 +65,8 @@ _KINDS = {'hmm': 'Gaussian', 'hmm_cat': 'categorical',
           'hmm_seg': 'Gaussian (the long-chain form)',
           'hmm_seg_cat': 'categorical (the long-chain form)',
           'hmm_vocab': 'categorical (the large-vocabulary form)',
-          'hmm_mult': 'multinomial', 'hmm_diag': 'diagonal-Gaussian'}
+          'hmm_mult': 'multinomial', 'hmm_diag': 'diagonal-Gaussian',
+          'hmm_states': 'multinomial (the wide-state form)'}
 
 
 def hmm_limits():

@@ -1510,6 +1510,33 @@ int32_t vmp_hmm_mult_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t M, int32_t
                           double *ws, double *z0sum, double *xisum, double *S, double *scal,
                           double *gamma, double *z0, double *zz);
 
+/* Hidden Markov model with multinomial emissions and 65 to 128 states (details:
+ * bayespy_amd/csrc/vmp_hmm_states.hip, vmp_hmm_states_dev.h): the model, the arguments and the
+ * outputs of vmp_hmm_mult_pass.  The emission and statistics kernels are those of that pass with
+ * eight state tiles; the chain stage runs in the domain of scaled probabilities with its K x K
+ * products on the fp64 matrix cores, P = exp(elog_A) resident in LDS, tiles of 16 chains per
+ * workgroup, sum xi kept in accumulator registers.  RANGE: an entry of elog_A below about -745 acts
+ * as -inf (elog_a0 is taken less its maximum first), and a step whose predicted mass underflows
+ * entirely gives NaN, as an impossible observation does.  There is no log-domain fallback.
+ *   vmp_hmm_states_limits (host only): *max_K = 128, *min_K = 65, *max_M = 1024,
+ *     *max_count = 65534.
+ *   vmp_hmm_states_plan (host only): *chains_per_wg (a multiple of 16, a function of B alone) and
+ *     *workspace_doubles: E (B T 128), gamma (B T K), the partials, at most 16384 sums of row
+ *     shifts, 1024.  The status rules of vmp_hmm_mult_plan; K below 65 or above 128:
+ *     VMP_ERR_UNSUPPORTED.
+ *   vmp_hmm_states_pass: the contract of vmp_hmm_mult_pass, argument for argument, for
+ *     65 <= K <= 128 (any other K: VMP_ERR_UNSUPPORTED).  ws: vmp_hmm_states_plan's doubles.  No
+ *     atomics: the bits of every output depend on the inputs and (B, T, M, K) alone, with or
+ *     without the optional outputs; a mask of ones gives the bits of a NULL mask. */
+int32_t vmp_hmm_states_limits(int32_t *max_K, int32_t *min_K, int32_t *max_M, int32_t *max_count);
+int32_t vmp_hmm_states_plan(int64_t B, int32_t T, int32_t M, int32_t K, int64_t *chains_per_wg,
+                            int64_t *workspace_doubles);
+int32_t vmp_hmm_states_pass(vmp_ctx *ctx, int64_t B, int32_t T, int32_t M, int32_t K,
+                            const uint16_t *x_packed, const double *elogPt, const double *elog_a0,
+                            const double *elog_A, const int32_t *labels, const uint8_t *mask,
+                            double *ws, double *z0sum, double *xisum, double *S, double *scal,
+                            double *gamma, double *z0, double *zz);
+
 /* Hidden Markov model with diagonal-Gaussian emissions: every time step carries D real numbers with
  * one precision per dimension (details: bayespy_amd/csrc/vmp_hmm_diag.hip, vmp_hmm_diag_dev.h)
  *     Z = CategoricalMarkovChain(a0, A, states=T);  mu = GaussianARD(m0, beta0, shape=(D,), plates=(K,))

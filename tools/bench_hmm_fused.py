@@ -40,7 +40,7 @@ tests/hmm_models.py, Z from fixed random labels):
            length in use.  --wide-pass then times ``vmp_hmm_wide_pass``, the sequential chain
            stage, on the same state in the same process.
 
-  mult     (--emissions multinomial --engine fused+counts, --M 64,256,1024, --trials n) the legs
+  mult     (--emissions multinomial --engine fused+counts, or fused+states with --K 65 .. 128, --M 64,256,1024, --trials n) the legs
            for the multinomial-emission form (inference/plans/hmm_mult.py): count vectors of n
            trials drawn on the device, learned P, Z from fixed random labels; the pass is
            ``vmp_hmm_mult_pass`` (4 M + 24 KP + 32 K bytes per chain step: the uint16 counts read by
@@ -238,7 +238,7 @@ def multinomial_legs(a, emit, M):
         torch.cuda.reset_peak_memory_stats()
         Q = build_mult(a.engine)
         plan = Q.plans[0]
-        assert type(plan).__name__ == 'MultinomialHMMPlan'
+        assert type(plan).__name__ == ('WideStateMultinomialHMMPlan' if K > 64 else 'MultinomialHMMPlan')
         emit(dict(leg='fused', what='Q.update()',
                   **timed(lambda: Q.update(verbose=False), a.steps, a.warmup)))
         emit(dict(leg='fused_bound', L=float(Q.L[Q.iter - 1]),
@@ -246,7 +246,8 @@ def multinomial_legs(a, emit, M):
         if 'pass' in legs:
             r = timed(lambda: plan._run_pass(refresh=False), a.steps, a.warmup)
             nbytes = 4 * M + 24 * KP + 32 * K
-            emit(dict(leg='pass', what='vmp_hmm_mult_pass', bytes_per_chain_step=nbytes,
+            emit(dict(leg='pass', what='vmp_hmm_states_pass' if K > 64 else 'vmp_hmm_mult_pass',
+                      bytes_per_chain_step=nbytes,
                       GB_per_s=float(B) * T * nbytes / (1e-3 * r['ms_median']) / 1e9,
                       Gflop_per_s_each_product=2.0 * B * T * M * K / (1e-3 * r['ms_median']) / 1e9,
                       **r))
@@ -410,7 +411,7 @@ def main():
                          'in one process')
     ap.add_argument('--engine', default='fused',
                     choices=('fused', 'fused+emissions', 'fused+chains', 'fused+words',
-                             'fused+counts', 'fused+diagonal'))
+                             'fused+counts', 'fused+diagonal', 'fused+states'))
     ap.add_argument('--dims', default='64,256,1024',
                     help='diagonal legs: comma-separated D, the legs once per value; B is capped '
                          'so that y stays at or below 2^30 doubles')
