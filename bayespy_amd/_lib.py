@@ -195,6 +195,17 @@ SIGNATURES = {
     'vmp_gmm_prepare_z_annealed': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f64, c_vp]),
     'vmp_gmm_update_annealed': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f64, c_vp]),
     'vmp_gmm_lower_bound_annealed': (c_i32, [c_vp, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_vp]),
+    'vmp_gmm_hd_get_layout': (c_i32, [c_i32, c_i32, P(GMMLayout)]),
+    'vmp_gmm_hd_workspace_bytes': (c_i32, [c_vp, c_i32, c_i32, P(c_sz)]),
+    'vmp_gmm_hd_init_state': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_f64, c_f64, c_vp, c_vp]),
+    'vmp_gmm_hd_stats_from_labels': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                             c_vp]),
+    'vmp_gmm_hd_update_mu': (c_i32, [c_vp, c_i32, c_i32, c_vp]),
+    'vmp_gmm_hd_update_lambda': (c_i32, [c_vp, c_i32, c_i32, c_vp]),
+    'vmp_gmm_hd_prepare_z': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp]),
+    'vmp_gmm_hd_pass': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'vmp_gmm_hd_update_alpha': (c_i32, [c_vp, c_i32, c_i32, c_vp]),
+    'vmp_gmm_hd_lower_bound': (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     'vmp_sum_multiply': (c_i32, [c_vp, c_i32, P(c_i64), c_i32, P(c_vp), P(c_i64), P(c_i64),
                                  ctypes.c_uint32, c_f64, c_vp, c_vp, c_sz]),
     'vmp_sum_multiply_workspace_bytes': (c_sz, []),

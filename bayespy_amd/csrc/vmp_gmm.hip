@@ -930,13 +930,18 @@ __device__ inline void wave_sum_dd(double &h, double &lo)
 // The temperatures enter as factors of the plain form's own operands, so T = 1 gives its bits;
 // the alpha term keeps the (value, rounding error) evaluation at T = 1.
 constexpr int NTLB = 512;
-template <bool ANN = false>
+// MD: the largest D of the instance (vmp_gmm_hd.hip runs the MD = 64 one; nothing else depends on it)
+template <bool ANN = false, int MD = MAXD>
 __global__ void __launch_bounds__(NTLB)
 gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st, double Tz = 1.0, double Ta = 1.0,
                        double Tm = 1.0, double TL = 1.0)
 {
     __shared__ double red[NTLB / 64];
-    __shared__ double lgs[MAXK][2 * MAXD];         // the log-Gamma values of Lambda, ONE call site
+    // the log-Gamma values of Lambda, ONE call site.  MD <= MAXD: row k holds the D terms of
+    // Gamma_D(n0/2), then those of Gamma_D(n_k/2).  MD > MAXD (two full rows per cluster would be
+    // the whole 64 KB): the terms of n0, the same for every cluster, are kept once, in row MAXK
+    constexpr bool ONE_N0 = MD > MAXD;
+    __shared__ double lgs[ONE_N0 ? MAXK + 1 : MAXK][ONE_N0 ? MD : 2 * MD];
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
     const int KP = (int)L.KP;
     const double beta0 = st[L.off_prior + KP + 0], n0 = st[L.off_prior + KP + 1];
@@ -948,7 +953,12 @@ gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st, double Tz = 1
         double x;
         if (c < D) x = 0.5 * n0 - 0.5 * c;                            // Gamma_D(n0/2) terms
         else x = 0.5 * st[L.off_nk + k] - 0.5 * (c - D);              // Gamma_D(n_k/2) terms
-        lgs[k][c] = vmp_lgamma(x);
+        if constexpr (ONE_N0) {
+            if (c >= D) lgs[k][c - D] = vmp_lgamma(x);
+            else if (k == 0) lgs[MAXK][c] = vmp_lgamma(x);
+        } else {
+            lgs[k][c] = vmp_lgamma(x);
+        }
     }
     __syncthreads();
     const double mgc = (double)D * (D - 1) / 4.0 * log(M_PI);
@@ -987,7 +997,10 @@ gmm_lower_bound_kernel(vmp_gmm_layout L, int D, int K, double *st, double Tz = 1
                        - 0.5 * st[L.off_logdetLmu + k] + 0.5 * (double)D;
             const double nk = st[L.off_nk + k];
             double mg0 = mgc, mgk = mgc;
-            for (int c = 0; c < D; ++c) { mg0 += lgs[k][c]; mgk += lgs[k][D + c]; }
+            for (int c = 0; c < D; ++c) {
+                mg0 += lgs[ONE_N0 ? MAXK : k][c];
+                mgk += lgs[k][ONE_N0 ? c : D + c];
+            }
             const double gp = 0.5 * n0 * ldV0 - 0.5 * D * n0 * log(2.0) - mg0;
             const double gq = 0.5 * nk * st[L.off_logdetV + k] - 0.5 * D * nk * log(2.0) - mgk;
             if constexpr (ANN)
@@ -1203,6 +1216,26 @@ int32_t run_gmm_pass(vmp_ctx *ctx, bool from_labels, const double *Y, int64_t N,
 }
 
 }  // namespace
+
+// for vmp_gmm_hd.hip (declared in vmp_gmm_hd_dev.h): the two kernels of the block that serve D <= 64
+// as they are -- the Dirichlet update does not depend on D, the bound only through a table size
+int32_t vmp_gmm_launch_update_alpha(vmp_ctx *ctx, const vmp_gmm_layout &L, int D, int K,
+                                    double *state)
+{
+    hipLaunchKernelGGL(gmm_update_alpha_kernel<false>, dim3(1), dim3(NT), 0, ctx->stream, L, D, K,
+                       state, 1.0);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
+
+int32_t vmp_gmm_launch_lower_bound_hd(vmp_ctx *ctx, const vmp_gmm_layout &L, int D, int K,
+                                      double *state)
+{
+    hipLaunchKernelGGL((gmm_lower_bound_kernel<false, 64>), dim3(1), dim3(NTLB), 0, ctx->stream, L,
+                       D, K, state, 1.0, 1.0, 1.0, 1.0);
+    VMP_HIP_CHECK(ctx, hipGetLastError());
+    return VMP_OK;
+}
 
 extern "C" {
 

@@ -6,6 +6,7 @@ block and maps the reference's per-node operations (``update``,
 from .pca import PCAPlan
 from .masked_pca import MaskedPCAPlan
 from .gmm import GMMPlan, GMMSVIPlan
+from .gmm_hd import HighDimGMMPlan
 from .lssm import LSSMPlan
 from .lssm_masked import MaskedLSSMPlan
 from .lda import LDAPlan, LDASVIPlan
@@ -116,6 +117,12 @@ OPT_IN_DIAGONAL_EMISSIONS = {HMMPlan: [DiagGaussianHMMPlan]}
 # engine='fused+counts'; every other engine value does not try this form and keeps its answer; it
 # is not combined with the other '+' suffixes
 OPT_IN_WIDE_STATES = {MultinomialHMMPlan: [WideStateMultinomialHMMPlan]}
+# engine='fused+dims': the form of the Gaussian-mixture block for 33 to 64 dimensions
+# (plans/gmm_hd.py: both contractions of the pass as products with the D x D matrices on the matrix
+# cores), a plan class of its own, tried right after that block (which declines D > 32 with a
+# reason).  Everything else is engine='fused'; every other engine value does not try this form and
+# keeps its answer; it is not combined with the other '+' suffixes
+OPT_IN_HIGH_DIMS = {GMMPlan: [HighDimGMMPlan]}
 
 
 def _with_masked(types):
@@ -165,6 +172,11 @@ def _with_wide_states(types):
     return [Q for P in types for Q in [P] + OPT_IN_WIDE_STATES.get(P, [])]
 
 
+def _with_high_dims(types):
+    """``types`` with the plan classes of ``OPT_IN_HIGH_DIMS`` inserted after their block."""
+    return [Q for P in types for Q in [P] + OPT_IN_HIGH_DIMS.get(P, [])]
+
+
 def _with_hyper(types):
     """``types`` with the plan classes of ``OPT_IN_HYPER`` inserted after their form (or after the
     opt-in form that stands in its place), where that form is among ``types``."""
@@ -212,6 +224,7 @@ def _reusable_plans(nodes, engine, options=None):
                                  or any(type(p) in v for v in OPT_IN_COUNT_EMISSIONS.values())
                                  or any(type(p) in v for v in OPT_IN_DIAGONAL_EMISSIONS.values())
                                  or any(type(p) in v for v in OPT_IN_WIDE_STATES.values())
+                                 or any(type(p) in v for v in OPT_IN_HIGH_DIMS.values())
                                  for p in plans):
         return None             # an opt-in form is kept only where it is asked for
     covered = set(id(m) for p in plans for m in p.nodes())
@@ -257,7 +270,8 @@ def compile_model(nodes, engine=None, **options):
     states = engine == 'fused+states'
     counts = engine == 'fused+counts' or states
     diagonal = engine == 'fused+diagonal'
-    if batches or topics or hyper or emissions or chains or words or counts or diagonal:
+    dims = engine == 'fused+dims'
+    if batches or topics or hyper or emissions or chains or words or counts or diagonal or dims:
         engine = 'fused'
     kept = _reusable_plans(nodes, engine, options)
     if kept is not None and not topics \
@@ -281,6 +295,9 @@ def compile_model(nodes, engine=None, **options):
     if kept is not None and not states \
             and any(type(p) in v for p in kept for v in OPT_IN_WIDE_STATES.values()):
         kept = None             # the wide-state form is kept only where it is asked for
+    if kept is not None and not dims \
+            and any(type(p) in v for p in kept for v in OPT_IN_HIGH_DIMS.values()):
+        kept = None             # the high-dimensional form is kept only where it is asked for
     if kept is not None and not hyper \
             and any(type(p) in v for p in kept for v in OPT_IN_HYPER.values()):
         kept = None             # a form with learnt concentrations is kept only where it is asked for
@@ -328,6 +345,8 @@ def compile_model(nodes, engine=None, **options):
         types = _with_diagonal_emissions(types)
     if states:
         types = _with_wide_states(types)
+    if dims:
+        types = _with_high_dims(types)
     remaining = [n for n in nodes]
     plans = []
     progress = True

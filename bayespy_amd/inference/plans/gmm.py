@@ -129,11 +129,21 @@ class GMMPlan:
                 "D <= 32, K <= 64")
 
     @staticmethod
-    def match(nodes, why=None):
+    def _dims(D, K):
+        """What is wrong with (D, K) for this block (the text of a reason), or None."""
+        if D > 32 or K > 64:
+            return 'D = %d, K = %d exceed the limits of the block (D <= 32, K <= 64)' % (D, K)
+        return None
+
+    @staticmethod
+    def match(nodes, why=None, label='fused Gaussian-mixture block', dims_rule=None):
+        """``label`` and ``dims_rule``: the name in the reasons and the rule for (D, K) of another
+        form of the block (plans/gmm_hd.py); the defaults are this block's."""
+        dims_rule = dims_rule or GMMPlan._dims
+
         def no(Y, msg):
             if why is not None:
-                why.append('fused Gaussian-mixture block, observed node %s: %s'
-                           % (Y.name or '<unnamed>', msg))
+                why.append('%s, observed node %s: %s' % (label, Y.name or '<unnamed>', msg))
         # mini-batch multipliers (stochastic VI) go through the generic engine
         if any(any(m != 1 for m in n.plates_multiplier) for n in nodes):
             return None
@@ -161,8 +171,8 @@ class GMMPlan:
                 continue
             N = Y.plates[0]
             K, D = Y.clusters, Y.dims[0][0]
-            if D > 32 or K > 64:
-                no(Y, 'D = %d, K = %d exceed the limits of the block (D <= 32, K <= 64)' % (D, K))
+            if dims_rule(D, K):
+                no(Y, dims_rule(D, K))
                 continue
             if z.plates != (N,) or mu.plates != (K,) or Lam.plates != (K,) or mu.shape != (D,):
                 no(Y, 'plates of z / mu / Lambda are not (N,), (K,), (K,)')

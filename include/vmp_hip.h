@@ -683,6 +683,43 @@ int32_t vmp_gmm_update_annealed(vmp_ctx *ctx, int32_t D, int32_t K, int32_t node
 int32_t vmp_gmm_lower_bound_annealed(vmp_ctx *ctx, int32_t D, int32_t K, double T_z, double T_alpha,
                                      double T_mu, double T_lambda, double *state);
 
+/* ---- the same block for 1 <= D <= 64, K <= 64: the high-dimensional form ---- *
+ *
+ * Every entry point has the signature and the meaning of its vmp_gmm_* namesake and works on a
+ * vmp_gmm_layout state of its own (vmp_gmm_hd_get_layout).  Every field keeps its meaning; DP is D
+ * rounded up to 16, and the coefficient table at off_C is in the NATURAL order of the statistics,
+ * row k = [c_k, h_k (D), -1/2 <Lambda_k> (D x D, symmetric)] with row stride F2P = FP = FS rounded up
+ * to 8 (padded clusters: -inf in the constant slot, zeros elsewhere), so that sum_nk r phi = <C, T>
+ * is one contraction of two tables with the same indexing.  The pass is two plate kernels on the
+ * fp64 matrix cores -- the responsibilities from Z = A_k Y^T and the column sums of Z o Y^T, the
+ * statistics from (r_k o Y)^T Y on the upper 16 x 16 tiles -- and a fixed-order reduce: no atomics,
+ * two calls leave the same bits.  D > 64 or K > 64: VMP_ERR_UNSUPPORTED. */
+int32_t vmp_gmm_hd_get_layout(int32_t D, int32_t K, vmp_gmm_layout *out);
+int32_t vmp_gmm_hd_workspace_bytes(vmp_ctx *ctx, int32_t D, int32_t K, size_t *bytes);
+/* Store the priors and initialise every node from its prior (expfamily.py:168-184). */
+int32_t vmp_gmm_hd_init_state(vmp_ctx *ctx, int32_t D, int32_t K, const double *alpha0_host,
+                              double beta0, double n0, const double *V0_host, double *state);
+/* One-hot responsibilities of given labels (bit-exact) written to R, their statistics to T; the
+ * slots of sum lse and sum r phi are left alone. */
+int32_t vmp_gmm_hd_stats_from_labels(vmp_ctx *ctx, const double *Y, int64_t N, int32_t D, int32_t K,
+                                     const int64_t *labels, double *R, double *state,
+                                     void *workspace);
+/* mu.update() and Lambda.update(): one workgroup per cluster, the D x D matrix in LDS, SPD inverse
+ * by Gauss-Jordan sweeps in pivot order.  A matrix that is not positive definite sets the status
+ * word of the state to VMP_ERR_NOT_POSDEF. */
+int32_t vmp_gmm_hd_update_mu(vmp_ctx *ctx, int32_t D, int32_t K, double *state);
+int32_t vmp_gmm_hd_update_lambda(vmp_ctx *ctx, int32_t D, int32_t K, double *state);
+/* z.update(), replicated half: the coefficient table in the natural order (see above). */
+int32_t vmp_gmm_hd_prepare_z(vmp_ctx *ctx, int32_t D, int32_t K, int32_t prior_only, double *state);
+/* z.update(), plate half: r = normalized_exp(phi) written to R, T = r^T [1, y, y y^T], sum lse and
+ * sum r phi (local partial; the caller all-reduces T and zs). */
+int32_t vmp_gmm_hd_pass(vmp_ctx *ctx, const double *Y, int64_t N, int32_t D, int32_t K, double *R,
+                        double *state, void *workspace);
+/* alpha.update() (the kernel of vmp_gmm_update_alpha: it does not depend on D). */
+int32_t vmp_gmm_hd_update_alpha(vmp_ctx *ctx, int32_t D, int32_t K, double *state);
+/* Lower bound of Y, z, alpha, mu, Lambda (expfamily.py:400-480). */
+int32_t vmp_gmm_hd_lower_bound(vmp_ctx *ctx, int32_t D, int32_t K, double *state);
+
 /* ---- generic plate-broadcast kernels -------------------------------------- *
  *
  * Arrays are fp64 with explicit ELEMENT strides per axis; stride 0 marks a
